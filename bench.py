@@ -3,8 +3,20 @@
 (CyclePose) + pose chain + back-projection on synthetic 640x480 sequences.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype f16|bf16] [--precision accurate|fast]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run (no --full) does only what the headline needs: set-up (weights, frames, pipeline, calibration), W warm-up steps, K timed
+steps of --precision, the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  Its frames are
+made on the device (device_sequence: make_sequence_at's construction, noise from a seeded device generator), so set-up does not grow
+with K.  --full adds everything else described below, as before: the other precision mode, the CPU baseline and the depth check
+against the oracle (frames made on the host by make_sequence, before the first GPU call), per-kernel HIP-event timing and the
+rooflines, the PMC traffic child runs, board power, and the PCIe, outlier-weights, SLAM-loop and latency legs; the --no-* switches
+below select among them.
+--dump-outputs DIR: after the timed steps, what the last timed step computed -- the arrays its caller receives (depth maps, relative
+and absolute poses, point counts, back-projected points; the per-frame arrays for a fixed, seeded sample of the batch's frames, < 64 MB
+in all) -- goes to DIR/<name>.npy in float32 / float64 (rank 0's block at N > 1).  The same arguments give the same inputs.
 
 A step = one pass of the full loop over one batch of B consecutive frames per rank (default B = 128, 2 steps = 256 frames):
   MDEM  B frames -> 2B network forwards (flip-aug) -> B depth maps (fp32 metres + uint16)
@@ -25,7 +37,7 @@ shard_bounds (ragged: 125 frames per rank at 8 GPUs); a step = BodySlamPipeline.
 chain, back-projection of its block); value = K x frames / max-over-ranks time; "scaling": "strong".
 
 The primary line is precision="accurate" (split-precision products, depth L1 vs the fp32 oracle <= 1e-4 m -- the north
-star's tolerance); the single-pass "fast" mode is measured in the same run and reported under "other_mode".
+star's tolerance); with --full the single-pass "fast" mode is measured in the same run and reported under "other_mode".
 
 roofline: per-kernel HIP-event timing of every bs_gemm launch inside the timed steps, aggregated per
 kernel instantiation (tile variant x conv/plain); the dominant one by time is reported against the dense
@@ -69,7 +81,7 @@ def measure_pmc_traffic(args):
     try:
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             cmd = [exe, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", tmp, "-o", counter, "--",
-                   "python3", os.path.join(ROOT, "bench.py"), "--single-mode", "--precision", args.precision, "--steps", "1", "--warmup", "0",
+                   "python3", os.path.join(ROOT, "bench.py"), "--full", "--single-mode", "--precision", args.precision, "--steps", "1", "--warmup", "0",
                    "--batch", str(args.batch), "--dtype", args.dtype, "--height", str(args.height), "--width", str(args.width),
                    "--weights", args.weights, "--weights-seed", str(args.weights_seed), "--no-cpu-baseline", "--no-kernel-timing", "--no-pmc-traffic", "--no-slam-loop", "--no-outlier-leg",
                    "--no-pcie-leg", "--no-latency-leg"]
@@ -170,6 +182,78 @@ class PowerSampler:
                 "source": "amdgpu hwmon power1_average / freq1_input, 25 ms samples over the timed steps (host thread)"}
 
 
+def device_sequence(n: int, h: int, w: int, seed: int, dev, chunk: int = 64) -> torch.Tensor:
+    """[n, h, w, 3] uint8 frames of ONE synthetic sequence, made on `dev`: make_sequence_at's construction (the same eight sinusoids per
+    channel drawn from `seed`, the field cropped along its diagonal, i.e. frame i shifted by i pixels, i.i.d. noise sigma = 8 around 106),
+    with the noise drawn from a device generator seeded with `seed`.  The same arguments give the same frames; a plain run's set-up
+    then costs milliseconds instead of ~17 ms of host time per frame."""
+    rng = np.random.default_rng(seed)
+    terms = [[] for _ in range(3)]
+    for c in range(3):
+        for _ in range(8):
+            fy, fx = rng.uniform(0.002, 0.02, size=2)
+            ph = rng.uniform(0, 2 * np.pi)
+            amp = rng.uniform(5, 20)
+            terms[c].append((float(fy), float(fx), float(ph), float(amp)))
+    yy = np.arange(h + n, dtype=np.float64)[:, None]
+    xx = np.arange(w + n, dtype=np.float64)[:, None]
+    # amp sin(2 pi (fy y + fx x) + ph) = [amp sin(ay), amp cos(ay)] . [cos(bx), sin(bx)]: one [rows, 16] and one [cols, 16] table per channel
+    ytab, xtab = [], []
+    for c in range(3):
+        fy, fx, ph, amp = (np.array([t[j] for t in terms[c]]) for j in range(4))
+        ay = 2 * np.pi * fy[None, :] * yy + ph[None, :]
+        bx = 2 * np.pi * fx[None, :] * xx
+        ytab.append(torch.from_numpy(np.concatenate([np.sin(ay) * amp, np.cos(ay) * amp], 1).astype(np.float32)).to(dev))
+        xtab.append(torch.from_numpy(np.concatenate([np.cos(bx), np.sin(bx)], 1).astype(np.float32)).to(dev))
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    ar_h = torch.arange(h, device=dev)
+    ar_w = torch.arange(w, device=dev)
+    for i0 in range(0, n, chunk):
+        i1 = min(n, i0 + chunk)
+        fi = torch.arange(i0, i1, device=dev)
+        rows, cols = fi[:, None] + ar_h[None, :], fi[:, None] + ar_w[None, :]
+        fr = torch.randn(i1 - i0, h, w, 3, generator=g, device=dev).mul_(8.0).add_(106.0)
+        for c in range(3):
+            a, b = ytab[c][rows], xtab[c][cols]              # [f, h, 16], [f, w, 16]
+            f_c = fr[..., c]
+            for k in range(a.shape[-1]):
+                f_c += a[:, :, k, None] * b[:, None, :, k]
+        out[i0:i1] = fr.round_().clamp_(0, 255).to(torch.uint8)
+    return out
+
+
+def dump_outputs(path: str, last: dict, H: int, W: int):
+    """The last timed step's outputs as float32 / float64 .npy files under `path`.  Per-frame arrays (depth maps, back-projected points)
+    for a fixed, seeded sample of the step's frames, sized to stay below 64 MB in all; per-step arrays (poses, point counts) whole.
+    points_xyz / points_idx: the first count entries of a frame are its points (backproject's layout), the rest NaN / -1."""
+    os.makedirs(path, exist_ok=True)
+    n = int(last["depth_u16"].shape[0])
+    per_frame = H * W * 4 * (1 + 1 + 3 + 1)                 # depth_m, depth_u16, xyz, idx as float32
+    n_sample = max(1, min(n, 8, (56 << 20) // per_frame))
+    sample = np.sort(np.random.default_rng(0).choice(n, size=n_sample, replace=False))
+    sel = torch.from_numpy(sample).to(last["depth_u16"].device)
+    arrays = {}
+    if last.get("depth_m") is not None:
+        arrays["depth_m"] = last["depth_m"].index_select(0, sel).float().cpu().numpy()
+    arrays["depth_u16"] = last["depth_u16"].index_select(0, sel).cpu().numpy().view(np.uint16).astype(np.float32)
+    arrays["t_rel"] = last["t_rel"].float().cpu().numpy()
+    arrays["g_abs"] = last["g_abs"].double().cpu().numpy()
+    counts = last["counts"].cpu().numpy()
+    arrays["point_counts"] = counts.astype(np.float64)
+    if last.get("xyz") is not None:
+        xyz = last["xyz"].index_select(0, sel).cpu().numpy().astype(np.float32)
+        idx = last["idx"].index_select(0, sel).cpu().numpy().astype(np.float32)
+        for r, j in enumerate(sample):
+            xyz[r, counts[j]:] = np.nan
+            idx[r, counts[j]:] = -1.0
+        arrays["points_xyz"], arrays["points_idx"] = xyz, idx
+    arrays["sample_frames"] = sample.astype(np.float64)       # which frames of the step the per-frame arrays hold
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def weak_frame_indices(steps: int, B: int, world: int, rank: int):
     """N > 1, weak scaling: (frames of the ONE sequence, the indices rank `rank` holds).  Step k gives rank r the B frames
     (k * world + r) * B + 1 .. + B and, in front of them, the frame before (its halo = the last frame of rank r - 1's block of the same
@@ -214,7 +298,19 @@ def main():
     ap.add_argument("--no-latency-leg", action="store_true", help="skip the extra `latency_b1_ms` figures (one frame / one pair per call: the reference's call pattern)")
     ap.add_argument("--no-pmc-traffic", action="store_true",
                     help="skip the two rocprofv3 --pmc child runs (FETCH_SIZE, WRITE_SIZE) that measure roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline (other mode, CPU baseline + oracle depth check, kernel timing and rooflines, PMC "
+                         "traffic, power, PCIe / outlier / SLAM-loop / latency legs); without it only --precision's timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, a seeded sample of the per-frame arrays)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # the plain run: the headline's timed steps only (the --no-* switches all on, one precision mode)
+        args.single_mode = True
+        args.no_cpu_baseline = args.no_slam_loop = args.no_kernel_timing = args.no_pmc_traffic = True
+        args.no_outlier_leg = args.no_pcie_leg = args.no_latency_leg = True
 
     if args.dtype == "bf16" and args.precision == "accurate":
         # BASELINE config 2 names bf16.  With e4m3 correction planes bf16 storage carries 8 + 4 significant bits -- fp16's single pass -- and
@@ -270,7 +366,10 @@ def main():
         nmax = max(e - s for s, e in bounds)
         B = -(-nmax // (-(-nmax // B)))
         foff = max(s0 - 1, 0)
-        frames = torch.from_numpy(make_sequence(Nseq, H, W, seed=0)[foff:e0]).to(dev)    # the rank's block + halo, resident in HBM
+        if args.full:
+            frames = torch.from_numpy(make_sequence(Nseq, H, W, seed=0)[foff:e0]).to(dev)    # the rank's block + halo, resident in HBM
+        else:
+            frames = device_sequence(Nseq, H, W, 0, dev)[foff:e0].clone()
         n_frames = Nseq
     else:
         n_frames = (K + Wm) * B + 1
@@ -330,7 +429,7 @@ def main():
         frames = frames_host.to(dev)
         del frames_host
     elif frames is None:
-        frames = torch.from_numpy(make_sequence(n_frames, H, W, seed=0)).to(dev)
+        frames = torch.from_numpy(make_sequence(n_frames, H, W, seed=0)).to(dev) if args.full else device_sequence(n_frames, H, W, 0, dev)
     pairs = torch.tensor([[i, i + 1] for i in range(B)], dtype=torch.int32, device=dev)
 
     def barrier():
@@ -338,10 +437,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(precision, wz=wz, K=K, Wm=Wm, host_io=False, pipe=None, samples=()):
+    def measure(precision, wz=wz, K=K, Wm=Wm, host_io=False, pipe=None, samples=(), keep_last=False):
         """W warm-up + K timed steps of the whole loop in one precision mode -> (pipeline, plan, fps, elapsed, rooflines, table).
         host_io: the PCIe-inclusive variant -- every step's frames come from pinned host memory and its depth maps (uint16), point counts and
-        relative poses go back to pinned host buffers, all on the compute stream (nothing overlapped: the conservative figure)."""
+        relative poses go back to pinned host buffers, all on the compute stream (nothing overlapped: the conservative figure).
+        keep_last: the result's "last" holds the last step's outputs (references only: nothing is copied inside the timed steps)."""
         if pipe is None:
             pipe = BodySlamPipeline(wz, wp, cfg, dtype=dtype, device=local_rank, batch=B, precision=precision)
         pipe.calibrate(H, W)        # the correction modes: measured once by rank 0 on the device and shared (every rank runs the same arithmetic)
@@ -361,6 +461,8 @@ def main():
             zplan.plan.events = events if timed_kernels else None
             if strong:      # the whole sequence: this rank's block through run_sequence (all-gather + chain + back-projection inside)
                 res = pipe.run_sequence(frames, rank, world, frame_offset=foff, n_frames=Nseq)
+                if keep_last:
+                    state["last"] = dict(depth_u16=res.depth_u16, t_rel=res.t_rel, g_abs=res.g_abs, counts=res.point_counts)
                 return res.point_counts
             chunk = frames[k * B: (k + 1) * B + 1] if world == 1 else frames[weak_chunk(k, B)]     # halo frame + B frames
             if host_io:
@@ -386,13 +488,15 @@ def main():
                 h_depth.copy_(zplan.depth_u16, non_blocking=True)
                 h_cnt.copy_(cnt, non_blocking=True)
                 h_T.copy_(pplan.T.view(B, 16), non_blocking=True)
+            if keep_last:       # (the plan's own buffers hold the last step's maps and relatives until the plan runs again)
+                state["last"] = dict(depth_m=zplan.depth_m, depth_u16=zplan.depth_u16, t_rel=pplan.T, g_abs=g_abs, counts=cnt, xyz=xyz, idx=idx)
             return cnt
 
         for k in range(Wm):
             step(k, False)
         barrier()
         sampler = None
-        if rank == 0:
+        if rank == 0 and args.full:
             pr = torch.cuda.get_device_properties(local_rank)
             pci = ("%04x:%02x:%02x.0" % (getattr(pr, "pci_domain_id", 0), pr.pci_bus_id, pr.pci_device_id)) if hasattr(pr, "pci_bus_id") else None
             sampler = PowerSampler(pci).start()
@@ -503,10 +607,13 @@ def main():
                                  executed=round(tf(st["ex"], st["ms"]), 1), executed_frac=round(tf(st["ex"], st["ms"]) / MFMA_PEAK_TFLOPS, 4),
                                  conv_mode_only=(dict(achieved=round(tf(cfl, cms), 1), frac=round(tf(cfl, cms) / MFMA_PEAK_TFLOPS, 4),
                                                       executed_frac=round(tf(cex, cms) / MFMA_PEAK_TFLOPS, 4), ms_per_step=round(cms / K, 3)) if cms > 0 else None))
-        return dict(pipe=pipe, zplan=zplan, fps=fps, elapsed=elapsed, roof=roof, roof_conv=roof_conv, kern=kern_table, d_timed=d_timed, power=power)
+        return dict(pipe=pipe, zplan=zplan, fps=fps, elapsed=elapsed, roof=roof, roof_conv=roof_conv, kern=kern_table, d_timed=d_timed, power=power,
+                    last=state.get("last"))
 
     samples = sorted(oracle_d)
-    main_run = measure(args.precision, samples=samples)
+    main_run = measure(args.precision, samples=samples, keep_last=args.dump_outputs is not None)
+    if args.dump_outputs is not None and rank == 0:      # (before any other leg runs a plan again)
+        dump_outputs(args.dump_outputs, main_run.pop("last"), H, W)
     pipe, zplan, fps, elapsed = main_run["pipe"], main_run["zplan"], main_run["fps"], main_run["elapsed"]
     roof, roof_conv, kern_table = main_run["roof"], main_run["roof_conv"], main_run["kern"]
     other = None
@@ -666,6 +773,7 @@ def main():
                             if pipe.zoe.acc else None),
             "hbm_allocated_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1),
             "power": main_run.get("power"),
+            "full": args.full,
         }
         if slam:
             out["slam_loop"] = slam

@@ -4,7 +4,7 @@ import json
 import subprocess
 import sys
 
-out = subprocess.run([sys.executable, "bench.py", *sys.argv[1:]], capture_output=True, text=True)
+out = subprocess.run([sys.executable, "bench.py", "--full", *sys.argv[1:]], capture_output=True, text=True)
 lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
 if not lines:
     print(out.stdout[-2000:], out.stderr[-4000:])

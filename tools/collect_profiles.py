@@ -3,7 +3,7 @@
 
     cd /tmp && TMPDIR=/tmp python $REPO/tools/collect_profiles.py r02        -> $REPO/gpurun_out/r02/*
 
-  <tag>_bench_n1.json                    python3 bench.py                                       (the default line)
+  <tag>_bench_n1.json                    python3 bench.py --full                                (the default line + everything else)
   <tag>_bench_strong_n1.json             python3 bench.py --scaling strong --single-mode --steps 2
   <tag>_bench_kernel_stats_<mode>.csv    rocprofv3 --kernel-trace --stats -- python3 bench.py --single-mode --precision <mode> ...
   <tag>_pmc_hbm_traffic.json             two more runs per mode with --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), folded
@@ -16,10 +16,11 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
-COMMON = ["--single-mode", "--no-cpu-baseline", "--no-kernel-timing", "--no-pmc-traffic", "--no-slam-loop"]
+COMMON = ["--full", "--single-mode", "--no-cpu-baseline", "--no-kernel-timing", "--no-pmc-traffic", "--no-slam-loop"]
 
 
 def run(cmd, log):
@@ -55,9 +56,9 @@ def main(tag, only_stats=False):
     rp = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not only_stats:
         with open(os.path.join(out, f"{tag}_bench_n1.json"), "w") as f:
-            subprocess.run(["python3", BENCH], cwd="/tmp", stdout=f, stderr=open(os.path.join(out, "bench_n1.err"), "w"))
+            subprocess.run(["python3", BENCH, "--full"], cwd=tempfile.gettempdir(), stdout=f, stderr=open(os.path.join(out, "bench_n1.err"), "w"))
         with open(os.path.join(out, f"{tag}_bench_strong_n1.json"), "w") as f:
-            subprocess.run(["python3", BENCH, "--scaling", "strong", "--single-mode", "--steps", "2", "--warmup", "1", "--no-pmc-traffic"],
+            subprocess.run(["python3", BENCH, "--full", "--scaling", "strong", "--single-mode", "--steps", "2", "--warmup", "1", "--no-pmc-traffic"],
                            cwd="/tmp", stdout=f, stderr=open(os.path.join(out, "bench_strong.err"), "w"))
     traffic, busy = {"modes": {}}, {"modes": {}}
     for mode in ("accurate", "fast"):

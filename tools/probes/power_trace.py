@@ -44,7 +44,7 @@ def main():
         print(subprocess.run(["rocm-smi", "--showpower", "--showclocks", "--showmaxpower"], capture_output=True, text=True).stdout[-3000:])
         return
     idle = {h: sample(h) for h in hs}
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--single-mode", "--no-slam-loop", "--no-pmc-traffic", "--no-outlier-leg", "--no-pcie-leg",
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--single-mode", "--no-slam-loop", "--no-pmc-traffic", "--no-outlier-leg", "--no-pcie-leg",
             "--steps", "12", "--warmup", "2"] + sys.argv[1:]
     t0 = time.time()
     child = subprocess.Popen(args, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, cwd=ROOT)

@@ -3,7 +3,7 @@
 # calibration chose, its figures on the calibration and hold-out frames.   bash tools/probes/seed_throughput.sh > profiles/rNN_seed_throughput.txt
 cd "$(dirname "$0")/../.."
 for s in ${SEEDS:-0 1 2 3 4 5 6 7 8}; do
-    python3 bench.py --single-mode --no-pmc-traffic --no-slam-loop --no-cpu-baseline --weights-seed $s --steps 3 --warmup 1 2>/dev/null | python3 -c "
+    python3 bench.py --full --single-mode --no-pmc-traffic --no-slam-loop --no-cpu-baseline --weights-seed $s --steps 3 --warmup 1 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.readline())
 c = d['calibration'] or {}
