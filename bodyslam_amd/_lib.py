@@ -123,6 +123,9 @@ _SIGS = {
     "bs_pose_chain": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pose_chain_from": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pixel_to_3d": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_depth_metrics_workspace": [C.c_int32, C.c_int32, C.c_int32],
+    "bs_depth_metrics": [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_double, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                                                       C.c_void_p, C.c_void_p],
 }
 EXPORTS = sorted(list(_SIGS) + ["bs_last_error"])
 
@@ -144,6 +147,7 @@ def load_library() -> C.CDLL:
     lib.bs_last_error.restype = C.c_char_p
     lib.bs_last_error.argtypes = []
     lib.bs_engine_device_bytes.restype = C.c_int64
+    lib.bs_depth_metrics_workspace.restype = C.c_int64
     _lib = lib
     return lib
 
@@ -741,3 +745,23 @@ def pose_chain_from(t_rel, N, g0_dev, g_abs):
 def pixel_to_3d(uvd, K4, out, n):
     Karr = (C.c_double * 4)(*[float(v) for v in K4])
     check(load_library().bs_pixel_to_3d(p(uvd), n, C.cast(Karr, C.c_void_p), p(out), stream_ptr()), "bs_pixel_to_3d")
+
+
+DEPTH_SCALE_MEDIAN, DEPTH_SCALE_FIXED = 0, 1
+DEPTH_METRICS_FIELDS = 16
+
+
+def depth_metrics(pred, gt, gt_lo, gt_hi, scale, workspace, out):
+    """pred, gt: int16 / uint16 [B, H, W] device tensors (uint16 values); scale None = the per-frame median scale, else the fixed value;
+    workspace: uint8 device tensor of at least depth_metrics_workspace(B, H, W) bytes; out: fp64 [B, DEPTH_METRICS_FIELDS]
+    (include/bodyslam_hip.h)"""
+    B, H, W = pred.shape
+    assert tuple(gt.shape) == (B, H, W) and pred.is_contiguous() and gt.is_contiguous()
+    assert out.dtype == torch.float64 and tuple(out.shape) == (B, DEPTH_METRICS_FIELDS) and out.is_contiguous()
+    mode = DEPTH_SCALE_MEDIAN if scale is None else DEPTH_SCALE_FIXED
+    check(load_library().bs_depth_metrics(p(pred), p(gt), B, H, W, float(gt_lo), float(gt_hi), mode, 0.0 if scale is None else float(scale),
+                                          p(workspace), workspace.numel() * workspace.element_size(), p(out), stream_ptr()), "bs_depth_metrics")
+
+
+def depth_metrics_workspace(B: int, H: int, W: int) -> int:
+    return int(load_library().bs_depth_metrics_workspace(B, H, W))

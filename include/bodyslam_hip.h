@@ -489,6 +489,29 @@ int bs_odo_accumulate(const float* src_intensity, const float* src_depth, const 
                       const double* K, const double* T, double depth_outlier_trunc, double depth_huber, double intensity_huber,
                       double* partial, double* out29, int32_t flags, void* stream);
 
+/* ---- depth evaluation with the reference's MDEM protocol ----------------------------------------------------------------------------
+ * Replaces the per-frame body of compute_metrics_for (BodySLAM_not_refactored/EVALUATION/MDEM_eval.py:179-197 masking and median
+ * scaling with compute_median_scale_factor :114-127; the MDEM_Metrics functions of EVALUATION/evaluation_metrics.py:24-102).
+ * pred, gt: uint16 [B, H, W] (device; pred = depth in metres*256 as bs_zoedepth_forward writes it, gt in dataset units).  Per frame, fp64:
+ *   mask      gt_lo < gt < gt_hi on GT only (Hamlyn (1, 300), SCARED (0, inf), EndoSlam no mask: (-inf, inf); NaN bounds: empty)
+ *   scale     BS_DEPTH_SCALE_MEDIAN: s = median(gt[mask]) / median(pred[mask]), numpy's median (the mean of the two middle values for an
+ *             even count); BS_DEPTH_SCALE_FIXED: s = `scale`.  p = s * pred
+ *   metrics   over the masked pixels: abs_rel = mean |g - p| / g, sq_rel = mean (g - p)^2 / g, rmse = sqrt(mean (g - p)^2) over
+ *             g != 0 with p not NaN (np.nanmean skips NaN terms); rmse_log = sqrt(mean (log g - log p)^2) and delta_k = the fraction
+ *             with max(g / p, p / g) < 1.25^(2k) (the reference squares its criterion 1.25^k) over g > 0 and p > 0.  log g is the
+ *             fp32 logarithm of g (numpy takes np.log of a uint16 array in fp32), log p fp64.  An empty mask gives NaN medians and NaN
+ *             metrics; median(pred) = 0 gives s = inf, IEEE arithmetic as numpy's
+ * out: fp64 [B, BS_DEPTH_METRICS_FIELDS] (device), per frame: 0 abs_rel, 1 sq_rel, 2 rmse, 3 rmse_log, 4 delta_1, 5 delta_2, 6 delta_3,
+ *   7 scale, 8 median(gt[mask]), 9 median(pred[mask]), 10 n_mask (masked pixels), 11 n_valid (terms of 0-2), 12 n_pos (terms of 3-6),
+ *   13-15 zero.  A frame's record has the same bits in every run, alone or at any position of any batch (fixed summation order).
+ * workspace: device memory of bs_depth_metrics_workspace(B, H, W) bytes (>= workspace_bytes is checked), reused across calls on one
+ * stream.  Six launches and one memset on `stream`, nothing else. */
+enum { BS_DEPTH_SCALE_MEDIAN = 0, BS_DEPTH_SCALE_FIXED = 1 };
+#define BS_DEPTH_METRICS_FIELDS 16
+int64_t bs_depth_metrics_workspace(int32_t B, int32_t H, int32_t W);
+int bs_depth_metrics(const uint16_t* pred, const uint16_t* gt, int32_t B, int32_t H, int32_t W, double gt_lo, double gt_hi, int32_t scale_mode,
+                     double scale, void* workspace, int64_t workspace_bytes, double* out, void* stream);
+
 /* ---- engine files: the forward of a whole model for a host without Python ------------------------------------
  * The reference's hosts are DepthEstimator.infer_depth_map (BodySLAM_Refactored/src/depth_estimation/interface.py:39-45) and
  * MPEMInterface.infer_relative_pose_between (BodySLAM_not_refactored/MPEM/mpem_interface.py:61-99), both Python.  A plan -- the launch
