@@ -562,8 +562,9 @@ def conv_geom(Hin, Win, Cin, KH, KW, stride, pad):
     return (Hin, Win, Cin, Hout, Wout, KH, KW, stride, pad, pad)
 
 
-def attention(q, k, vt, bias, out, B, nh, S, Sp):
-    check(load_library().bs_attention(p(q), p(k), p(vt), p(bias), p(out), B, nh, S, Sp, dt(q), stream_ptr()), "bs_attention")
+def attention(q, k, vt, bias, out, B, nh, S, Sp, split=0):
+    """split: 0 = rows [B*S, nh*64]; 16 = (hi | lo) 16-bit pairs, 32 = (hi16 | hi8 | lo8) planes, rows [B*S, 2*nh*64]"""
+    check(load_library().bs_attention(p(q), p(k), p(vt), p(bias), p(out), B, nh, S, Sp, dt(q) | split, stream_ptr()), "bs_attention")
 
 
 def attention_table(q, k, vt, table, out, B, nh, hp, wp, Sp, split=0, grouped=0):

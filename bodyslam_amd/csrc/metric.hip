@@ -401,7 +401,7 @@ __global__ __launch_bounds__(256) void logbinom_kernel(const T* last, const floa
 }
 
 // ---------------------------------------------------------------------------------------------
-// router pieces: small multi-head attention (S <= 256, head_dim 32, no mask), argmax
+// router pieces: small multi-head attention (S <= 512, head_dim 32, no mask), argmax
 // qkv fp32 [B*S, 3*D] (q | k | v), out 16-bit [B*S, D]
 // ---------------------------------------------------------------------------------------------
 template <typename T>
@@ -558,14 +558,18 @@ extern "C" int bs_small_attention(const float* qkv, void* out, int32_t B, int32_
     BS_REQUIRE(qkv && out && B >= 0 && S > 0 && S <= 512 && nheads > 0, "bs_small_attention: bad argument");
     BS_REQUIRE(dtype == BS_F16 || dtype == BS_BF16, "bs_small_attention: dtype");
     if (B == 0) return BS_OK;
-    const size_t smem = (size_t)2 * S * 33 * sizeof(float);
-    BS_REQUIRE(smem <= 64 * 1024, "bs_small_attention: S too large for LDS");
+    // K and V rows of one (image, head), 32 floats each, unpadded: 256 bytes per token -- the router's 1 + (h/32)(w/32) tokens of a 384x672
+    // network input (253) need 63.25 KiB, of a 672x512 one (337) 84.25 KiB: more than the default 64 KiB of dynamic LDS
+    const size_t smem = (size_t)2 * S * 32 * sizeof(float);
     const float scale = 1.0f / sqrtf(32.0f);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == BS_F16)
+    if (dtype == BS_F16) {
+        BS_MAX_DYNAMIC_LDS(reinterpret_cast<const void*>(small_attention_kernel<f16>), 128 * 1024);
         hipLaunchKernelGGL(small_attention_kernel<f16>, dim3(B * nheads), dim3(256), smem, st, qkv, (f16*)out, S, nheads, scale);
-    else
+    } else {
+        BS_MAX_DYNAMIC_LDS(reinterpret_cast<const void*>(small_attention_kernel<bf16>), 128 * 1024);
         hipLaunchKernelGGL(small_attention_kernel<bf16>, dim3(B * nheads), dim3(256), smem, st, qkv, (bf16*)out, S, nheads, scale);
+    }
     BS_CHECK_LAUNCH();
     return BS_OK;
 }

@@ -497,6 +497,144 @@ def test_qkv_scatter_and_attention(L, dtype, B, S, nh):
     assert err < (4e-3 if dtype == torch.float16 else 3e-2)
 
 
+def _attn_operands(B, nh, S, dtype, seed):
+    """bs_attention's operands as the image-major plan lays them out: Q (log2(e) / sqrt(64) folded in), K [B, nh, Sp, 64] and
+    V^T [B, nh, 64, Sp] with zeros past S; the log2-domain bias [nh, Sp, Sp] as _rel_bias builds it: -1e30 in the padded key
+    columns, 0 in the padded query rows."""
+    Sp = (S + 63) // 64 * 64
+    g = torch.Generator(device=dev()).manual_seed(seed)
+    q = torch.zeros(B, nh, Sp, 64, device=dev(), dtype=dtype)
+    k = torch.zeros(B, nh, Sp, 64, device=dev(), dtype=dtype)
+    vt = torch.zeros(B, nh, 64, Sp, device=dev(), dtype=dtype)
+    q[:, :, :S] = (torch.randn(B, nh, S, 64, generator=g, device=dev()) * (0.25 * LOG2E)).to(dtype)
+    k[:, :, :S] = torch.randn(B, nh, S, 64, generator=g, device=dev()).to(dtype)
+    vt[:, :, :, :S] = torch.randn(B, nh, 64, S, generator=g, device=dev()).to(dtype)
+    bias = torch.full((nh, Sp, Sp), -1.0e30, device=dev())
+    bias[:, :S, :S] = torch.randn(nh, S, S, generator=g, device=dev()) * LOG2E
+    bias[:, S:, :S] = 0.0
+    return q, k, vt, bias, Sp
+
+
+def _attn_ref64(q, k, vt, bias, S):
+    """fp64 softmax attention on exactly the 16-bit operands and fp32 bias the kernel reads (scores in the log2 domain) -> [B*S, nh*64]"""
+    B, nh = q.shape[0], q.shape[1]
+    s = q[:, :, :S].double() @ k[:, :, :S].double().transpose(2, 3) + bias[None, :, :S, :S].double()
+    a = torch.softmax(s * math.log(2.0), dim=-1)
+    return (a @ vt[:, :, :, :S].double().transpose(2, 3)).permute(0, 2, 1, 3).reshape(B * S, nh * 64)
+
+
+def _half_ulp(hi, dtype):
+    """half a unit in the last place of the 16-bit values `hi` (fp64; below the normal range: half the subnormal step)"""
+    mant, emin = (10, -14) if dtype == torch.float16 else (7, -126)
+    _, e = torch.frexp(hi.float())                         # |hi| = m 2^e, m in [0.5, 1)
+    e = torch.where(hi == 0, torch.full_like(e, emin), e - 1).clamp(min=emin)
+    return ((e - mant - 1 + 1023).long() << 52).view(torch.float64)       # 2^(e - mant - 1) from its bits (a device pow may be 1 ulp off)
+
+
+# (B, nh, S): the image-major windows of the full-size plans -- 24x24 (320x320 frames), 24x30 (288x360), 24x42 (16:9), 42x32 (640 tall x 480
+# wide) -- and toy lengths for the 4-wave (S 25, 50, 120) and 3-wave (65, 96) blocks and other S % 64 tails
+ATTN_GENERIC = [(2, 16, 24 * 24 + 1), (2, 16, 24 * 30 + 1), (2, 16, 24 * 42 + 1), (2, 16, 42 * 32 + 1),
+                (3, 2, 25), (3, 2, 50), (2, 4, 65), (2, 4, 96), (3, 2, 120)]
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("B,nh,S", ATTN_GENERIC)
+def test_attention_against_fp64_all_outputs(L, dtype, B, nh, S):
+    """bs_attention (the image-major path's kernel: host-built [nh, Sp, Sp] bias, cls first, natural order) against fp64, in its three
+    output formats.  Plain rows to the 16-bit bound; the (hi | lo) pairs and (hi16 | hi8 | lo8) planes of accurate mode: hi16 the plain
+    output bit for bit, lo within half an ulp of hi, lo8 the split-16 lo to e4m3 precision (the plain bound cannot see a lost lo8 plane);
+    rows past B*S never written."""
+    q, k, vt, bias, Sp = _attn_operands(B, nh, S, dtype, seed=S)
+    ref = _attn_ref64(q, k, vt, bias, S)
+    hid, G, fill = nh * 64, 37, -3.0
+    outs = {}
+    for split in (0, 16, 32):
+        out = torch.full((B * S + G, hid * (2 if split else 1)), fill, device=dev(), dtype=dtype)
+        L.attention(q, k, vt, bias, out, B, nh, S, Sp, split=split)
+        assert (out[B * S:] == fill).all(), f"split {split}: rows past B*S = {B * S} were written"
+        outs[split] = out[:B * S]
+    lim = 4e-3 if dtype == torch.float16 else 3e-2
+    err = (outs[0].double() - ref).abs().max().item()
+    hi, lo = outs[16][:, :hid], outs[16][:, hid:]
+    assert torch.equal(hi.view(torch.int16), outs[0].view(torch.int16)), "split 16: hi differs from the plain output"
+    assert torch.equal(outs[32][:, :hid].view(torch.int16), outs[0].view(torch.int16)), "split 32: hi16 differs from the plain output"
+    pair = hi.double() + lo.double()
+    err_pair = (pair - ref).abs().max().item()
+    over = (lo.double().abs() - _half_ulp(hi, dtype)).max().item()
+    planes = outs[32][:, hid:].contiguous().view(torch.uint8)
+    hi8 = planes[:, :hid].contiguous().view(torch.float8_e4m3fn).float().double() * 2.0 ** -L.F8_ACT_HI_EXP
+    lo8 = planes[:, hid:].contiguous().view(torch.float8_e4m3fn).float().double() * 2.0 ** -L.F8_ACT_LO_EXP
+    err_hi8 = (hi8 - ref).abs().max().item()
+    lo8_excess = ((lo8 - lo.double()).abs() - (2.0 ** -4 * lo.double().abs() + 2.0 ** -9 * 2.0 ** -L.F8_ACT_LO_EXP)).max().item()
+    report(f"attention generic {dtype} B{B} S{S} nh{nh}: max|err| plain {err:.3e}, hi+lo {err_pair:.3e}, hi8 {err_hi8:.3e}; "
+           f"|lo| - ulp/2 max {over:.1e}, |lo8 - lo| over bound max {lo8_excess:.1e} (ref max {ref.abs().max().item():.2f})")
+    assert err < lim
+    assert over <= 0, "split 16: |lo| exceeds half an ulp of hi"
+    assert err_pair < lim
+    assert err_hi8 < 0.07 * ref.abs().max().item() + 1e-2
+    assert lo8_excess <= 0, "split 32: hi16 + lo8 is not hi + lo of the split-16 output to e4m3 precision"
+
+
+@pytest.mark.parametrize("S", [24 * 24 + 1, 96])
+def test_attention_running_max_moves_in_both_lane_halves(L, S):
+    """test_attention_table_running_max_moves_in_both_lane_halves in bs_attention's layout (cls first, natural order): a key that far
+    out-scores the rest moves the deferred running max in whichever lane half holds it (key % 32 in 8..15, 24..31: the upper half of
+    the wave), and an EARLY spike leaves its query's running max far above every later tile: when another query of the same 32-query
+    tile moves its max afterwards (the partner spike), the shift of the early query must not go negative (exp2(+190) overflowed)."""
+    dtype = torch.float16
+    B, nh = 1, 2
+    Sp = (S + 63) // 64 * 64
+    g = torch.Generator().manual_seed(7)
+    qf = torch.randn(B, nh, S, 64, generator=g) * 0.3
+    kf = torch.randn(B, nh, S, 64, generator=g)
+    vf = torch.randn(B, nh, S, 64, generator=g)
+    late = [(S - 1 - 64 + 9, 5), (S - 1 - 32 + 27, 40), (S - 1 - 32 + 2, 70)]          # (key, query): upper, upper, lower lane half
+    early = [(109, 200), (S - 1 - 64 + 30, 210)] if S > 256 else [(9, 80), (S - 1 - 32 + 28, 85)]
+    for pos, qpos in late + early:
+        kf[0, :, pos] = qf[0, :, qpos] / qf[0, :, qpos].norm(dim=-1, keepdim=True) * 60.0
+    q = torch.zeros(B, nh, Sp, 64, device=dev(), dtype=dtype)
+    k = torch.zeros_like(q)
+    vt = torch.zeros(B, nh, 64, Sp, device=dev(), dtype=dtype)
+    q[:, :, :S] = (qf * LOG2E).to(dtype).to(dev())
+    k[:, :, :S] = kf.to(dtype).to(dev())
+    vt[:, :, :, :S] = vf.transpose(2, 3).to(dtype).to(dev())
+    bias = torch.full((nh, Sp, Sp), -1.0e30, device=dev())
+    bias[:, :S, :S] = (torch.randn(nh, S, S, generator=g) * LOG2E).to(dev())
+    bias[:, S:, :S] = 0.0
+    out = torch.zeros(B * S, nh * 64, device=dev(), dtype=dtype)
+    L.attention(q, k, vt, bias, out, B, nh, S, Sp)
+    assert torch.isfinite(out.float()).all(), "exp2 overflowed: the running max did not follow a spiked key"
+    ref = _attn_ref64(q, k, vt, bias, S)
+    err = (out.double() - ref).abs().max().item()
+    report(f"attention generic spiked keys S{S}: max|err|={err:.3e}")
+    assert err < 6e-3
+
+
+def test_attention_is_deterministic_at_scale(L):
+    """bs_attention at the bench's batch (128 network inputs, 16 heads) on the 16:9 and portrait windows: three runs give the same bits,
+    and images 0, 63 and 127 run alone give their rows of the batch (the table kernel's B = 128 test, for the generic kernel)."""
+    dtype = torch.float16
+    B, nh = 128, 16
+    for S in (24 * 42 + 1, 42 * 32 + 1):
+        q, k, vt, bias, Sp = _attn_operands(B, nh, S, dtype, seed=3)
+        for split in (0, 32):
+            width = nh * 64 * (2 if split else 1)
+
+            def run(qq, kk, vv, b):
+                out = torch.zeros(b * S, width, device=dev(), dtype=dtype)
+                L.attention(qq, kk, vv, bias, out, b, nh, S, Sp, split=split)
+                return out.view(torch.int16)       # (bits: FP8 plane bytes read as 16-bit values may be NaN patterns)
+            a = run(q, k, vt, B)
+            for _ in range(2):
+                assert torch.equal(run(q, k, vt, B), a), f"bs_attention is not deterministic at B = {B} (S {S}, split {split})"
+            for b in (0, 63, B - 1):
+                one = run(q[b:b + 1].contiguous(), k[b:b + 1].contiguous(), vt[b:b + 1].contiguous(), 1)
+                assert torch.equal(one, a[b * S:(b + 1) * S]), f"image {b} of the batch differs from the same image alone (S {S}, split {split})"
+            del a
+        del q, k, vt, bias
+        torch.cuda.empty_cache()
+
+
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("B,hp,nh,split,grouped", [(2, 24, 16, 0, 0), (1, 26, 4, 0, 0), (3, 3, 2, 0, 0), (2, 24, 2, 16, 0), (2, 24, 2, 32, 0),
                                                    (3, 24, 2, 32, 256), (2, 4, 2, 0, 2),
@@ -728,10 +866,14 @@ def test_layernorm_and_cast(L, dtype, rows, cols):
     assert torch.equal(c, x.to(dtype))
 
 
+# (frame H, W, network input nh, nw): the table path's two inputs and the image-major path's square, 16:9 and portrait ones
+PRE_POST_GEOMS = [(480, 640, 384, 512), (480, 600, 416, 512), (320, 320, 384, 384), (720, 1280, 384, 672), (640, 480, 672, 512)]
+
+
 def test_preprocess_matches_oracle(L):
     from oracle import zoedepth_ref as Z
     g = torch.Generator().manual_seed(0)
-    for (H, W, nh, nw) in [(480, 640, 384, 512), (480, 600, 416, 512)]:
+    for (H, W, nh, nw) in PRE_POST_GEOMS:
         f = torch.randint(0, 256, (2, H, W, 3), dtype=torch.uint8, generator=g)
         ref = Z.preprocess(f)
         assert ref.shape[-2:] == (nh, nw)
@@ -1056,17 +1198,20 @@ def test_logbinom_depth(L, dtype, lfmt, geom):
         assert err < 2e-4
 
 
-def test_postprocess_matches_oracle(L):
+@pytest.mark.parametrize("flip", [True, False], ids=["flip", "noflip"])
+@pytest.mark.parametrize("H,W,nh,nw", PRE_POST_GEOMS, ids=[f"{h}x{w}" for h, w, _, _ in PRE_POST_GEOMS])
+def test_postprocess_matches_oracle(L, H, W, nh, nw, flip):
     from oracle import zoedepth_ref as Z
-    B, H, W, nh, nw = 2, 480, 640, 384, 512
-    d = torch.rand(2 * B, nh, nw, generator=torch.Generator().manual_seed(0)) * 3 + 0.2
-    ref = Z.postprocess(d[:B], d[B:], H, W)
+    B = 2
+    d = torch.rand(2 * B if flip else B, nh, nw, generator=torch.Generator().manual_seed(0)) * 3 + 0.2
+    ref = Z.postprocess(d[:B], d[B:] if flip else None, H, W)
+    assert ref.shape == (B, H, W)
     dd = d.to(dev())
     m = torch.empty(B, H, W, device=dev())
     u = torch.empty(B, H, W, device=dev(), dtype=torch.int16)
-    L.postprocess_depth(dd, m, u, B, H, W, nh, nw, True)
+    L.postprocess_depth(dd, m, u, B, H, W, nh, nw, flip)
     err = (m.cpu() - ref).abs().max().item()
-    report(f"postprocess: max|err|={err:.3e}")
+    report(f"postprocess {W}x{H} from {nw}x{nh} flip {flip}: max|err|={err:.3e}")
     assert err < 1e-5
     u16 = u.cpu().numpy().view(np.uint16)
     mm = m.cpu().numpy()
@@ -1094,6 +1239,24 @@ def test_small_attention(L, dtype):
     r = torch.empty(3, dtype=torch.int32, device=dev())
     L.route_argmax(lg, 4, r, 3)
     assert r.tolist() == [1, 0, 0]
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("S", [253, 337, 512])
+def test_small_attention_router_lengths(L, dtype, S):
+    """the router's token counts of the image-major networks (1 + 12 x 21 for 384x672, 1 + 21 x 16 for 672x512) and the entry's limit:
+    K and V of a head need more than 64 KiB of LDS from 257 tokens on"""
+    B, nh, D = 2, 4, 128
+    qkv = rnd(B * S, 3 * D, seed=S)
+    out = torch.full((B * S + 16, D), -3.0, device=dev(), dtype=dtype)
+    L.small_attention(qkv, out, B, S, nh)
+    y = qkv.double().view(B, S, 3, nh, 32)
+    q, k, v = y[:, :, 0].transpose(1, 2), y[:, :, 1].transpose(1, 2), y[:, :, 2].transpose(1, 2)
+    ref = (torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(32), -1) @ v).transpose(1, 2).reshape(B * S, D)
+    err = (out[:B * S].double() - ref).abs().max().item()
+    report(f"small_attention {dtype} S{S}: max|err|={err:.3e}")
+    assert err < tol(dtype, 1) * 4
+    assert (out[B * S:] == -3.0).all()
 
 
 # ------------------------------------------------------------------------------------------------

@@ -99,17 +99,26 @@ def test_pre_post_geometry():
     assert u16.dtype == np.uint16 and u16.min() >= 128  # bicubic may undershoot random data a little
 
 
-def test_preprocess_matches_hf_processor():
+# (frame H, W) -> network input (nh, nw): the 512-wide inputs of the table attention path and the square, 384x480, 16:9 and portrait
+# inputs of the image-major path
+HF_SIZES = [((480, 640), (384, 512)), ((480, 600), (416, 512)), ((1024, 1280), (416, 512)), ((320, 320), (384, 384)),
+            ((288, 360), (384, 480)), ((720, 1280), (384, 672)), ((1080, 1920), (384, 672)), ((640, 480), (672, 512))]
+
+
+@pytest.mark.parametrize("hw,net", HF_SIZES, ids=[f"{h}x{w}" for (h, w), _ in HF_SIZES])
+def test_preprocess_matches_hf_processor(hw, net):
     """pad + resize + normalise against HF's ZoeDepthImageProcessorPil (cites upstream depth_model.py#L57)."""
     pytest.importorskip("transformers")
     from transformers.models.zoedepth.image_processing_pil_zoedepth import ZoeDepthImageProcessorPil
+    from bodyslam_amd.zoedepth import net_size
     # upstream PrepForMidas uses ensure_multiple_of=32 (as does the released Intel/zoedepth-nyu-kitti
     # preprocessor config); the bare class default (1/32) is not what any checkpoint ships with
     proc = ZoeDepthImageProcessorPil(ensure_multiple_of=32)
     rng = np.random.default_rng(0)
-    img = rng.integers(0, 256, size=(480, 640, 3), dtype=np.uint8)
+    img = rng.integers(0, 256, size=(*hw, 3), dtype=np.uint8)
     ref = proc(images=[img], return_tensors="pt")["pixel_values"]
     x = Z.preprocess(torch.from_numpy(img)[None])
+    assert tuple(ref.shape[-2:]) == net and net_size(*hw) == net
     assert ref.shape == x.shape
     assert (ref - x).abs().max() < 1e-5
 
