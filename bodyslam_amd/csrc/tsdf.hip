@@ -9,6 +9,7 @@
 // exist, which block each owns) is an open-addressing hash table in HBM filled by atomicCAS (Open3D: an unordered_map on the host);
 // blocks are carved from zero-filled slabs whose base addresses the kernels get as a small device array.
 #include <stdlib.h>
+#include <string.h>
 
 #include <mutex>
 
@@ -394,7 +395,8 @@ __device__ double ts_tsdf_at(const double p[3], const long long* __restrict__ ke
         idx0[a] = i0;
         r[a] = pg - (double)i0;
     }
-    if (ts_find(keys, slots, mask, ts_pack(index0[0], index0[1], index0[2])) < 0) return 0.0;
+    const int s0 = ts_find(keys, slots, mask, ts_pack(index0[0], index0[1], index0[2]));
+    if (s0 < 0) return 0.0;
     double sum = 0.0;
     for (int c = 0; c < 8; ++c) {
         int index1[3], idx1[3];
@@ -409,7 +411,9 @@ __device__ double ts_tsdf_at(const double p[3], const long long* __restrict__ ke
                 index1[a] += 1;
             }
         }
-        const int s = ts_find(keys, slots, mask, ts_pack(index1[0], index1[1], index1[2]));
+        // (a corner inside the first corner's unit -- all eight, away from the unit's upper faces -- needs no second probe)
+        const bool same = index1[0] == index0[0] && index1[1] == index0[1] && index1[2] == index0[2];
+        const int s = same ? s0 : ts_find(keys, slots, mask, ts_pack(index1[0], index1[1], index1[2]));
         if (s >= 0) sum += w * (double)ts_block(slab_base, slab_units, unit_bytes, s)[((int64_t)idx1[0] * res * res + idx1[1] * res + idx1[2]) * 5];
     }
     return sum;
@@ -595,6 +599,194 @@ __global__ __launch_bounds__(256) void tsdf_mesh_kernel(const int32_t* __restric
             cols[(at + k) * 3 + c] = (float)(((double)cp[a][2 + c] + w * ((double)cp[b][2 + c] - (double)cp[a][2 + c])) / 255.0);
         }
         vkeys[at + k] = key;
+    }
+}
+
+// ---- the model seen from a camera: ray cast of the map ----------------------------------------------------------------------------
+// What BodySLAM_not_refactored/3DM/tsdf.py:81-83 asks of Open3D after every integration (VoxelBlockGrid's
+// synthesize_model_frame: a ray cast of the voxel grid at the current pose) and 3DM/synthetic_depth_generator.py:74-97 /
+// 3DM/mapping_module.py:204-228 ask of the extracted mesh (pinhole rays, t_hit as the depth image).  Open3D is not vendored: the
+// marching scheme below is KinectFusion's / VoxelBlockGrid::RayCast's in outline, restated in tests/_raycast_ref.py; parity with
+// Open3D itself is unpinned.
+//
+// Thread = (view, pixel).  Ray of pixel (u, v): d_cam = ((u - cx) / fx, (v - cy) / fy, 1), d = R d_cam, so the parameter t of
+// o + t d is the camera-frame z of the point and IS the depth written (the convention of tsdf_observe); n = |d_cam| turns metres
+// along the ray into t.  t starts at depth_min with no valid previous sample (f_prev = -1) and while t < depth_max:
+//   unit of p = o + t d absent from the table (or present without a block): t moves to where the ray leaves the unit's box
+//     (slab exit over the three axes) + half a voxel, f_prev = -1;
+//   else (f, w) = the nearest voxel; in the near band (w > 0, |f| sdf_trunc < 2 voxels) f = ts_tsdf_at(p), the trilinear value;
+//     hit when w > 0, f_prev > 0, f <= 0: t* = t_prev + (t - t_prev) f_prev / (f_prev - f).  A negative sample without a valid
+//     positive predecessor (back face, start inside the surface, entry from unobserved space) is no hit: marching goes on;
+//     otherwise t_prev = t, f_prev = (w > 0 ? f : -1), t += max(w > 0 ? f sdf_trunc : 0, voxel) / n.
+// Outputs at a hit (zeros elsewhere; every one but depth may be NULL): depth = t*, vertex = o + t* d, normal = the central difference
+// of ts_tsdf_at at +-0.99 voxel exactly as tsdf_extract_kernel writes it, colour = the trilinear mean of r, g, b over the corners
+// with weight > 0, renormalised, rounded to nearest.
+//
+// Shape: a wave is an 8 x 8 pixel tile and a block 16 x 16, so the rays of a wave walk the same units and their gathers share cache
+// lines; (view, tile) is folded into blockIdx.x.  The unit's key and block pointer stay in registers: the table is probed only when
+// the unit index changes, the eight-corner read happens in the near band only (two or three steps per ray).  World positions are
+// fp64 in the restatement's operation order (the build has -ffp-contract=off), which is what lets the tests hold the depth to
+// 1e-6 m.  Lanes finish at different steps and the loop runs until the wave is done; depth_max bounds the trip count, and
+// TS_RAY_MAX_STEPS caps it so that a corrupt table cannot spin a wave: a step advances t by at least half a voxel / n, so the cap
+// binds only when (depth_max - depth_min) n / voxel_length exceeds 32 768 (the reference: 3 m / 1 mm = 3 000); such a ray ends
+// without a hit.  The map is only read: no atomics, no LDS, and nothing that needs the unit count, so the launch may follow
+// un-synchronised integrations on the same stream.
+constexpr int TS_RAY_MAX_STEPS = 1 << 16;
+constexpr int TS_RAY_VIEWS = BS_TSDF_RAYCAST_VIEWS;           // views per launch: their camera records travel as kernel arguments
+
+struct TsdfRayViews {
+    double pose[TS_RAY_VIEWS][12];                            // camera -> world, rows 0..2
+};
+
+// colour at p: the corners of ts_tsdf_at, those with weight > 0 only
+__device__ __forceinline__ void ts_color_at(const double p[3], const long long* __restrict__ keys, const int32_t* __restrict__ slots, unsigned mask,
+                                            const int64_t* __restrict__ slab_base, int slab_units, int res, double voxel_length, uint8_t out[3]) {
+    const double unit_len = voxel_length * res;
+    const int64_t unit_bytes = (int64_t)res * res * res * 20;
+    int index0[3], idx0[3];
+    double r[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double pl = p[a] - 0.5 * voxel_length;
+        index0[a] = (int)floor(pl / unit_len);
+        const double pg = (pl - (double)index0[a] * unit_len) / voxel_length;
+        int i0 = (int)floor(pg);
+        i0 = i0 < 0 ? 0 : (i0 >= res ? res - 1 : i0);
+        idx0[a] = i0;
+        r[a] = pg - (double)i0;
+    }
+    const int s0 = ts_find(keys, slots, mask, ts_pack(index0[0], index0[1], index0[2]));
+    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, wsum = 0.0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        int index1[3], idx1[3];
+        double w = 1.0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int sh = (c >> (2 - a)) & 1;
+            w *= sh ? r[a] : 1.0 - r[a];
+            idx1[a] = idx0[a] + sh;
+            index1[a] = index0[a];
+            if (idx1[a] >= res) {
+                idx1[a] -= res;
+                index1[a] += 1;
+            }
+        }
+        const bool same = index1[0] == index0[0] && index1[1] == index0[1] && index1[2] == index0[2];
+        const int s = same ? s0 : ts_find(keys, slots, mask, ts_pack(index1[0], index1[1], index1[2]));
+        if (s < 0) continue;
+        const float* vox = ts_block(slab_base, slab_units, unit_bytes, s) + ((int64_t)idx1[0] * res * res + idx1[1] * res + idx1[2]) * 5;
+        if (vox[1] > 0.0f) {
+            wsum += w;
+            acc0 += w * (double)vox[2];
+            acc1 += w * (double)vox[3];
+            acc2 += w * (double)vox[4];
+        }
+    }
+    const double acc[3] = {acc0, acc1, acc2};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double v = wsum > 0.0 ? floor(acc[k] / wsum + 0.5) : 0.0;
+        out[k] = (uint8_t)(v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v));
+    }
+}
+
+__global__ __launch_bounds__(256) void tsdf_raycast_kernel(TsdfRayViews views, int n_views, int H, int W, double fx, double fy, double cx, double cy,
+                                                            double depth_min, double depth_max, const long long* __restrict__ keys,
+                                                            const int32_t* __restrict__ slots, unsigned mask, const int64_t* __restrict__ slab_base,
+                                                            int slab_units, int res, double voxel_length, double sdf_trunc, float* __restrict__ depth,
+                                                            float* __restrict__ vertex, float* __restrict__ normal, uint8_t* __restrict__ color) {
+    const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
+    const int tiles = tiles_x * tiles_y;
+    const int view = blockIdx.x / tiles, tile = blockIdx.x - view * tiles;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int u = (tile % tiles_x) * 16 + (wave & 1) * 8 + (lane & 7), v = (tile / tiles_x) * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (view >= n_views || u >= W || v >= H) return;
+    const double* P = views.pose[view];
+    const double dc0 = ((double)u - cx) / fx, dc1 = ((double)v - cy) / fy;
+    const double o[3] = {P[3], P[7], P[11]};
+    const double d[3] = {P[0] * dc0 + P[1] * dc1 + P[2], P[4] * dc0 + P[5] * dc1 + P[6], P[8] * dc0 + P[9] * dc1 + P[10]};
+    const double n = sqrt(dc0 * dc0 + dc1 * dc1 + 1.0);
+    const double unit_len = voxel_length * res, half_step = 0.5 * voxel_length / n;
+    const int64_t unit_bytes = (int64_t)res * res * res * 20;
+
+    long long cur_key = TS_EMPTY;              // the unit the ray is in, and its block (nullptr: no such unit / no block yet)
+    const float* cur_blk = nullptr;
+    double t = depth_min, tp = depth_min, fp = -1.0, hit = 0.0;
+    for (int step = 0; t < depth_max && step < TS_RAY_MAX_STEPS; ++step) {
+        const double p[3] = {o[0] + t * d[0], o[1] + t * d[1], o[2] + t * d[2]};
+        int ui[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) ui[a] = (int)floor(p[a] / unit_len);
+        const long long key = ts_pack(ui[0], ui[1], ui[2]);
+        if (key != cur_key) {
+            const int s = ts_find(keys, slots, mask, key);
+            cur_blk = s >= 0 ? ts_block(slab_base, slab_units, unit_bytes, s) : nullptr;
+            cur_key = key;
+        }
+        if (!cur_blk) {
+            double te = INFINITY;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (d[a] > 0.0) te = fmin(te, ((double)(ui[a] + 1) * unit_len - p[a]) / d[a]);
+                else if (d[a] < 0.0) te = fmin(te, ((double)ui[a] * unit_len - p[a]) / d[a]);
+            }
+            tp = t;
+            fp = -1.0;
+            t = t + (fmax(te, 0.0) + half_step);
+            continue;
+        }
+        int idx[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int i = (int)floor((p[a] - (double)ui[a] * unit_len) / voxel_length);
+            idx[a] = i < 0 ? 0 : (i >= res ? res - 1 : i);
+        }
+        const float* vox = cur_blk + ((int64_t)idx[0] * res * res + idx[1] * res + idx[2]) * 5;
+        double f = (double)vox[0];
+        const bool seen = vox[1] > 0.0f;
+        if (seen && fabs(f) * sdf_trunc < 2.0 * voxel_length) f = ts_tsdf_at(p, keys, slots, mask, slab_base, slab_units, res, voxel_length);
+        if (seen && fp > 0.0 && f <= 0.0) {
+            hit = tp + (t - tp) * fp / (fp - f);
+            break;
+        }
+        tp = t;
+        fp = seen ? f : -1.0;
+        t = t + fmax(seen ? f * sdf_trunc : 0.0, voxel_length) / n;
+    }
+
+    const int64_t at = ((int64_t)view * H + v) * W + u;
+    depth[at] = (float)hit;
+    const bool is_hit = hit > 0.0;
+    const double q[3] = {o[0] + hit * d[0], o[1] + hit * d[1], o[2] + hit * d[2]};
+    if (vertex) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) vertex[at * 3 + c] = is_hit ? (float)q[c] : 0.0f;
+    }
+    if (normal) {
+        double g[3] = {0.0, 0.0, 0.0};
+        if (is_hit) {
+            const double gap = 0.99 * voxel_length;
+            for (int a = 0; a < 3; ++a) {
+                double pp[3] = {q[0], q[1], q[2]}, pm[3] = {q[0], q[1], q[2]};
+                pp[a] += gap;
+                pm[a] -= gap;
+                g[a] = ts_tsdf_at(pp, keys, slots, mask, slab_base, slab_units, res, voxel_length) -
+                       ts_tsdf_at(pm, keys, slots, mask, slab_base, slab_units, res, voxel_length);
+            }
+            const double len = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+            if (len > 0.0) {
+                g[0] /= len; g[1] /= len; g[2] /= len;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) normal[at * 3 + c] = (float)g[c];
+    }
+    if (color) {
+        uint8_t rgb[3] = {0, 0, 0};
+        if (is_hit) ts_color_at(q, keys, slots, mask, slab_base, slab_units, res, voxel_length, rgb);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) color[at * 3 + c] = rgb[c];
     }
 }
 
@@ -832,5 +1024,36 @@ extern "C" int bs_tsdf_mesh(const int32_t* unit_index, int32_t units, const void
         hipLaunchKernelGGL(tsdf_mesh_kernel<true>, grid, dim3(256), 0, st, unit_index, keys, table_slots, (unsigned)(table_cap - 1), slab_base, slab_units,
                            res, voxel_length, mc_tab, tri_width, unit_count, unit_offset, vertices, colors, reinterpret_cast<long long*>(vertex_keys), err);
     BS_CHECK_LAUNCH();
+    return BS_OK;
+}
+
+extern "C" int bs_tsdf_raycast(const double* K, const double* extrinsics, int32_t n_views, int32_t H, int32_t W, double depth_min, double depth_max,
+                               const void* table_keys, const int32_t* table_slots, int32_t table_cap, const int64_t* slab_base, int32_t slab_units,
+                               int32_t res, double voxel_length, double sdf_trunc, float* depth, float* vertex, float* normal, uint8_t* color,
+                               void* stream) {
+    if (!initialized()) { set_error("bs_tsdf_raycast: call bs_init first"); return BS_ERR_NOT_INIT; }
+    BS_REQUIRE(n_views >= 0 && H > 0 && W > 0 && res > 0 && res <= 64 && slab_units > 0 && voxel_length > 0.0 && sdf_trunc > 0.0,
+               "bs_tsdf_raycast: bad geometry");
+    BS_REQUIRE(depth_min >= 0.0 && depth_min < depth_max, "bs_tsdf_raycast: need 0 <= depth_min < depth_max (got %g, %g)", depth_min, depth_max);
+    if (n_views == 0) return BS_OK;
+    BS_REQUIRE(K && extrinsics && table_keys && table_slots && slab_base && depth, "bs_tsdf_raycast: null argument");
+    BS_REQUIRE(K[0] != 0.0 && K[1] != 0.0, "bs_tsdf_raycast: zero focal length");
+    BS_REQUIRE(table_cap >= 256 && (table_cap & (table_cap - 1)) == 0, "bs_tsdf_raycast: table_cap must be a power of two >= 256");
+    const long long tiles = (long long)cdiv(W, 16) * cdiv(H, 16);
+    BS_REQUIRE(tiles * BS_TSDF_RAYCAST_VIEWS < 0x7fffffffll, "bs_tsdf_raycast: image too large for one launch");
+    for (int f = 0; f < n_views; ++f) BS_REQUIRE(det_ok(extrinsics + 16 * f), "bs_tsdf_raycast: extrinsic %d is singular", f);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the camera records go down as kernel arguments, BS_TSDF_RAYCAST_VIEWS views per launch: nothing has to outlive the call
+    for (int a = 0; a < n_views; a += BS_TSDF_RAYCAST_VIEWS) {
+        const int m = n_views - a < BS_TSDF_RAYCAST_VIEWS ? n_views - a : BS_TSDF_RAYCAST_VIEWS;
+        TsdfRayViews views;
+        memset(&views, 0, sizeof(views));
+        for (int f = 0; f < m; ++f) affine_inverse(extrinsics + 16 * (a + f), views.pose[f]);
+        const int64_t px = (int64_t)a * H * W;
+        hipLaunchKernelGGL(tsdf_raycast_kernel, dim3((unsigned)(tiles * m)), dim3(256), 0, st, views, m, H, W, K[0], K[1], K[2], K[3], depth_min, depth_max,
+                           reinterpret_cast<const long long*>(table_keys), table_slots, (unsigned)(table_cap - 1), slab_base, slab_units, res, voxel_length,
+                           sdf_trunc, depth + px, vertex ? vertex + px * 3 : nullptr, normal ? normal + px * 3 : nullptr, color ? color + px * 3 : nullptr);
+        BS_CHECK_LAUNCH();
+    }
     return BS_OK;
 }

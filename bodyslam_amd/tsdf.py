@@ -13,6 +13,10 @@ restates the same algorithm in numpy; tests/ compare the two).  ``extract_pcd`` 
 ``extract_point_cloud``; ``extract_mesh`` / ``save_mesh`` (tsdf.py:42-52, called on the last frame at 3DM/slam.py:189-193) run marching
 cubes over every voxel cube on the device (bs_tsdf_mesh) with the case table of bodyslam_amd/marching_cubes.py and merge the
 vertices of shared cube edges on the host.
+
+``TSDF.raycast`` asks the map what a camera at a given pose sees (depth, colour, vertices, normals; bs_tsdf_raycast, one thread
+per pixel through the unit table, every view of a call in one launch), and ``MAP`` is the drop-in for the reference's second class
+(tsdf.py:56-107), which synthesises such a model frame after every integration.
 """
 from __future__ import annotations
 
@@ -69,6 +73,32 @@ class TriangleMesh:
     vertices: np.ndarray                    # [V, 3] float32
     vertex_colors: np.ndarray               # [V, 3] float32 in [0, 1]
     triangles: np.ndarray                   # [T, 3] int32, wound so that the normal points from tsdf < 0 to tsdf > 0
+
+
+@dataclass
+class RaycastFrame:
+    """What ``TSDF.raycast`` returns: device tensors, [n, H, W, ...] for a sequence of views, [H, W, ...] for a single 4x4."""
+    depth: torch.Tensor                         # fp32 metres (camera-frame z of the surface point), 0 = no surface
+    color: Optional[torch.Tensor] = None        # u8 x 3
+    vertex: Optional[torch.Tensor] = None       # fp32 x 3, world coordinates, 0 where there is no surface
+    normal: Optional[torch.Tensor] = None       # fp32 x 3, unit length, 0 where there is no surface (or the tsdf gradient vanishes)
+
+    def _view(self, t: torch.Tensor, i: int) -> torch.Tensor:
+        if self.depth.dim() == 2:
+            if i != 0:
+                raise IndexError(f"view {i} of a single-view RaycastFrame")
+            return t
+        return t[i]
+
+    def to_rgbd(self, i: int = 0) -> RGBDImage:
+        """view i as an RGBDImage of device tensors: straight into build_3D_map, rgbd_odometry or a comparison"""
+        return RGBDImage(None if self.color is None else self._view(self.color, i), self._view(self.depth, i))
+
+    def depth_u16(self, depth_scale: float = 1000.0) -> torch.Tensor:
+        """depth * depth_scale rounded to nearest as uint16 values in int16 storage (values above 65 535 saturate): the layout
+        evaluation.evaluate_depth reads, 0 = no surface"""
+        v = torch.clamp(torch.round(self.depth.to(torch.float64) * float(depth_scale)), 0.0, 65535.0).to(torch.int32)
+        return torch.where(v >= 32768, v - 65536, v).to(torch.int16)
 
 
 BATCH_MAX = 64              # frames per pass of build_3D_map_batch (BS_TSDF_BATCH_MAX: one bit per frame in a unit's mask)
@@ -361,6 +391,33 @@ class TSDF:
     def save_mesh(self, saving_path: str) -> None:
         write_ply_mesh(saving_path, self.extract_mesh())
 
+    def raycast(self, intrinsic: PinholeCameraIntrinsic, extrinsic, depth_min: float = 0.0, depth_max: float = 3.0, vertex: bool = False,
+                normal: bool = False, color: bool = True) -> RaycastFrame:
+        """The map as a camera sees it: ``extrinsic`` (world -> camera, the convention of build_3D_map -- raycast(extrinsic=E)
+        re-renders what build_3D_map(..., E) integrated) is one 4x4, or a sequence / [n, 4, 4] array or tensor of them; all views go
+        down in one call.  Rays run from depth_min to depth_max metres.  Nothing is read back and nothing waits: the call may follow
+        build_3D_map(sync=False) frames directly, and the frame's tensors are valid in stream order."""
+        if isinstance(extrinsic, (list, tuple)):
+            E = np.stack([self._np(e) for e in extrinsic]) if len(extrinsic) else np.zeros((0, 4, 4))
+        else:
+            E = self._np(extrinsic)
+        E = np.asarray(E, dtype=np.float64)
+        single = E.ndim == 2
+        E = np.ascontiguousarray(E.reshape(-1, 4, 4))
+        n, H, W = E.shape[0], int(intrinsic.height), int(intrinsic.width)
+        K = np.array([intrinsic.fx, intrinsic.fy, intrinsic.cx, intrinsic.cy], dtype=np.float64)
+        d = self.dev
+        out_d = torch.empty(n, H, W, dtype=torch.float32, device=d)
+        out_v = torch.empty(n, H, W, 3, dtype=torch.float32, device=d) if vertex else None
+        out_n = torch.empty(n, H, W, 3, dtype=torch.float32, device=d) if normal else None
+        out_c = torch.empty(n, H, W, 3, dtype=torch.uint8, device=d) if color else None
+        L.check(L.load_library().bs_tsdf_raycast(K.ctypes.data_as(C.c_void_p), E.ctypes.data_as(C.c_void_p), n, H, W, float(depth_min), float(depth_max),
+                                                 L.p(self.table_keys), L.p(self.table_slots), self.table_cap, L.p(self.slab_base), self.slab_units,
+                                                 self.res, self.voxel_length, self.sdf_trunc, L.p(out_d), L.p(out_v), L.p(out_n), L.p(out_c),
+                                                 L.stream_ptr()), "bs_tsdf_raycast")
+        pick = (lambda t: None if t is None else t[0]) if single else (lambda t: t)
+        return RaycastFrame(pick(out_d), pick(out_c), pick(out_v), pick(out_n))
+
     # ---- views of the device state (tests, diagnostics) ---------------------------------------------
     @staticmethod
     def _np(m):
@@ -375,6 +432,67 @@ class TSDF:
         """voxels of one unit as fp32 [res, res, res, 5]"""
         s = self.index.index(tuple(int(v) for v in key))
         return self.slabs[s // self.slab_units][s % self.slab_units].view(self.res, self.res, self.res, 5).cpu().numpy()
+
+
+class MAP:
+    """Drop-in for the reference's ``MAP`` (BodySLAM_not_refactored/3DM/tsdf.py:56-107), which wraps Open3D's tensor SLAM model
+    (``o3d.t.pipelines.slam.Model(voxel_size, 16, block_count, ...)``): ``integrate(curr_rgbd, i, curr_global_pose)`` integrates
+    a frame at its pose and then synthesises the model's view from that pose into ``raycast_frame`` (:81-83).
+
+    Kept: the constructor and method names, blocks of 16^3 voxels, ``block_count`` as the map's capacity, truncation =
+    ``trunc_voxel_multiplier * voxel_size``, and a synthesised frame (depth + colour, a ``RaycastFrame``) after every
+    integration, cast between the frame's ``depth_min`` and ``depth_max``.  Not kept: Open3D's tensor integration weights (the
+    voxels are this package's ``TSDF`` running means, csrc/tsdf.hip); its frame-pose bookkeeping (``update_frame_pose``) is the
+    list ``frame_poses``.  ``curr_global_pose`` is the camera -> world 4x4 (Open3D's T_frame_to_model).  ``curr_rgbd`` is this
+    package's ``RGBDImage`` (depth in metres; an integer depth image is divided by ``depth_scale``) or any object with ``color``
+    and ``depth``; its ``depth_min`` / ``depth_max`` attributes (metres) are used when present, as the reference reads them from
+    its frame, otherwise the minimum and maximum of the depth image -- one read-back per frame.  The rays start ``sdf_trunc``
+    before ``depth_min`` and run ``sdf_trunc`` past ``depth_max``: a surface is found where the tsdf changes sign, between a
+    sample in front of it and one behind it, so the nearest and the farthest pixel of the frame need that margin."""
+
+    def __init__(self, width, height, intrinsic, device, depth_scale, voxel_size=0.0058, block_count=40000, trunc_voxel_multiplier=8.0):
+        if not isinstance(intrinsic, PinholeCameraIntrinsic):
+            m = np.asarray(TSDF._np(intrinsic), dtype=np.float64)          # Open3D's Frame takes the 3x3 matrix
+            intrinsic = PinholeCameraIntrinsic(int(width), int(height), float(m[0, 0]), float(m[1, 1]), float(m[0, 2]), float(m[1, 2]))
+        self.intrinsic = intrinsic
+        self.width, self.height = int(width), int(height)
+        self.depth_scale, self.trunc_voxel_multiplier = float(depth_scale), float(trunc_voxel_multiplier)
+        index = device if isinstance(device, int) else (torch.device(device).index or 0)
+        self.model = TSDF(float(voxel_size), self.trunc_voxel_multiplier * float(voxel_size), volume_unit_resolution=16, device=index,
+                          max_units=int(block_count))
+        self.frame_poses = []                                               # (i, camera -> world) per integrate call
+        self.raycast_frame: Optional[RaycastFrame] = None
+
+    def integrate(self, curr_rgbd, i, curr_global_pose) -> None:
+        depth = curr_rgbd.depth
+        if isinstance(depth, torch.Tensor):
+            depth = depth.to(self.model.dev)
+            depth = depth.to(torch.float32) if depth.is_floating_point() else depth.to(torch.float32) / self.depth_scale
+        else:
+            depth = np.asarray(depth)
+            depth = depth.astype(np.float32) if depth.dtype.kind == "f" else depth.astype(np.float32) / np.float32(self.depth_scale)
+            depth = torch.from_numpy(np.ascontiguousarray(depth)).to(self.model.dev)
+        pose = np.asarray(TSDF._np(curr_global_pose), dtype=np.float64)
+        E = np.linalg.inv(pose)
+        self.frame_poses.append((i, pose))
+        self.model.build_3D_map(RGBDImage(curr_rgbd.color, depth), self.intrinsic, E)
+        lo, hi = getattr(curr_rgbd, "depth_min", None), getattr(curr_rgbd, "depth_max", None)
+        if lo is None or hi is None:
+            lo, hi = (float(v) for v in torch.stack([depth.min(), depth.max()]).cpu())
+        lo, hi = max(float(lo) - self.model.sdf_trunc, 0.0), float(hi) + self.model.sdf_trunc
+        self.raycast_frame = self.model.raycast(self.intrinsic, E, depth_min=lo, depth_max=hi, color=True)
+
+    def extract_pcd(self) -> PointCloud:
+        return self.model.extract_pcd()
+
+    def extract_mesh(self) -> TriangleMesh:
+        return self.model.extract_mesh()
+
+    def save_pcd(self, saving_path: str) -> None:
+        self.model.save_pcd(saving_path)
+
+    def save_mesh(self, saving_path: str) -> None:
+        self.model.save_mesh(saving_path)
 
 
 def write_ply(path: str, pcd: PointCloud) -> None:

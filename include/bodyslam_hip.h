@@ -451,6 +451,27 @@ int bs_tsdf_mesh(const int32_t* unit_index, int32_t units, const void* table_key
                  const int64_t* slab_base, int32_t slab_units, int32_t res, double voxel_length, const int32_t* mc_tab, int32_t tri_width,
                  int32_t* unit_count, const int64_t* unit_offset, float* vertices, float* colors, int64_t* vertex_keys, int32_t* err, void* stream);
 
+/* The model seen from a camera: a ray cast of the map.  The reference asks for it in three places: the MAP class
+ * (BodySLAM_not_refactored/3DM/tsdf.py:56-107) calls Open3D's synthesize_model_frame after every integrate (:81-83) -- a ray cast of the
+ * voxel grid at the current pose into its raycast_frame; 3DM/synthetic_depth_generator.py:74-97 (compute_synthetic_depth) and
+ * 3DM/mapping_module.py:204-228 (_compute_synthetic_depth) cast pinhole rays against the extracted mesh and keep t_hit as the depth
+ * image.  Open3D is not vendored: the marching scheme (KinectFusion's / VoxelBlockGrid::RayCast's in outline: sphere tracing on the
+ * nearest voxel, trilinear samples near the surface, linear zero crossing; csrc/tsdf.hip and tests/_raycast_ref.py state it in full)
+ * is pinned against analytic scenes, parity with Open3D itself is unpinned.
+ *   K = (fx, fy, cx, cy) and extrinsics = n_views world->camera 4x4 (row-major fp64), both host pointers: the entry inverts them
+ *   (a singular one is refused) and hands the camera records to the kernel itself, BS_TSDF_RAYCAST_VIEWS views per launch -- the
+ *   caller sees no view limit.  Rays run from depth_min to depth_max (metres of camera-frame z, 0 <= depth_min < depth_max).
+ *   Outputs, device memory: depth fp32 [n_views, H, W] (camera-frame z of the surface point, 0 = no surface); vertex fp32
+ *   [n_views, H, W, 3] (world), normal fp32 [n_views, H, W, 3] (GetNormalAt of the point, as bs_tsdf_extract writes it), color u8
+ *   [n_views, H, W, 3]; zeros where there is no hit; vertex, normal and color may each be NULL and are then not computed.
+ *   The map is only read, through the unit table (an entry without a block is empty space): neither the unit count nor a host
+ *   round trip is needed, so the call may follow un-synchronised bs_tsdf_touch / bs_tsdf_integrate calls on the same stream.
+ *   n_views == 0 returns BS_OK. */
+#define BS_TSDF_RAYCAST_VIEWS 32
+int bs_tsdf_raycast(const double* K, const double* extrinsics, int32_t n_views, int32_t H, int32_t W, double depth_min, double depth_max,
+                    const void* table_keys, const int32_t* table_slots, int32_t table_cap, const int64_t* slab_base, int32_t slab_units,
+                    int32_t res, double voxel_length, double sdf_trunc, float* depth, float* vertex, float* normal, uint8_t* color, void* stream);
+
 /* dense RGB-D odometry (N3) -------------------------------------------------------------------- *
  * The role of Open3D's rgbd_odometry_multi_scale (Method.Hybrid, 20 / 10 / 5 iterations) at
  * BodySLAM_not_refactored/3DM/visual_odometry.py:97-120; the algorithm is stated in oracle/rgbd_odometry_ref.py (parity with Open3D
