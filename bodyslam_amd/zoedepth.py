@@ -26,6 +26,7 @@ from __future__ import annotations
 import math
 import os
 import warnings
+import dataclasses
 from dataclasses import dataclass
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -34,6 +35,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
+from .calibration import DEFAULT_POLICY, NECK_RELHEAD_WONLY, CalibrationPolicy, Scope, choose, finish_report, saving_gflop, worst  # noqa: F401
 
 LOG2E = 1.4426950408889634
 
@@ -86,88 +88,35 @@ class ZoeConfig:
         return self.level_attractors[level] if self.single_head else self.n_attractors
 
 
-# Which correction products accurate mode evaluates per backbone GEMM class (tools/probes/precision_classes.py,
-# tools/probes/weight_mean_correction.py, DESIGN.md Numerics).
-#   "full"  A_hi W_hi + A_hi8 W_lo8 + A_lo8 W_hi8 on every row (2 pass-equivalents): depth L1 vs the fp32 oracle 1.3e-5 m
-#   "wcls"  the activation-rounding correction on the cls-token tile only (its error is the only coherent one): 1.5 passes,
-#           4.3e-5 / 2.0e-5 m on two weight seeds
-#   "wmean" patch tiles run ONE 16-bit pass; the weight-rounding error A dW^T, a coherent offset, is replaced by its
-#           token-independent part 1 (mean_tokens(A) dW^T) -- a per-image bias from a column mean and a tiny GEMM; the cls tile
-#           keeps both corrections: ~1.0 pass, 4.8e-5 / 2.6e-5 m on those two seeds, 1.7e-5 ... 6.3e-5 m over eight
-#           (profiles/r02_accurate_seeds.txt: "wcls" 1.6e-5 ... 5.6e-5, "full" <= 2.1e-5 on the same seeds)
-# The neck keeps both products (weight correction only: 0.9-2.0e-4).
-# "auto" (the default): the engine measures, on the device and with the weights it was given, which of these each class tolerates
-# (ZoeDepthEngine.calibrate, run before the first plan is built): the random-weight studies above say nothing about a trained
-# checkpoint's outlier channels and layer-scale, so no fixed choice is trusted.
-# "pairs" (not a calibration candidate): the operands as (hi | lo) 16-bit pairs and the product as three 16-bit passes, ~22 significant
-# bits per operand -- the REFERENCE precision (precision="reference"), against which calibrate() takes its absolute error.
+# The calibration's thresholds, candidate orders and the record of why each is what it is live in calibration.py (CalibrationPolicy); these
+# are read-only aliases of the default policy's fields.  Assigning to one steers nothing: pass calibrate() a policy.
 BACKBONE_CLASSES = ("qkv", "o", "fc1", "fc2")
 ACCURATE_CLASS_MODES = "auto"
-AUTO_CANDIDATES = ("wmean", "wcls", "full")       # cheapest first
-#   "wstat" (round 6; a candidate in front of "wmean" only with BS_AUTO_WSTAT=1) "wmean" with the token-independent part of the weight-rounding error
-#           taken from the CALIBRATION frames' channel means instead of each image's own: a static fp32 bias row per product (backbone_bias_corr), no
-#           bs_col_mean / bs_rank1_bias launches at run time (192 per forward batch, 2.2 ms per 128 network inputs).  Measured: alone a class costs what
-#           "wmean" costs it (1.2-1.3e-5 m), but the four together read 3.46e-5 m where "wmean" reads 2.81e-5 -- the image-dependent remainder
-#           Sum_c (mean_t a_tc - E[a_c]) dw_c is coherent over an image -- and the neck loses products to it: +0.2 ... +1.1 % frames/s on three weight seeds,
-#           -2 % on the fourth (profiles/r06_calibration_experiments.txt (8)).  Not a default: the gain is inside the box-to-box spread and the static means
-#           stand on the calibration frames' statistics.
-AUTO_TOL_CLASS_M = 4.0e-5                        # depth L1 against the best mode's result that ONE class may cost
-AUTO_TOL_TOTAL_M = 6.0e-5                        # ... and the chosen combination as a whole
-AUTO_TOL_ABS_M = 8.0e-5                          # ... and the chosen combination against the 3-pass REFERENCE engine on the device (the
-                                                 # north star's tolerance is 1e-4 m; the margin covers frames other than the calibration frame)
-TOLERANCE_M = 1.0e-4                             # BASELINE.json north_star: depth L1 vs the reference; calibrate() warns above it
+AUTO_CANDIDATES = DEFAULT_POLICY.candidates
+AUTO_TOL_CLASS_M = DEFAULT_POLICY.tol_class
+AUTO_TOL_TOTAL_M = DEFAULT_POLICY.tol_total
+AUTO_TOL_ABS_M = DEFAULT_POLICY.tol_abs
+TOLERANCE_M = DEFAULT_POLICY.tolerance_m
 # Attention operands: "single" = Q, K, V^T and the probabilities as single 16-bit values (bs_attention_table); "corr" = each with its
 # rounding residual as a second 16-bit value, three MFMA passes per product (bs_attention_table_corr).  Seeded Gaussian weights lose
 # 2.6e-6 m to "single"; weights with outlier channels behind the LayerNorms (trained BEiT checkpoints) 2.9e-4 m
 # (tools/probes/outlier_rounding_study.py) -- so the choice is calibrated per weight set like the GEMM classes ("auto").
 ACCURATE_ATTN_MODE = "auto"
-# neck: "full", or the list of weight-key prefixes that keep both products (the rest: weight-rounding correction only).
-NECK_RELHEAD_WONLY = "ro,ra,nc,fu,pj,mh"         # everything but the relative head keeps both (mh: the bins head's bottleneck conv)
-# What a class's cheap mode saves, in executed GFLOP per network input (16-bit-pass equivalents; derived from the shapes in
-# ZoeDepthEngine._saving_gflop, round 6 -- rounds 2-5 carried millisecond figures measured once at B = 64).  When the chosen combination
-# misses the total tolerance, the class that pays the most depth error per unit saved goes back up first.
-AUTO_ATTN_RATE_FACTOR = 1.5                      # the attention kernels run at ~2/3 of the GEMMs' rate: a pass saved there is worth more time
-# The relative head (rh.projection, rh.conv1: 40 % of the conv stack's time) with the weight-rounding correction only is +1.1 % frames/s for
-# +0.7-1.8e-5 m (profiles/r03_neck_relhead_wonly.txt): a candidate since round 4, when calibrate() got an ABSOLUTE reference.  Without that
-# reference (no source weights) the neck stays "full".
-AUTO_NECK_CANDIDATES = (NECK_RELHEAD_WONLY, "full")
-# Round 5: the neck is calibrated PER SITE (VERDICT r4 #1c).  With the absolute reference available, calibrate() measures what each of the
-# neck's / heads' FP8-format products costs when it alone drops the activation-rounding correction, orders the sites by depth error per
-# FLOP saved and keeps the longest prefix of that order whose combination stays under AUTO_TOL_NECK_ABS_M against the reference
-# (tools/probes/neck_site_study.py: on the bench weights 11 ... 19 sites, not only the relative head, fit that budget).  The choice is
-# the neck mode "wonly:<site>,<site>,..." (ZoeDepthEngine.neck_site_wonly).  Sites below AUTO_NECK_SITE_MIN_SHARE of the neck's FLOPs are
-# not worth a calibration forward EACH; since round 6 they are candidates as GROUPS (AUTO_NECK_SMALL_GROUPS: one forward per group and
-# stage) -- in round 5 none of them was ever calibrated and all ran both corrections, 2-3x their algorithmic work (VERDICT r5 #1 ii).
-AUTO_TOL_NECK_ABS_M = 5.0e-5
-# (round 6: a calibration forward over four frames costs ~0.1 s, so every product above 0.1 % of the neck's FLOPs is a candidate of its own --
-# the first grouping tried, "all reassemble / projection GEMMs", hid one sensitive member behind 6.4e-5 m for the whole group)
-AUTO_NECK_SITE_MIN_SHARE = 0.001
-AUTO_NECK_SMALL_GROUPS = {"tiny": ("ro", "ra", "nc", "fu", "pj", "rh")}      # by weight-key prefix, first match; the bins head's bottleneck conv (mh.) stays out
-# Round 5, second stage: the large weight-only sites may drop the weight-rounding correction TOO -- one 16-bit pass, `f8_skip_from = -1`, the
-# form "wonly:...;plain:<site>,..." (ZoeDepthEngine.neck_site_plain).  tools/probes/neck_plain_study.py: a site alone moves the map by 2-3e-5 m,
-# but twelve of them together leave the distance to the reference where it was (4.5 -> 4.9e-5 m) -- weight rounding in the neck is incoherent
-# noise, like its activation rounding -- while two small sites (nc2, ra3.down) alone cost 3-8e-5.  So the stage walks the sites by FLOPs, largest
-# first, and keeps a site when the combination stays under AUTO_TOL_NECK_PLAIN_ABS_M against the reference.  BS_NECK_PLAIN=0 switches the stage off.
-# Round 6 (advisor): every stage is judged on the WORST of AUTO_CAL_FRAMES calibration frames (round 5: one frame, the
-# plain stage on the mean of two), a site is kept only when it ALSO stays within `tol_total` of the best mode, and the final combination is
-# validated on AUTO_HOLDOUT_FRAMES frames that no decision has seen: above AUTO_TOL_HOLDOUT_M there, the latest relaxations are withdrawn.
-# And the one-pass sites carry a STATIC bias correction: the token-independent part dW E[a] of their weight-rounding error, from the
-# calibration frames' channel means (site_bias_corr; the data-free-quantisation bias correction) -- no run-time cost.
-AUTO_NECK_PLAIN_MIN_SHARE = 0.001
-AUTO_TOL_NECK_PLAIN_ABS_M = 6.0e-5
-# The two neck stages are gated on what they ADD, not only on where they end (round-5 advisor): a weight set whose backbone choice already sits
-# at or above AUTO_TOL_NECK_ABS_M (the outlier-channel weights: 5.1e-5 m with every class "full" -- the floor of e4m3 correction planes on
-# those weights) got no neck relaxation at all in round 5, although one-pass products with the static bias correction cost it a few 1e-6.
-# Stage 1 may spend up to max(AUTO_TOL_NECK_ABS_M, backbone choice + AUTO_NECK_WONLY_INCREMENT_M), stage 2 up to max(AUTO_TOL_NECK_PLAIN_ABS_M,
-# stage 1's result + AUTO_NECK_PLAIN_INCREMENT_M), both capped at AUTO_TOL_NECK_CAP_M; the hold-out check (AUTO_TOL_HOLDOUT_M) stands behind them.
-AUTO_NECK_WONLY_INCREMENT_M = 0.5e-5
-AUTO_NECK_PLAIN_INCREMENT_M = 0.5e-5
-AUTO_TOL_NECK_CAP_M = 6.5e-5
-AUTO_CAL_FRAMES = 4
-AUTO_HOLDOUT_FRAMES = 4
-AUTO_TOL_HOLDOUT_M = 7.0e-5
-AUTO_CAL_SEEDS = (11, 12, 13, 14, 15, 16, 17, 18)        # synthetic.make_sequence(1, H, W, seed): the calibration frames ...
-AUTO_HOLDOUT_SEEDS = (21, 22, 23, 24, 25, 26, 27, 28)    # ... and the held-out ones
+AUTO_ATTN_RATE_FACTOR = DEFAULT_POLICY.attn_rate_factor
+AUTO_NECK_CANDIDATES = DEFAULT_POLICY.neck_candidates
+AUTO_TOL_NECK_ABS_M = DEFAULT_POLICY.tol_neck_abs
+AUTO_NECK_SITE_MIN_SHARE = DEFAULT_POLICY.neck_site_min_share
+AUTO_NECK_SMALL_GROUPS = dict(DEFAULT_POLICY.neck_small_groups)
+AUTO_NECK_PLAIN_MIN_SHARE = DEFAULT_POLICY.neck_plain_min_share
+AUTO_TOL_NECK_PLAIN_ABS_M = DEFAULT_POLICY.tol_neck_plain_abs
+AUTO_NECK_WONLY_INCREMENT_M = DEFAULT_POLICY.neck_wonly_increment
+AUTO_NECK_PLAIN_INCREMENT_M = DEFAULT_POLICY.neck_plain_increment
+AUTO_TOL_NECK_CAP_M = DEFAULT_POLICY.tol_neck_cap
+AUTO_CAL_FRAMES = DEFAULT_POLICY.cal_frames
+AUTO_HOLDOUT_FRAMES = DEFAULT_POLICY.holdout_frames
+AUTO_TOL_HOLDOUT_M = DEFAULT_POLICY.tol_holdout
+AUTO_CAL_SEEDS = DEFAULT_POLICY.cal_seeds
+AUTO_HOLDOUT_SEEDS = DEFAULT_POLICY.holdout_seeds
 ACCURATE_NECK_MODE = "full"
 # (Round 3 also had neck_corr="f4": e2m1 correction planes with E8M0 block scales on the FP4 MFMA -- +1.4 % frames/s for 1.5x the depth error,
 # profiles/r03_fp4_corrections.txt.  It never paid and was removed in round 4; the correction products run on the block-scaled FP8 MFMA.)
@@ -215,6 +164,39 @@ def _relative_position_index(wh: int, ww: int) -> torch.Tensor:
     idx[0, 0] = nrd - 1
     return idx
 
+
+class _Measurement:
+    """The device side of a calibration, as calibration.py's stages see it (calibration.Measurement): depth maps of the calibration or
+    held-out frames under a mode combination, the neck's FLOPs per product, the yardstick and reference maps, the static bias corrections."""
+
+    def __init__(self, eng: "ZoeDepthEngine", frames_u8: torch.Tensor):
+        self.eng, self.frames, self.hold = eng, frames_u8, None
+        self.ncal, self.H, self.W = int(frames_u8.shape[0]), int(frames_u8.shape[1]), int(frames_u8.shape[2])
+        self.site_flops: Dict[str, float] = {}
+        self.ref = self.truth = self.truth_hold = None
+
+    def depth(self, modes, neck, attn, holdout=False, means=None):
+        """depth maps [n,H,W] of the frames under a mode combination (one plan, dropped after use); means: a dict that receives the channel
+        means of every neck product's input rows (the run then goes launch by launch through the plan's tap path)"""
+        frames = self.hold if holdout else self.frames
+        self.eng.set_class_modes(modes, neck, attn)
+        plan = _ZoePlan(self.eng, int(frames.shape[0]), self.H, self.W, True)
+        plan.frames.copy_(frames)
+        plan.run(None if means is None else {"__site_means__": means})
+        d = plan.depth_m.clone()
+        torch.cuda.synchronize(self.eng.dev)
+        self.site_flops.update(plan.site_flops)
+        del plan
+        return d
+
+    def set_site_bias_corr(self, means):
+        """site_bias_corr[key] = dw_sum[key] @ E[a] from the channel means "in:<weight key>" of the calibration frames ({}: none)"""
+        e = self.eng
+        # (multiply + tree sum in fp64, not a library GEMV: split-K atomics would make the low bits -- and with them a borderline
+        # decision of the one-pass stage -- differ between two processes calibrating the same weights)
+        e.site_bias_corr = {k_[3:]: (e.dw_sum[k_[3:]].double() * m_.double()).sum(1).float().contiguous() for k_, m_ in means.items() if k_[3:] in e.dw_sum}
+        e._bias_corr_cache.clear()
+        return sorted(e.site_bias_corr)
 
 class ZoeDepthEngine:
     """Weights resident on the GPU + per-shape launch plans.
@@ -416,43 +398,36 @@ class ZoeDepthEngine:
         """drop the reference to the caller's weight dict (after this, calibrate() has no absolute reference)"""
         self._sd = None
 
-    def _saving_gflop(self, S: int) -> Dict[str, float]:
-        """what a cheap mode saves per network input, in executed GFLOP (16-bit-pass equivalents): "wmean" against "full" is one pass of the
-        class's products; the single-operand attention against the split-precision one is two passes of 4 S^2 hidden (weighted by
-        AUTO_ATTN_RATE_FACTOR).  step_up()'s yardstick (the error a choice costs per unit it saves)."""
-        c = self.cfg
-        per = lambda n, k: 2.0 * S * n * k * c.layers / 1e9
-        return {"qkv": per(3 * c.hidden, c.hidden), "o": per(c.hidden, c.hidden), "fc1": per(c.intermediate, c.hidden),
-                "fc2": per(c.hidden, c.intermediate), "attn": 2.0 * AUTO_ATTN_RATE_FACTOR * 4.0 * S * S * c.hidden * c.layers / 1e9}
-
-    def calibrate(self, H: int = 480, W: int = 640, frames_u8: Optional[torch.Tensor] = None, tol_class: float = AUTO_TOL_CLASS_M,
-                  tol_total: float = AUTO_TOL_TOTAL_M, neck_candidates: Optional[Sequence[str]] = None, tol_abs: float = AUTO_TOL_ABS_M,
-                  reference: bool = True, holdout_u8: Optional[torch.Tensor] = None) -> dict:
+    def calibrate(self, H: int = 480, W: int = 640, frames_u8: Optional[torch.Tensor] = None, tol_class: Optional[float] = None,
+                  tol_total: Optional[float] = None, neck_candidates: Optional[Sequence[str]] = None, tol_abs: Optional[float] = None,
+                  reference: bool = True, holdout_u8: Optional[torch.Tensor] = None, policy: Optional[CalibrationPolicy] = None) -> dict:
         """Choose, with THESE weights on THIS device, the cheapest correction mode per backbone GEMM class, for the attention operands
         and for the neck that keeps the depth maps of the calibration frames within `tol_class` metres (L1, the WORST frame) of the BEST
         mode's result (all classes "full", attention "corr"), check the combination against `tol_total` and step the most expensive
         offender back up until it holds.  Then the ABSOLUTE check: the chosen combination against a reference-precision engine built from
         the same weights (reference_depth: three 16-bit passes everywhere) -- if that exceeds `tol_abs` the stepping continues, and if even
         the best mode misses the north star's 1e-4 m the report carries a "warning" (bench.py prints it, DepthEstimator warns).  With the
-        reference at hand the neck is then calibrated per product in two stages (AUTO_TOL_NECK_ABS_M, AUTO_TOL_NECK_PLAIN_ABS_M) and the
-        result validated on held-out frames (AUTO_TOL_HOLDOUT_M).
+        reference at hand the neck is then calibrated per product in two stages (tol_neck_abs, tol_neck_plain_abs) and the
+        result validated on held-out frames (tol_holdout).
+        `policy`: every threshold of the procedure (calibration.CalibrationPolicy; default: DEFAULT_POLICY, whose three caller tolerances
+        are 4e-5 / 6e-5 / 8e-5 m); an explicit `tol_class` / `tol_total` / `tol_abs` wins over the policy's value.  The decisions themselves
+        are calibration.py's stages; this method is their device side.
         `frames_u8` [N,H,W,3]: the caller's own calibration frames -- ALL of them are used, every decision is judged on the worst one
-        (default: AUTO_CAL_FRAMES synthetic frames); `holdout_u8`: frames no decision may see (default: AUTO_HOLDOUT_FRAMES synthetic ones).
+        (default: policy.cal_frames synthetic frames); `holdout_u8`: frames no decision may see (default: policy.holdout_frames synthetic ones).
         One forward over the calibration frames per candidate (about fifty plans, each dropped after use).  The report is kept in
         ``self.calibration``.  Only what was left on "auto" is calibrated; classes / attention given a fixed mode keep it."""
         assert self.acc, "calibrate() is for precision='accurate'"
         import time as _time
         t_start = _time.perf_counter()
-        # the same weights, geometry, tolerances and arithmetic switches give the same choice (every kernel is deterministic): a process that
+        given = {k: v for k, v in (("tol_class", tol_class), ("tol_total", tol_total), ("tol_abs", tol_abs)) if v is not None}
+        policy = dataclasses.replace(policy or DEFAULT_POLICY, **given)
+        # the same weights, geometry, policy and arithmetic switches give the same choice (every kernel is deterministic): a process that
         # builds several engines from one weight set (the bench's legs, a test module) calibrates once
         ckey = None
         if frames_u8 is None and holdout_u8 is None and self._sd is not None and reference and neck_candidates is None:
-            ckey = (self._weights_fingerprint(), repr(self.cfg), str(self.dtype), H, W, tuple(self.target_hw), tol_class, tol_total, tol_abs,
+            ckey = (self._weights_fingerprint(), repr(self.cfg), str(self.dtype), H, W, tuple(self.target_hw), repr(policy),
                     self.auto_classes, self.auto_attn, tuple(sorted(self.class_modes.items())), self.attn_mode, self.neck_mode,
-                    self.fuse_mlp, self.add_projection, self.neck_f8,
-                    AUTO_TOL_NECK_ABS_M, AUTO_TOL_NECK_PLAIN_ABS_M, AUTO_TOL_HOLDOUT_M, AUTO_CAL_FRAMES, AUTO_HOLDOUT_FRAMES,
-                    AUTO_NECK_WONLY_INCREMENT_M, AUTO_NECK_PLAIN_INCREMENT_M, AUTO_TOL_NECK_CAP_M,
-                    tuple(os.environ.get(k_, "") for k_ in _ARITHMETIC_SWITCHES))
+                    self.fuse_mlp, self.add_projection, self.neck_f8, tuple(os.environ.get(k_, "") for k_ in _ARITHMETIC_SWITCHES))
             hit = _CALIBRATION_CACHE.get(ckey)
             if hit is not None:
                 self.apply_calibration(hit)
@@ -462,301 +437,73 @@ class ZoeDepthEngine:
         from .synthetic import make_sequence
         synth = lambda seeds: torch.from_numpy(np.concatenate([make_sequence(1, H, W, seed=s_) for s_ in seeds], 0)).to(self.dev)
         if frames_u8 is None:
-            frames_u8 = synth(AUTO_CAL_SEEDS[:AUTO_CAL_FRAMES])
-        frames_u8 = frames_u8.to(self.dev).contiguous()
-        ncal = int(frames_u8.shape[0])
-        H, W = int(frames_u8.shape[1]), int(frames_u8.shape[2])
-        switchable = [k for k in BACKBONE_CLASSES if self.class_modes[k] in ("full", "wcls", "wmean", "wstat")] if self.auto_classes else []
+            frames_u8 = synth(policy.cal_seeds[:policy.cal_frames])
+        m = _Measurement(self, frames_u8.to(self.dev).contiguous())
+        H, W = m.H, m.W
+        wstat = os.environ.get("BS_AUTO_WSTAT") == "1"
+        switchable = tuple(k for k in BACKBONE_CLASSES if self.class_modes[k] in ("full", "wcls", "wmean", "wstat")) if self.auto_classes else ()
         neck_cands = ["full"] if (not self.neck_f8 or not self.auto_classes or (neck_candidates is None and (not reference or self._sd is None))) \
-            else list(neck_candidates or AUTO_NECK_CANDIDATES)
+            else list(neck_candidates or policy.neck_candidates)
         # default (no explicit candidates, absolute reference available): the neck is calibrated per site AFTER the backbone classes and
-        # the attention have been settled with the neck on both products (below); the group candidates are for explicit requests
+        # the attention have been settled with the neck on both products; the group candidates are for explicit requests
         per_site = neck_candidates is None and len(neck_cands) > 1
         if per_site:
             neck_cands = ["full"]
         nh_, nw_ = net_size(H, W, self.target_hw)
         corr_ok = nw_ // self.cfg.patch == 32 and (nh_ // self.cfg.patch) % 2 == 0 and nh_ // self.cfg.patch <= 40
-        attn_best = ("corr" if corr_ok else "single") if self.auto_attn else self.attn_mode
+        scope = Scope(switchable=switchable, class_cands=(("wstat",) if wstat else ()) + tuple(policy.candidates),
+                      fixed_modes={k: self.class_modes[k] for k in BACKBONE_CLASSES}, auto_attn=self.auto_attn,
+                      attn_best=("corr" if corr_ok else "single") if self.auto_attn else self.attn_mode,
+                      neck_full="full" if (len(neck_cands) > 1 or per_site) else self.neck_mode, neck_cands=tuple(neck_cands),
+                      explicit_neck=neck_candidates is not None, per_site=per_site, neck_plain=os.environ.get("BS_NECK_PLAIN", "1") != "0",
+                      saving=saving_gflop(self.cfg.hidden, self.cfg.intermediate, self.cfg.layers,
+                                          1 + (nh_ // self.cfg.patch) * (nw_ // self.cfg.patch), policy.attn_rate_factor))
         saved_auto, self.auto_modes = self.auto_modes, False
-        neck0 = self.neck_mode
-        self.site_bias_corr = {}
-        self._bias_corr_cache.clear()
-        site_flops: Dict[str, float] = {}
-
-        def depth(modes, neck, attn, frames=frames_u8, means=None):
-            """depth maps [n,H,W] of `frames` under a mode combination (one plan, dropped after use); means: a dict that receives the channel
-            means of every neck product's input rows (the run then goes launch by launch through the plan's tap path)"""
-            self.set_class_modes(modes, neck, attn)
-            plan = _ZoePlan(self, int(frames.shape[0]), H, W, True)
-            plan.frames.copy_(frames)
-            plan.run(None if means is None else {"__site_means__": means})
-            d = plan.depth_m.clone()
-            torch.cuda.synchronize(self.dev)
-            site_flops.update(plan.site_flops)
-            del plan
-            return d
-
-        l1f = lambda a, b: (a - b).abs().flatten(1).mean(1)              # per-frame L1
-        worst = lambda a, b: float(l1f(a, b).max())
-
+        m.set_site_bias_corr({})
         full = {k: "full" for k in switchable}
-        neck_full = "full" if (len(neck_cands) > 1 or per_site) else neck0
         bmeans: Dict[str, torch.Tensor] = {}
-        ref = depth(full, neck_full, attn_best, means=bmeans if (switchable and os.environ.get("BS_AUTO_WSTAT") == "1") else None)
-        # The yardstick of every decision below is run twice: the same launches must give the same bits.  (Earlier in round 6 one forward in a few
+        m.ref = m.depth(full, scope.neck_full, scope.attn_best, means=bmeans if (switchable and wstat) else None)
+        # The yardstick of every decision is run twice: the same launches must give the same bits.  (Earlier in round 6 one forward in a few
         # hundred differed beside another process allocating on the same GPU; it was located in the log-binomial kernel, whose shipped form has not
         # shown it since -- DESIGN section 7 -- and the check costs one forward and stays.)  A yardstick that does not reproduce is measured a
         # third time and the report says so.
-        ref2 = depth(full, neck_full, attn_best)
-        rerun_equal = bool(torch.equal(ref, ref2))
+        ref2 = m.depth(full, scope.neck_full, scope.attn_best)
+        rerun_equal = bool(torch.equal(m.ref, ref2))
         if not rerun_equal:
-            ref3 = depth(full, neck_full, attn_best)
-            ref = ref2 if torch.equal(ref2, ref3) else ref
+            ref3 = m.depth(full, scope.neck_full, scope.attn_best)
+            m.ref = ref2 if torch.equal(ref2, ref3) else m.ref
             warnings.warn("ZoeDepthEngine.calibrate: two runs of the same plan differed (is another process using this GPU?); the calibration's choices may not "
                           "be reproducible")
         del ref2
         # "wstat": the static correction rows dW E[a] of every backbone product, from the channel means of its patch rows on the calibration frames
         # (taken with every correction on: the means of the 16-bit values do not depend on the mode to any digit that matters here)
         self.backbone_bias_corr = {k_[3:]: (self.w[k_[3:] + ".lo"].double() * m_.double()).sum(1).float().view(1, -1).contiguous()
-                                   for k_, m_ in bmeans.items() if k_[3:] + ".lo" in self.w}       # (deterministic form: see site_bias_corr below)
+                                   for k_, m_ in bmeans.items() if k_[3:] + ".lo" in self.w}       # (deterministic form: see _Measurement.set_site_bias_corr)
         del bmeans
-        report = {"frame": f"{H}x{W}", "frames": ncal, "statistic": "worst frame (max over the calibration frames of the per-frame mean |d - d_ref|)",
-                  "tol_class_m": tol_class, "tol_total_m": tol_total, "tol_abs_m": tol_abs, "l1_vs_full_m": {}, "yardstick_rerun_equal": rerun_equal}
-        truth = hold = truth_h = None
+        report = {"frame": f"{H}x{W}", "frames": m.ncal, "statistic": "worst frame (max over the calibration frames of the per-frame mean |d - d_ref|)",
+                  "tol_class_m": policy.tol_class, "tol_total_m": policy.tol_total, "tol_abs_m": policy.tol_abs, "l1_vs_full_m": {},
+                  "yardstick_rerun_equal": rerun_equal}
         if reference and self._sd is not None:
-            if holdout_u8 is None and per_site and AUTO_HOLDOUT_FRAMES > 0:
-                holdout_u8 = synth(AUTO_HOLDOUT_SEEDS[:AUTO_HOLDOUT_FRAMES])
+            if holdout_u8 is None and per_site and policy.holdout_frames > 0:
+                holdout_u8 = synth(policy.holdout_seeds[:policy.holdout_frames])
             if holdout_u8 is not None:
-                hold = holdout_u8.to(self.dev).contiguous()
-                assert tuple(hold.shape[1:]) == tuple(frames_u8.shape[1:])
-            t_all = self.reference_depth(frames_u8 if hold is None else torch.cat([frames_u8, hold], 0))     # ONE reference engine for both sets
-            truth, truth_h = t_all[:ncal], (t_all[ncal:] if hold is not None else None)
-            report["l1_best_vs_reference_m"] = worst(ref, truth)          # the floor: nothing the calibration chooses can be closer than this
-        chosen, cost = dict(full), {}
-        cands_cls = (("wstat",) if os.environ.get("BS_AUTO_WSTAT") == "1" else ()) + tuple(AUTO_CANDIDATES)
-        for k in switchable:
-            for cand in cands_cls:
-                if cand == "full":
-                    chosen[k], cost[k] = "full", 0.0
-                    break
-                l1 = worst(depth({**full, k: cand}, neck_full, attn_best), ref)
-                report["l1_vs_full_m"][f"{k}:{cand}"] = l1
-                if l1 <= tol_class:
-                    chosen[k], cost[k] = cand, l1
-                    break
-        attn = attn_best
-        if self.auto_attn and attn_best == "corr":
-            l1 = worst(depth(full, neck_full, "single"), ref)
-            report["l1_vs_full_m"]["attn:single"] = l1
-            if l1 <= tol_class:
-                attn, cost["attn"] = "single", l1
-        neck = neck_full
-        for cand in neck_cands:
-            if cand == "full":
-                break
-            l1 = worst(depth(full, cand, attn_best), ref)
-            report["l1_vs_full_m"][f"neck:{cand}"] = l1
-            if l1 <= tol_class:
-                neck, cost["neck"] = cand, l1
-                break
-        saving = self._saving_gflop(1 + (nh_ // self.cfg.patch) * (nw_ // self.cfg.patch))
-        passes_saved = {"wstat": 1.02, "wmean": 1.0, "wcls": 0.5, "full": 0.0}
-
-        def step_up():
-            """the live choice that pays the most depth error per unit of work saved goes one step back up; False when none is left"""
-            nonlocal neck, attn
-            live = [k_ for k_ in cost if cost[k_] > 0.0]
-            if not live:
-                return False
-            def worth(k_):
-                if k_ == "neck":
-                    return 0.5 * sum(site_flops.values()) / max(2 * ncal, 1) / 1e9
-                return saving[k_] * (1.0 if k_ == "attn" else passes_saved[chosen[k_]])
-            worst_k = max(live, key=lambda k_: cost[k_] / max(worth(k_), 1e-9))
-            if worst_k == "neck":
-                neck = neck_full
-            elif worst_k == "attn":
-                attn = attn_best
-            else:
-                chosen[worst_k] = cands_cls[min(cands_cls.index(chosen[worst_k]) + 1, len(cands_cls) - 1)]
-            cost[worst_k] = 0.0 if (worst_k in ("neck", "attn") or chosen[worst_k] == "full") else report["l1_vs_full_m"].get(f"{worst_k}:{chosen[worst_k]}", 0.0)
-            return True
-
-        # the combination, against the best mode and then against the reference
-        while True:
-            cheap = any(v != "full" for v in chosen.values()) or neck != neck_full or attn != attn_best
-            d_c = depth(chosen, neck, attn) if cheap else ref
-            total = worst(d_c, ref) if cheap else 0.0
-            l1_abs = worst(d_c, truth) if truth is not None else None
-            if neck != neck_full and neck_candidates is None and l1_abs is not None and l1_abs > AUTO_TOL_NECK_ABS_M:
-                neck, cost["neck"] = neck_full, 0.0           # the cheaper neck is only worth half the tolerance (see AUTO_TOL_NECK_ABS_M)
-                continue
-            if total <= tol_total and (l1_abs is None or l1_abs <= tol_abs):
-                break
-            if not step_up():
-                break
-        report["l1_backbone_choice_vs_reference_m"] = l1_abs
-        wsites, plain, cand_sites = [], [], {}
-
-        def site_mode(names, pl=()):
-            """the neck mode that runs the named candidates weight-only and those of `pl` on one pass"""
-            return "wonly:" + ",".join(sorted(k_ for n_ in names for k_ in cand_sites[n_])) + \
-                (";plain:" + ",".join(sorted(k_ for n_ in pl for k_ in cand_sites[n_])) if pl else "")
-
-        def executed_gflop(chosen_, attn_, wsites_, plain_):
-            """executed work per network input in 16-bit-pass GFLOP (backbone classes + attention + neck products): what the outer loop below
-            minimises -- a proxy for time that needs no timing run"""
-            g = sum(saving[k_] * {"wstat": 0.98, "wmean": 1.0, "wcls": 1.5, "full": 2.0}.get(chosen_.get(k_, self.class_modes[k_]), 2.0) for k_ in BACKBONE_CLASSES)
-            g += saving["attn"] * (0.5 if attn_ == "single" else 1.5)
-            wk = {k_ for n_ in wsites_ for k_ in cand_sites[n_]}
-            pk = {k_ for n_ in plain_ for k_ in cand_sites[n_]}
-            for k_, f_ in site_flops.items():
-                g += f_ / max(2 * ncal, 1) / 1e9 * (1.0 if k_ in pk else (1.5 if k_ in wk else 2.0))
-            return g
-
-        def neck_stages(chosen_, attn_, d_c_, l1_abs_, total_):
-            """the two per-product stages of the neck under one backbone choice -> dict(neck, wsites, plain, l1_abs, total, rep, corr)"""
-            out = dict(neck=neck_full, wsites=[], plain=[], l1_abs=l1_abs_, total=total_, rep=None, corr={})
-            tol_neck1 = min(max(AUTO_TOL_NECK_ABS_M, l1_abs_ + AUTO_NECK_WONLY_INCREMENT_M), AUTO_TOL_NECK_CAP_M)
-            if l1_abs_ > AUTO_TOL_NECK_CAP_M - AUTO_NECK_WONLY_INCREMENT_M:
-                return out
-            # ---- candidate by candidate: what each product (or group of small products) costs when it alone drops the activation-rounding
-            # correction (against the combination chosen so far), then the longest prefix of the error-per-FLOP order that stays within the
-            # stage's budget against the reference AND within tol_total of the best mode.  The error grows along that order
-            # (tools/probes/neck_site_study.py), so the prefix is bisected.
-            tot_f = sum(site_flops.values()) or 1.0
-            if not cand_sites:
-                for k_, f_ in site_flops.items():
-                    if k_.endswith("w_cls") or k_.startswith("mh."):
-                        continue
-                    if f_ >= AUTO_NECK_SITE_MIN_SHARE * tot_f:
-                        cand_sites[k_] = [k_]
-                    else:
-                        g_ = next((n_ for n_, pre in AUTO_NECK_SMALL_GROUPS.items() if any(k_.startswith(p_) for p_ in pre)), None)
-                        if g_ is not None:
-                            cand_sites.setdefault("group:" + g_, []).append(k_)
-            cflops = {n_: sum(site_flops[k_] for k_ in ks) for n_, ks in cand_sites.items()}
-            err = {n_: worst(depth(chosen_, site_mode([n_]), attn_), d_c_) for n_ in cand_sites}
-            order = sorted(cand_sites, key=lambda n_: err[n_] / cflops[n_])
-            lo, hi, kept = 0, len(order), None
-            while lo < hi:
-                mid = (lo + hi + 1) // 2
-                d_s = depth(chosen_, site_mode(order[:mid]), attn_)
-                a_, t_ = worst(d_s, truth), worst(d_s, ref)
-                if a_ <= tol_neck1 and t_ <= tol_total:
-                    lo, kept = mid, (a_, t_)
-                else:
-                    hi = mid - 1
-            ws = list(order[:lo])
-            rep = {"tol_abs_m": tol_neck1, "groups": {n_: ks for n_, ks in cand_sites.items() if n_.startswith("group:")},
-                   "l1_alone_vs_chosen_m": {n_: round(err[n_], 8) for n_ in order}, "weight_only": ws,
-                   "flops_share_weight_only": round(sum(cflops[n_] for n_ in ws) / tot_f, 4)}
-            out.update(wsites=ws, rep=rep)
-            if lo > 0:
-                out.update(neck=site_mode(ws), l1_abs=kept[0], total=kept[1])
-            if lo > 0 and os.environ.get("BS_NECK_PLAIN", "1") != "0":
-                # ---- second stage: one 16-bit pass for the weight-only candidates, largest first, with the static bias correction
-                means: Dict[str, torch.Tensor] = {}
-                self.site_bias_corr = {}
-                self._bias_corr_cache.clear()
-                depth(chosen_, out["neck"], attn_, means=means)      # channel means of every product's input rows on the calibration frames
-                for k_, m_ in means.items():
-                    k_ = k_[3:]                                       # "in:<weight key>"
-                    if k_ in self.dw_sum:
-                        # (multiply + tree sum in fp64, not a library GEMV: split-K atomics would make the low bits -- and with them a borderline
-                        # decision below -- differ between two processes calibrating the same weights)
-                        self.site_bias_corr[k_] = (self.dw_sum[k_].double() * m_.double()).sum(1).float().contiguous()
-                cands = sorted((n_ for n_ in ws if cand_sites[n_] != ["rh.conv2.w"] and (n_.startswith("group:") or cflops[n_] >= AUTO_NECK_PLAIN_MIN_SHARE * tot_f)),
-                               key=lambda n_: -cflops[n_])
-                a0 = worst(depth(chosen_, out["neck"], attn_), truth)
-                tol_neck2 = min(max(AUTO_TOL_NECK_PLAIN_ABS_M, a0 + AUTO_NECK_PLAIN_INCREMENT_M), AUTO_TOL_NECK_CAP_M)
-                pl, trail, a_now = [], {}, a0
-                for n_ in cands:
-                    d_p = depth(chosen_, site_mode(ws, pl + [n_]), attn_)
-                    a_, t_ = worst(d_p, truth), worst(d_p, ref)
-                    trail[n_] = round(a_, 8)
-                    if a_ <= tol_neck2 and t_ <= tol_total:
-                        pl.append(n_)
-                        a_now = a_
-                        out.update(l1_abs=a_, total=t_)
-                rep.update(plain_tol_abs_m=tol_neck2, l1_weight_only_m=round(a0, 8), l1_with_candidate_plain_m=trail, plain=list(pl),
-                           l1_plain_m=round(a_now, 8), flops_share_plain=round(sum(cflops[n_] for n_ in pl) / tot_f, 4),
-                           static_bias_correction=sorted(self.site_bias_corr))
-                out.update(plain=pl, corr=dict(self.site_bias_corr))
-                if pl:
-                    out["neck"] = site_mode(ws, pl)
-            return out
-
-        if per_site and truth is not None and l1_abs is not None:
-            best = neck_stages(chosen, attn, d_c, l1_abs, total)
-            best_cost = executed_gflop(chosen, attn, best["wsites"], best["plain"])
-            # (The stages run in sequence: the backbone classes take the cheapest modes their own tolerances allow, the neck gets what is left of
-            # its budget -- on some weight sets little: eight seeds, round 6: a backbone choice at 5.4e-5 m leaves the neck two products and the
-            # rate 8 % under the median.  Trading the other way was tried and does not pay -- a tighter backbone budget (3.5e-5 / 4.2e-5 m) made
-            # those seeds 21 % / 4 % SLOWER, and a search over single class steps with the neck stages redone under each found no combination
-            # with less executed work on four seeds: a backbone class one step up costs more than the neck products it frees.
-            # profiles/r06_calibration_experiments.txt)
-            neck, wsites, plain, l1_abs, total = best["neck"], best["wsites"], best["plain"], best["l1_abs"], best["total"]
-            self.site_bias_corr = dict(best["corr"])
-            self._bias_corr_cache.clear()
-            if best["rep"] is not None:
-                report["neck_sites"] = best["rep"]
-            report["executed_gflop_per_input"] = round(best_cost, 1)
-        # ---- held-out validation: frames no decision above has seen.  Above the line the latest relaxations are withdrawn, newest first
-        if hold is not None:
-            hv = {"tol_m": AUTO_TOL_HOLDOUT_M, "frames": int(hold.shape[0]), "withdrawn": []}
-            neck_base = neck if not wsites else neck_full
-            while True:
-                per = l1f(depth(chosen, neck, attn, frames=hold), truth_h)
-                if float(per.max()) <= AUTO_TOL_HOLDOUT_M:
-                    break
-                if plain:
-                    hv["withdrawn"].append("plain:" + plain.pop())
-                elif wsites:
-                    hv["withdrawn"].append("wonly:" + wsites.pop())
-                elif step_up():
-                    hv["withdrawn"].append("backbone step")
-                else:
-                    break
-                neck = site_mode(wsites, plain) if wsites else neck_base
-            if hv["withdrawn"]:
-                d_c = depth(chosen, neck, attn)
-                l1_abs, total = worst(d_c, truth), worst(d_c, ref)
-                if "neck_sites" in report:
-                    report["neck_sites"].update(weight_only=list(wsites), plain=list(plain))
-            hv.update(l1_frames_m=[round(float(v), 8) for v in per], l1_max_m=round(float(per.max()), 8), l1_mean_m=round(float(per.mean()), 8))
-            report["holdout"] = hv
-        if self.auto_attn and not corr_ok:
-            # the split-precision kernel could not be tried on this geometry (every candidate above ran "single"): the engine keeps "corr",
-            # which a plan of a capable geometry then uses and this one falls back from (_ZoePlan) -- "single" must be earned by a measurement
-            attn = "corr"
-            report["attn_note"] = f"attention not calibrated on a {nh_}x{nw_} network input (no split-precision kernel for it): kept at 'corr'"
+                m.hold = holdout_u8.to(self.dev).contiguous()
+                assert tuple(m.hold.shape[1:]) == tuple(m.frames.shape[1:])
+            t_all = self.reference_depth(m.frames if m.hold is None else torch.cat([m.frames, m.hold], 0))     # ONE reference engine for both sets
+            m.truth, m.truth_hold = t_all[:m.ncal], (t_all[m.ncal:] if m.hold is not None else None)
+            report["l1_best_vs_reference_m"] = worst(m.ref, m.truth)          # the floor: nothing the calibration chooses can be closer than this
+        c = choose(policy, scope, m, report)
         # the static corrections travel with the report (a sharded run's ranks all apply rank 0's): only those of the sites that run one pass
-        keep_corr = {k_ for part in neck.split(";") if part.startswith("plain:") for k_ in part[6:].split(",")}
+        keep_corr = {k_ for part in c.neck.split(";") if part.startswith("plain:") for k_ in part[6:].split(",")}
         self.site_bias_corr = {k_: v for k_, v in self.site_bias_corr.items() if k_ in keep_corr}
         self._bias_corr_cache.clear()
-        final_modes = {**{k: self.class_modes[k] for k in BACKBONE_CLASSES}, **chosen}
+        final_modes = {**scope.fixed_modes, **c.modes}
         self.backbone_bias_corr = {k_: v for k_, v in self.backbone_bias_corr.items() if final_modes.get(k_.split(".")[-2]) == "wstat"}
-        report.update(class_modes=final_modes, neck_mode=neck, attn_mode=attn,
-                      l1_total_vs_full_m=total, l1_abs_vs_reference_m=l1_abs,
-                      site_bias_corr={k_: v.cpu().tolist() for k_, v in self.site_bias_corr.items()},
-                      backbone_bias_corr={k_: v.view(-1).cpu().tolist() for k_, v in self.backbone_bias_corr.items()})
-        if l1_abs is not None and l1_abs > TOLERANCE_M:
-            fixed = [k for k in BACKBONE_CLASSES if k not in switchable]
-            report["warning"] = (f"depth L1 of the calibration frames against the reference-precision engine is {l1_abs:.2e} m with every calibrated "
-                                 f"choice at its most accurate: above the {TOLERANCE_M:.0e} m tolerance for these weights"
-                                 + (f" (modes fixed by the caller, not calibrated: {({k: self.class_modes[k] for k in fixed})})" if fixed else ""))
-            warnings.warn("ZoeDepthEngine.calibrate: " + report["warning"])
-        elif truth is None:
-            report["note"] = "no absolute reference (the engine holds no source weights): l1_total_vs_full_m is relative to the best mode only"
-        if truth is not None and report.get("l1_best_vs_reference_m", 0.0) > 0.5 * TOLERANCE_M and "warning" not in report:
-            # (round 6, the outlier-channel weights: the best mode reads 5.1e-5 m on the calibration frames and 1.2e-5 ... 2.2e-4 m on eight frames of
-            # the bench's sequence -- on such weights the error of the e4m3 correction planes varies several-fold from frame to frame)
-            report["margin_note"] = (f"even with every correction on, the calibration frames read {report['l1_best_vs_reference_m']:.2e} m against the reference-precision "
-                                     f"engine -- more than half the {TOLERANCE_M:.0e} m tolerance: frames with other statistics may exceed it.  precision='reference' "
-                                     "(three 16-bit passes per product) holds ~1.5e-5 m on such weights at about half the rate")
-            warnings.warn("ZoeDepthEngine.calibrate: " + report["margin_note"])
-        self.set_class_modes(chosen, neck, attn)
+        for msg in finish_report(policy, scope, c, report, None if (corr_ok or not self.auto_attn) else f"{nh_}x{nw_}",
+                                 {k_: v.cpu().tolist() for k_, v in self.site_bias_corr.items()},
+                                 {k_: v.view(-1).cpu().tolist() for k_, v in self.backbone_bias_corr.items()}, m.truth is not None):
+            warnings.warn("ZoeDepthEngine.calibrate: " + msg)
+        self.set_class_modes(c.modes, c.neck, c.attn)
         self.auto_modes = saved_auto
         torch.cuda.synchronize(self.dev)
         report["calibrate_s"] = round(_time.perf_counter() - t_start, 2)

@@ -13,6 +13,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import bodyslam_amd.zoedepth as ZD  # noqa: E402
+from bodyslam_amd.calibration import CalibrationPolicy  # noqa: E402
 from bodyslam_amd.synthetic import WEIGHT_VARIANTS, make_sequence, random_zoedepth_weights  # noqa: E402
 
 seeds = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "0").split(",")]
@@ -27,11 +28,10 @@ for seed in seeds:
         WEIGHT_VARIANTS[variant](w)
     truth = None
     for (t_abs, t_plain, t_hold) in sets:
-        ZD.AUTO_TOL_NECK_ABS_M, ZD.AUTO_TOL_NECK_PLAIN_ABS_M, ZD.AUTO_TOL_HOLDOUT_M = t_abs, t_plain, t_hold
-        ZD._CALIBRATION_CACHE.clear()
+        policy = CalibrationPolicy(tol_neck_abs=t_abs, tol_neck_plain_abs=t_plain, tol_holdout=t_hold)      # (the cache keys on the policy)
         eng = ZD.ZoeDepthEngine(w, cfg, precision="accurate")
         t0 = time.time()
-        cal = eng.calibrate(H, W)
+        cal = eng.calibrate(H, W, policy=policy)
         t_cal = time.time() - t0
         if truth is None:
             truth = eng.reference_depth(test_frames)
