@@ -310,44 +310,8 @@ class Plan:
         self.gemm_info = {}  # call index -> dict(tile, conv, flops, bytes)
         self.stack_info = {} # call index -> dict(name, alg_flops, flops): launches other than bs_gemm that carry matrix-core work of a GEMM / conv
                              # the reference has (the fused up-convolution, the attractor MLPs): timed with the GEMMs for the roofline
-        self.lane = 0        # lane of the calls being added: 0 = the caller's stream, 1 = the plan's side stream
-        self.lanes = []      # per call
         self.events = None   # a list: run() records a HIP event pair around every bs_gemm launch into it (see run_timed)
         self._graph = None   # torch.cuda.CUDAGraph of the captured sequence (capture())
-        self._side = None    # torch side stream + fork / join events, created at the first run
-        self._events = {}
-
-    # ---- two-lane plans: calls added while `lane` is 1 are issued on the plan's side stream.  `signal(k)` records event k on
-    # the current lane's stream, `wait(k)` makes the current lane's stream wait for it: a run of small, latency-bound kernels
-    # that only depends on data available at some point of the main lane overlaps the main lane's big kernels from there on
-    # (the bins head's router / seeds / attractor chain beside the fusion stage and the relative head).
-    def signal(self, k: int):
-        self.calls.append(("signal", (k, self.lane)))
-        self.names.append(f"signal{k}")
-        self.lanes.append(self.lane)
-
-    def wait(self, k: int):
-        self.calls.append(("wait", (k, self.lane)))
-        self.names.append(f"wait{k}")
-        self.lanes.append(self.lane)
-
-    def _streams(self):
-        main = torch.cuda.current_stream(self.device)
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-            self._events = {}
-        return main, self._side
-
-    def _sync_op(self, op, args, main, side):
-        k, lane = args
-        ev = self._events.get(k)
-        if ev is None:
-            ev = self._events[k] = torch.cuda.Event()
-        st = side if lane else main
-        if op == "signal":
-            ev.record(st)
-        else:
-            st.wait_event(ev)
 
     def gemm(self, name, A, W, out, **kw):
         passes = kw.pop("precision_passes", 1)
@@ -357,7 +321,6 @@ class Plan:
         self.keep_descs.append(d)
         self.calls.append((load_library().bs_gemm, (C.byref(d),)))
         self.names.append(name)
-        self.lanes.append(self.lane)
         # bookkeeping for the roofline: which kernel instantiation and how many algorithmic FLOPs
         self.gemm_info[len(self.calls) - 1] = dict(
             name=name, tile=load_library().bs_gemm_tile(C.byref(d)), conv=bool(d.conv),
@@ -382,7 +345,6 @@ class Plan:
                 cargs.append(a)
         self.calls.append((getattr(load_library(), fn_name), tuple(cargs)))
         self.names.append(name)
-        self.lanes.append(self.lane)
 
     def tag_stack(self, alg_flops: float, flops: float):
         """the call added last carries this much matrix-core work (algorithmic / executed in 16-bit-pass equivalents)"""
@@ -394,42 +356,35 @@ class Plan:
     def run_timed(self, events: list):
         """Like run(), with a HIP event pair (recorded on the launch stream) around every bs_gemm launch;
         appends (call_index, start_event, end_event) to `events`."""
-        main, side = self._streams()
-        sts = (main, side)
-        ptrs = (main.cuda_stream, side.cuda_stream)
+        stream = torch.cuda.current_stream(self.device)
+        st = stream.cuda_stream
         for i, (fn, args) in enumerate(self.calls):
-            if isinstance(fn, str):
-                self._sync_op(fn, args, main, side)
-                continue
-            ln = self.lanes[i]
             if i in self.gemm_info or i in self.stack_info:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(sts[ln])
-                rc = fn(*args, ptrs[ln])
-                e1.record(sts[ln])
+                e0.record(stream)
+                rc = fn(*args, st)
+                e1.record(stream)
                 events.append((i, e0, e1))
             else:
-                rc = fn(*args, ptrs[ln])
+                rc = fn(*args, st)
             if rc:
                 check(rc, self.names[i])
 
     def capture(self):
-        """Capture the whole launch sequence (both lanes, their fork / join events, the GEMM tail launches) into one HIP graph;
+        """Capture the whole launch sequence (with the GEMM tail launches the library forks itself) into one HIP graph;
         run() then replays it with a single hipGraphLaunch instead of ~600 ctypes calls.  The buffers are static, so the
         captured pointers stay valid; inputs are copied into them before run() as usual.  Worth it for the reference's
         one-frame-per-call pattern (host time 3.6 ms -> ~0.1 ms per forward; the GPU time does not change)."""
         if self._graph is not None:
             return
-        self.run()                              # warm-up: first-use attribute calls, lazy streams and events
+        self.run()                              # warm-up: first-use attribute calls, the library's lazy streams and events
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         cap = torch.cuda.Stream(device=self.device)
         cap.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(cap):
             with torch.cuda.graph(g, stream=cap, capture_error_mode="thread_local"):
-                self._events = {}               # events recorded during capture belong to the capture
                 self.run()
-        self._events = {}
         torch.cuda.current_stream(self.device).wait_stream(cap)
         self._graph = g
 
@@ -439,19 +394,14 @@ class Plan:
         if taps is None and self._graph is not None and not torch.cuda.is_current_stream_capturing():
             self._graph.replay()
             return
+        st = torch.cuda.current_stream(self.device).cuda_stream
         if taps is None:
-            main, side = self._streams()
-            ptrs = (main.cuda_stream, side.cuda_stream)
             for i, (fn, args) in enumerate(self.calls):
-                if isinstance(fn, str):
-                    self._sync_op(fn, args, main, side)
-                    continue
-                rc = fn(*args, ptrs[self.lanes[i]])
+                rc = fn(*args, st)
                 if rc:
                     check(rc, self.names[i])
             return
-        st = torch.cuda.current_stream(self.device).cuda_stream       # tap mode (tests): one stream, program order
-        means = taps.get("__site_means__")
+        means = taps.get("__site_means__")                # tap mode (tests, the calibration's channel means)
         for i in range(len(self.calls) + 1):
             for (name, t, meta) in self.marks.get(i, []):
                 if meta and meta[0] == "chanmean":
@@ -465,8 +415,6 @@ class Plan:
                     taps[name] = (t.clone(), meta)
             if i < len(self.calls):
                 fn, args = self.calls[i]
-                if isinstance(fn, str):
-                    continue
                 check(fn(*args, st), self.names[i])
 
 

@@ -6,9 +6,9 @@ A plan (``_lib.Plan``) is a fixed sequence of C-ABI launches over static device 
 
   * every device buffer the launches touch: workspace (size only), zero-initialised (size only) or constant (weights in their packed
     device form, tables: size + bytes),
-  * every launch: entry-point name, stream lane, arguments -- integers, floats, and device pointers as (buffer, offset); a
-    ``bs_gemm`` descriptor goes in as its raw bytes plus the (field offset -> buffer, offset) relocations of its pointer fields,
-  * the fork / join events between the two lanes,
+  * every launch: entry-point name, stream lane (always 0: a plan is one chain; the loader still accepts the second lane and the fork /
+    join records of older files), arguments -- integers, floats, and device pointers as (buffer, offset); a ``bs_gemm`` descriptor goes in
+    as its raw bytes plus the (field offset -> buffer, offset) relocations of its pointer fields,
   * named input / output regions ("frames", "depth_m", "depth_u16"; "frames", "pairs", "T").
 
 ``bs_engine_load`` (csrc/engine.hip) allocates the buffers, uploads the constants and resolves the entry points inside the library;
@@ -31,7 +31,7 @@ from . import _lib as L
 MAGIC = b"BSENG02\0"      # csrc/engine.hip kMagic: bumped with every change of an enum's meaning or of bs_gemm_desc's layout
 KIND_WORKSPACE, KIND_ZERO, KIND_DATA = 0, 1, 2
 ARG_I64, ARG_F64, ARG_PTR, ARG_NULL, ARG_DESC = 0, 1, 2, 3, 4
-OP_CALL, OP_SIGNAL, OP_WAIT = 0, 1, 2
+OP_CALL = 0               # (1 / 2: the signal / wait records of older files' second lane; the exporter writes none)
 
 
 def _tensors(obj, out: list):
@@ -91,7 +91,7 @@ def export_plan(plan: L.Plan, path: str, io: Dict[str, torch.Tensor], workspace:
     desc_of = {}
     gi = 0
     for i, (fn, args) in enumerate(plan.calls):
-        if not isinstance(fn, str) and fn.__name__ == "bs_gemm":
+        if fn.__name__ == "bs_gemm":
             desc_of[i] = plan.keep_descs[gi]
             gi += 1
     ptr_fields = [(name, getattr(L.GemmDesc, name).offset) for name, ty in L.GemmDesc._fields_ if ty is C.c_void_p]
@@ -99,16 +99,10 @@ def export_plan(plan: L.Plan, path: str, io: Dict[str, torch.Tensor], workspace:
     calls = bytearray()
     n_ops = 0
     for i, (fn, args) in enumerate(plan.calls):
-        if isinstance(fn, str):
-            k, lane = args
-            calls += struct.pack("<II", OP_SIGNAL if fn == "signal" else OP_WAIT, lane) + _pack_name("", 48) + struct.pack("<I", 1)
-            calls += struct.pack("<Iq", ARG_I64, int(k))
-            n_ops += 1
-            continue
         name = fn.__name__
         sig = L._SIGS[name][:-1]                       # the trailing stream is supplied at run time
         assert len(sig) == len(args), (name, len(sig), len(args))
-        calls += struct.pack("<II", OP_CALL, plan.lanes[i]) + _pack_name(name, 48) + struct.pack("<I", len(args))
+        calls += struct.pack("<II", OP_CALL, 0) + _pack_name(name, 48) + struct.pack("<I", len(args))
         for j, (ty, a) in enumerate(zip(sig, args)):
             if name == "bs_gemm":
                 d = desc_of[i]

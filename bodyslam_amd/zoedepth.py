@@ -122,9 +122,8 @@ ACCURATE_NECK_MODE = "full"
 # profiles/r03_fp4_corrections.txt.  It never paid and was removed in round 4; the correction products run on the block-scaled FP8 MFMA.)
 
 _CALIBRATION_CACHE: Dict[Tuple, dict] = {}        # process-wide: (weights fingerprint, geometry, tolerances, ...) -> calibration report
-# environment switches that change the arithmetic a calibration measures (A / B runs): part of the cache key (round-5 advisor)
-_ARITHMETIC_SWITCHES = ("BS_PJ_LOWRES", "BS_UPCONV_FUSED", "BS_CLB_COMPOSED", "BS_RELU_OUT", "BS_NECK_PLAIN", "BS_MLP2", "BS_NECK_BIAS_CORR",
-                        "BS_PROJECTOR_LEVEL", "BS_AUTO_WSTAT")
+# environment switches that change the arithmetic a calibration measures (A / B runs): part of the cache key
+_ARITHMETIC_SWITCHES = ("BS_UPCONV_FUSED", "BS_NECK_PLAIN", "BS_MLP2", "BS_NECK_BIAS_CORR", "BS_PROJECTOR_LEVEL", "BS_AUTO_WSTAT")
 
 ZOED_NK = ZoeConfig()
 ZOED_N = ZoeConfig(head_names=("nyu",))
@@ -688,9 +687,7 @@ class ZoeDepthEngine:
         R = c.rel_features
         X = 1 if single else 0                                     # the single head's extra input: the relative depth
         w00, w01 = two("clb", "0.weight")                          # [HID, R + X + E] = [last R | (rel depth) | emb E]
-        w["clb.emb.w"] = self._wn(torch.cat([w00[:, R + X:], w01[:, R + X:]], 0))                               # [2*HID, E]
-        w["clb.emb.b"] = self._f(torch.cat(two("clb", "0.bias")))
-        # Round 5: the embedding half of the log-binomial MLP's first layer reads the LAST projector's output emb = W_c2 e1 + b_c2 (a 1x1 convolution
+        # The embedding half of the log-binomial MLP's first layer reads the LAST projector's output emb = W_c2 e1 + b_c2 (a 1x1 convolution
         # without activation, HF modeling_zoedepth.py:749-772): two linear maps in a row.  Composed here in fp32 -- (W_clb W_c2) e1 + (W_clb b_c2 +
         # b_clb) -- the product reads the projector's 64-channel hidden map instead of the 128-channel embedding (half the bytes, half the K).
         wce = torch.cat([w00[:, R + X:], w01[:, R + X:]], 0)                                                   # [2*HID, E]
@@ -795,16 +792,14 @@ class ZoeDepthEngine:
 class _Pool:
     """Plan-time buffer reuse.  The launch sequence of a plan is fixed, so the lifetime of every intermediate is known while the
     plan is being built: ``free(t)`` -- placed right after the call that reads ``t`` last -- returns its block, and a later
-    ``alloc`` of at most that size takes it over (best fit).  Kernels of the main lane run in program order, so a block handed
-    on at build position p is only ever overwritten by work issued after p.  A side lane (Plan.lane = 1; unused since round 5) must not use pooled blocks
-    (``hold``): it runs beside main-lane kernels that were added later."""
+    ``alloc`` of at most that size takes it over (best fit).  A plan's kernels run in program order on one stream, so a block handed
+    on at build position p is only ever overwritten by work issued after p."""
 
     def __init__(self, dev):
         self.dev = dev
         self.free_blocks = []        # uint8 tensors
         self.blocks = []             # every block ever made (engine export: pooled intermediates carry no data)
         self.owner = {}              # data_ptr -> block
-        self.hold = False
         self.bytes_new = 0
 
     def alloc(self, shape, dtype):
@@ -812,13 +807,11 @@ class _Pool:
         for d in shape:
             n *= int(d)
         nbytes = max(n * torch.empty((), dtype=dtype).element_size(), 16)
-        blk = None
-        if not self.hold:
-            fits = [b for b in self.free_blocks if b.numel() >= nbytes]
-            if fits:
-                blk = min(fits, key=lambda b: b.numel())
-                self.free_blocks = [b for b in self.free_blocks if b is not blk]
-        if blk is None:
+        fits = [b for b in self.free_blocks if b.numel() >= nbytes]
+        if fits:
+            blk = min(fits, key=lambda b: b.numel())
+            self.free_blocks = [b for b in self.free_blocks if b is not blk]
+        else:
             blk = torch.empty((nbytes + 255) // 256 * 256, dtype=torch.uint8, device=self.dev)
             self.bytes_new += blk.numel()
             self.blocks.append(blk)
@@ -834,142 +827,241 @@ class _Pool:
 
 
 class _ZoePlan:
-    """All buffers + the launch sequence for one (frames, H, W, flip) configuration."""
+    """All buffers + the launch sequence for one (frames, H, W, flip) configuration.
+
+    __init__ fixes the geometry and the format flags and then runs the stages in the network's order; a stage is a method that takes and
+    returns its tensors.  Intermediates of the neck / heads come from a pool and are handed on after their last reader (``pool.free``); the
+    backbone's buffers (whose padding rows must stay zero) are plain allocations.  The pool is best-fit over a free list, so the ORDER of
+    alloc / free across the stages is the buffer layout: tools/plan_digest.py prints a plan in an address-free form to diff two builders."""
+
+    MEAN_STEP = 8      # the rank-1 correction's token mean uses every 8th patch row (probe: same depth result as the full mean)
+    F8O = (L.F8_ACT_HI_EXP, L.F8_ACT_LO_EXP)
 
     def __init__(self, eng: ZoeDepthEngine, B: int, H: int, W: int, flip: bool):
-        self.eng = eng
-        c, w, dt_, dev = eng.cfg, eng.w, eng.dtype, eng.dev
-        NB = 2 * B if flip else B
-        nh_, nw_ = net_size(H, W, eng.target_hw)
-        hp, wp = nh_ // c.patch, nw_ // c.patch
-        T0 = hp * wp
-        S = T0 + 1
-        Sp = (S + 63) // 64 * 64
-        Hd = c.hidden
+        self.eng, self.c, self.w = eng, eng.cfg, eng.w
+        c = eng.cfg
+        self.B, self.H, self.W, self.flip = B, H, W, flip
+        self.NB = NB = 2 * B if flip else B
+        self.nh, self.nw = nh_, nw_ = net_size(H, W, eng.target_hw)
+        self.hp, self.wp = hp, wp = nh_ // c.patch, nw_ // c.patch
+        self.T0 = T0 = hp * wp
+        self.S = S = T0 + 1
+        self.Sp = Sp = (S + 63) // 64 * 64
         self.geom = dict(B=B, NB=NB, H=H, W=W, nh=nh_, nw=nw_, hp=hp, wp=wp, S=S, Sp=Sp)
         self.site_flops: Dict[str, float] = {}      # FP8-format neck / head products of this plan: weight key -> algorithmic FLOPs
-        P = L.Plan(dev)
-        self.plan = P
-        # intermediates of the neck / heads come from a pool and are handed on after their last reader (free); the backbone's
-        # buffers (whose padding rows must stay zero) are plain allocations
-        pool = _Pool(dev)
-        self.pool = pool
-        e16 = lambda *s: pool.alloc(s, dt_)
-        z16 = lambda *s: torch.zeros(*s, device=dev, dtype=dt_)
-        e32 = lambda *s: pool.alloc(s, torch.float32)
-        free = pool.free
-        use_tab = wp == 32 and hp <= 40         # every 512-wide network input: bias from the per-head table held in LDS
-        bias = eng._rel_table(hp, wp) if use_tab else eng._rel_bias(hp, wp, Sp)
+        self.plan = L.Plan(eng.dev)
+        self.pool = _Pool(eng.dev)
+        self.use_tab = wp == 32 and hp <= 40         # every 512-wide network input: bias from the per-head table held in LDS
         # Row order of the token tensors (residual stream, LN / attention outputs, MLP hidden).  Grouped (with the table
         # attention): rows [0, NB) are the cls tokens of the NB images, row NB + b*T0 + t is patch t of image b -- the cls rows
         # sit in the first GEMM tile, which alone evaluates the activation-rounding correction ("wcls", bs_gemm f8_wonly_from).
         # Otherwise image-major, cls first ([NB, S, hidden]).
         # The cls group is padded to whole 256-row GEMM tiles (CP rows, NB of them used): a tile then holds either cls rows or patch
         # rows, never both, so which rows get the activation-rounding correction does not depend on the batch size.
-        grouped = use_tab
-        self.grouped = grouped
-        CP = (NB + 255) // 256 * 256 if grouped else 0
-        MT = CP + NB * T0 if grouped else NB * S          # rows of the token tensors
-
-        acc = eng.acc
-        m2 = 2 if acc else 1          # channel multiplier of (hi | lo) activations
-        np3 = 3 if acc else 1         # K passes of a GEMM whose weights AND activations are split
-        SP = 16 if acc else 0         # "split" flag (bit 4 of the dtype argument) of the pointwise producers
-        self.frames = torch.empty(B, H, W, 3, device=dev, dtype=torch.uint8)
-        patches = e16(NB * T0, 3 * c.patch * c.patch * m2)
-        x = torch.zeros(MT, Hd, device=dev, dtype=torch.float32)           # (padding rows of the grouped layout stay finite)
-        xn = z16(MT, Hd * m2)
+        self.grouped = grouped = self.use_tab
+        self.CP = CP = (NB + 255) // 256 * 256 if grouped else 0
+        self.MT = CP + NB * T0 if grouped else NB * S          # rows of the token tensors
+        self.TOK = ("tokens_grouped" if grouped else "tokens", NB, S, c.hidden, CP)
+        self.acc = acc = eng.acc
+        self.m2 = 2 if acc else 1          # channel multiplier of (hi | lo) activations
+        self.np3 = 3 if acc else 1         # K passes of a GEMM whose weights AND activations are split
+        # Neck activations are NHWC 16-bit; in accurate mode every tensor is a pair per pixel: (hi16 | hi8 | lo8) with the corrections on
+        # the FP8 MFMA (nf8: the whole neck, when every K is whole FP8 stages), or (hi | lo) 16-bit pairs with the product as three K segments.
+        self.nf8 = nf8 = eng.neck_f8
+        self.NSP = (32 if nf8 else 16) if acc else 0          # format flag of the pointwise producers whose output stays (hi16 | hi8 | lo8)
+        self.RZ = 1 | ((4 if nf8 else 2) if acc else 0)       # bs_resize_bilinear_nhwc flag: align_corners | pair format
         # split-precision attention (eng.attn_mode == "corr"): Q, K, V^T are allocated twice over, the rounding residuals behind the
         # values (bs_gemm_desc.qkv_lo_off -> bs_attention_table_corr).  Built for the table kernel's pipelined form (512-wide inputs,
         # even hp: 384x512 and 416x512); other geometries run the single-operand kernel.
-        corr = bool(eng.acc and eng.attn_mode == "corr" and use_tab and hp % 2 == 0)
-        self.attn_corr = corr
+        self.attn_corr = bool(acc and eng.attn_mode == "corr" and self.use_tab and hp % 2 == 0)
+
+        x = self._embed()
+        taps16 = self._backbone(x)
+        feats, fshape = self._reassemble(taps16)
+        # (the router and the seed regressors depend only on the bottleneck map; a side stream for them beside the fusion stage hid nothing --
+        # the launches fill the chip -- so they are plain launches in front of it and their intermediates are pooled like all others)
+        bins, emb = self._bins_seed(feats[3], *fshape[3])
+        fused, pj_low = self._fusion(feats, fshape)
+        last = self._relative_head(*fused[3])
+        levels = self._levels_fused if self._projector_level_fits(fused, pj_low) else self._levels_four
+        bins, Eh, ph_, pw_ = levels(fused, pj_low, bins, emb, *fshape[3])
+        self._depth(last, Eh, bins, ph_, pw_)
+
+    def e16(self, *s):
+        return self.pool.alloc(s, self.eng.dtype)
+
+    def e32(self, *s):
+        return self.pool.alloc(s, torch.float32)
+
+    # ---- operand-format policy: pure functions of the engine's modes and of the cls group (CP, grouped); nothing here launches
+    def fmt(self, *wkeys):
+        """producer format flag of an activation: 32 = (hi16 | hi8 | lo8) when every consumer GEMM runs its corrections on
+        the FP8 MFMA, 16 = (hi | lo) 16-bit pairs otherwise (accurate mode), 0 = single (fast mode, or every consumer is a
+        single-pass GEMM)."""
+        if not self.acc or all(k_ in self.eng.single_keys for k_ in wkeys):
+            return 0
+        return 32 if all(k_ in self.eng.f8s for k_ in wkeys) else 16
+
+    def am(self, wkey):
+        """row multiplier of the activation a backbone GEMM reads: 1 = single rows, 2 = pair rows"""
+        return 2 if self.fmt(wkey) else 1
+
+    def prow(self, wkey):
+        """dtype-argument bits of a producer whose consumer GEMM runs no FP8 stage on the patch rows ("wmean"): only the rows
+        below CP (the cls tile) need their FP8 planes.  bs_layernorm: rows << 8"""
+        return (self.CP << 8) if (self.acc and self.grouped and self.fmt(wkey) == 32 and self.eng.mode_of(wkey) in ("wmean", "wstat")) else 0
+
+    def mfmt(self):
+        """format code of a marked neck tensor (tests/test_zoedepth_gpu.py to_nchw): 2 = (hi16 | hi8 | lo8), 1 = (hi | lo)"""
+        return (2 if self.nf8 else 1) if self.acc else 0
+
+    def f8_scales(self, wkey, lo_plane=True):
+        """bs_gemm_desc.f8_scales of a product on wkey's FP8 planes: (A_hi8, W_lo8, A_lo8, W_hi8) exponents; lo_plane=False: both halves of
+        the segment are A_hi8 x W_lo8"""
+        sb0, sb1 = self.eng.f8s[wkey]
+        if not lo_plane:
+            return (127 - L.F8_ACT_HI_EXP, sb0, 127 - L.F8_ACT_HI_EXP, sb0)
+        return (127 - L.F8_ACT_HI_EXP, sb0, 127 - L.F8_ACT_LO_EXP, sb1)
+
+    def f8kw(self, wkey):
+        """correction arguments of a neck / head product under the current neck mode"""
+        return dict(f8_scales=self.f8_scales(wkey), f8_wonly_from=-1 if self.eng.neck_site_wonly(wkey) else 0,
+                    f8_skip_from=-1 if self.eng.neck_site_plain(wkey) else 0)
+
+    def okw(self, Cout, out_pairs, out8):
+        """output-format arguments of a neck GEMM writing Cout channels per row / pixel"""
+        if not (self.acc and out_pairs):
+            return dict(ldo=Cout, out_split_off=0)
+        return dict(ldo=Cout * self.m2, out_split_off=Cout, out_f8=self.F8O if (self.nf8 and out8) else None)
+
+    def lo8_rows(self, *consumer_wkeys):
+        """out_lo8_rows of a producer whose output is read only by the named products: 256 (the first tile alone writes the lo8 plane) when
+        every one of them runs the weight-rounding correction only -- nobody reads that plane then, the epilogue need not form it"""
+        return 256 if (self.acc and self.nf8 and all(k_ in self.eng.f8s and self.eng.neck_site_wonly(k_) for k_ in consumer_wkeys)) else 0
+
+    def hi8_rows(self, *consumer_wkeys):
+        """out_planes_rows of a producer whose output is read only by the named products: 256 (the first tile alone writes its planes) when every
+        one of them runs ONE 16-bit pass (the calibration's "plain" sites) -- nobody reads the hi8 plane either"""
+        return 256 if (self.acc and self.nf8 and all(k_ in self.eng.f8s and self.eng.neck_site_plain(k_) for k_ in consumer_wkeys)) else 0
+
+    # ---- emitters.  Their branch structure is the numerics of the product (DESIGN.md, Numerics)
+    def bgemm(self, name, A, wkey, out, M, N, K, **kw):
+        """backbone GEMM.  Accurate mode: A_hi W_hi + A_hi W_lo + A_lo W_hi in one launch -- the two corrections on the
+        block-scaled FP8 MFMA where the weight was packed for it (A = [hi16 | hi8 | lo8], 2 pass-equivalents), else as
+        K segments of 16-bit (hi | lo) pairs (3 passes)."""
+        eng, P, w, acc, grouped, CP, NB, T0 = self.eng, self.plan, self.w, self.acc, self.grouped, self.CP, self.NB, self.T0
+        f8s, mode = eng.f8s, eng.mode_of(wkey)
+
+        def f8gemm(f8_seg, scales, **f8):
+            P.gemm(name, A, w[wkey], out, M=M, N=N, K=K, lda=2 * K, f8_seg=f8_seg, f8_scales=scales, precision_passes=1, **f8, **kw)
+
+        if acc and grouped and wkey in f8s and wkey[0] == "l":
+            # (calibrate(): the channel means of the product's patch rows, what "wstat"'s static correction is formed from)
+            P.mark("in:" + wkey, A, ("chanmean", CP * 2 * K, NB * T0, 2 * K, K))
+        if acc and wkey in eng.single_keys:
+            P.gemm(name, A, w[wkey], out, M=M, N=N, K=K, lda=K, precision_passes=1, **kw)
+        elif acc and wkey in f8s and mode == "w":
+            # weight-rounding correction only: the FP8 segment is A_hi8 x W_lo8 (K bytes per row, both halves on the same scales)
+            f8gemm(K, self.f8_scales(wkey, lo_plane=False))
+        elif acc and wkey in f8s and mode == "wstat" and grouped and wkey in eng.backbone_bias_corr:
+            # "wmean" with the calibration frames' channel means in place of the image's own: the correction is a constant row, added to the
+            # patch rows through the bias2 path as ONE group (the cls tile runs both FP8 corrections and must not get it)
+            f8gemm(2 * K, self.f8_scales(wkey), f8_skip_from=CP, bias2=(eng.backbone_bias_corr[wkey], CP, NB * T0))
+        elif acc and wkey in f8s and mode in ("wmean", "wstat") and grouped:
+            # cls tile: both FP8 corrections.  Patch tiles: ONE 16-bit pass; the weight-rounding error A dW^T is replaced by its
+            # token-independent part 1 (mean_tokens(A) dW^T), a per-image bias formed by a column-mean kernel over a sample of
+            # the image's patch rows and bs_rank1_bias, a [NB, K] x [K, N] product (DESIGN.md, Numerics)
+            abar = self.pool.alloc((NB, K), torch.bfloat16)
+            b2 = self.e32(NB, N)
+            P.add(name + ".cm", "bs_col_mean", A, 2 * K, CP, T0, NB, self.MEAN_STEP, K, abar, b2, NB * N, L.dt(A))
+            P.add(name + ".r1", "bs_rank1_bias", abar, w[wkey + ".lo"], b2, NB, N, K)
+            f8gemm(2 * K, self.f8_scales(wkey), f8_skip_from=CP, bias2=(b2, CP, T0))
+            self.pool.free(abar, b2)
+        elif acc and wkey in f8s:
+            wonly = CP if (mode == "wcls" and grouped) else 0      # tiles past the cls group: weight correction only
+            f8gemm(2 * K, self.f8_scales(wkey), f8_wonly_from=wonly)
+        else:
+            P.gemm(name, A, w[wkey], out, M=M, N=N, K=K * self.np3, lda=K * self.m2, seg1=K if acc else 0, precision_passes=self.np3, **kw)
+
+    def nplain(self, name, A, wkey, out, M, N, K, shuffle=None, out_pairs=True, **kw):
+        """plain GEMM on pair operands; out_pairs=False leaves the output alone (fp32 or caller-specified)"""
+        eng, P, w, acc = self.eng, self.plan, self.w, self.acc
+        out8 = kw.pop("out8", True)
+        ok = self.okw(shuffle[1] if shuffle else N, out_pairs, out8)
+        if "ldo" in kw:
+            ok["ldo"] = kw.pop("ldo")
+        if "split_off" in kw:
+            ok["out_split_off"] = kw.pop("split_off")
+        if not out_pairs:
+            ok = dict(ldo=ok["ldo"], out_split_off=0)
+        if acc and wkey in eng.f8s:
+            self.site_flops[wkey] = self.site_flops.get(wkey, 0.0) + 2.0 * M * N * K      # (calibrate(): what a site's second product is worth)
+            lda_ = kw.pop("lda", 2 * K)
+            # (calibrate(): the channel means of this product's input, and the static bias correction they give while it runs one pass;
+            # a product with a per-group bias -- the readout's token half -- gets its correction through the product that forms that bias)
+            P.mark("in:" + wkey, A, ("chanmean", kw.get("a_offset", 0), M, lda_, K))
+            if not kw.get("bias_group_rows"):
+                kw["bias"] = eng.site_bias(wkey, kw.get("bias"))
+            P.gemm(name, A, w[wkey], out, M=M, N=N, K=K, lda=lda_, f8_seg=2 * K, shuffle=shuffle,
+                   precision_passes=1, **ok, **self.f8kw(wkey), **kw)
+        else:
+            ok.pop("out_f8", None)
+            P.gemm(name, A, w[wkey], out, M=M, N=N, K=K * self.np3, lda=kw.pop("lda", K * self.m2), seg1=K if acc else 0,
+                   shuffle=shuffle, precision_passes=self.np3, **ok, **kw)
+
+    def nconv(self, name, A, wkey, out, hh, ww, Ci, Co, stride=1, **kw):
+        """3x3 convolution (pad 1) on pair operands; returns the output's (height, width)"""
+        eng, P, w, acc, NB, m2, np3 = self.eng, self.plan, self.w, self.acc, self.NB, self.m2, self.np3
+        use8 = acc and wkey in eng.f8s
+        g_ = L.conv_geom(hh, ww, Ci if use8 else Ci * m2, 3, 3, stride, 1)
+        ho, wo = g_[3], g_[4]
+        has_res = "res" in kw
+        if use8:
+            self.site_flops[wkey] = self.site_flops.get(wkey, 0.0) + 2.0 * NB * ho * wo * Co * 9 * Ci
+            P.mark("in:" + wkey, A, ("chanmean", 0, NB * hh * ww, 2 * Ci, Ci))
+            kw["bias"] = eng.site_bias(wkey, kw.get("bias"))
+            P.gemm(name, A, w[wkey], out, M=NB * ho * wo, N=Co, K=9 * Ci, lda=2 * Ci, conv=g_, f8_seg=2 * Ci, ldo=2 * Co,
+                   ldr=2 * Co if has_res else 0, res_f8=has_res, out_split_off=Co, out_f8=self.F8O, precision_passes=1, **self.f8kw(wkey), **kw)
+        else:
+            if has_res and acc:
+                kw["res_split_off"] = Co
+            P.gemm(name, A, w[wkey], out, M=NB * ho * wo, N=Co, K=9 * Ci * np3, lda=Ci * m2, conv=g_, seg1=Ci if acc else 0,
+                   ldo=Co * m2, ldr=Co * m2 if has_res else 0, out_split_off=Co if acc else 0, precision_passes=np3, **kw)
+        return ho, wo
+
+    # ---- the stages, in the network's order
+    def _embed(self):
+        """Z1 + Z2: pre-processing fused with the patch gather, patch embedding, cls token -> the fp32 residual stream x [MT, hidden]"""
+        c, w, P, NB, T0, S, CP, dev = self.c, self.w, self.plan, self.NB, self.T0, self.S, self.CP, self.eng.dev
+        B, H, W, Hd = self.B, self.H, self.W, c.hidden
+        PK = 3 * c.patch * c.patch
+        self.frames = torch.empty(B, H, W, 3, device=dev, dtype=torch.uint8)
+        patches = self.e16(NB * T0, PK * self.m2)
+        x = torch.zeros(self.MT, Hd, device=dev, dtype=torch.float32)           # (padding rows of the grouped layout stay finite)
+        P.add("preprocess", "bs_preprocess_patches", self.frames, patches, B, H, W, self.nh, self.nw, int(self.flip), L.dt(patches) | self.fmt("pe.w"))
+        if self.grouped:
+            P.add("cls", "bs_fill_rows", x, w["cls"], NB, 1, Hd)                 # rows 0 .. NB-1
+            self.bgemm("patch_embed", patches, "pe.w", x, NB * T0, Hd, PK, bias=w["pe.b"], out_group=(NB * T0, 0, CP))   # rows CP ..
+        else:
+            P.add("cls", "bs_fill_rows", x, w["cls"], NB, S, Hd)
+            self.bgemm("patch_embed", patches, "pe.w", x, NB * T0, Hd, PK, bias=w["pe.b"], out_group=(T0, S, 1))
+        self.pool.free(patches)
+        P.mark("embed", x, self.TOK)
+        return x
+
+    def _backbone(self, x):
+        """Z3: the BEiT layers on the residual stream x; returns the tapped layers' outputs as 16-bit token tensors [MT, hidden * m2]"""
+        c, w, P, eng, NB, S, Sp, CP, MT, hp, wp = self.c, self.w, self.plan, self.eng, self.NB, self.S, self.Sp, self.CP, self.MT, self.hp, self.wp
+        acc, grouped, use_tab, corr, m2, Hd = self.acc, self.grouped, self.use_tab, self.attn_corr, self.m2, c.hidden
+        fmt, prow, bgemm = self.fmt, self.prow, self.bgemm
+        z16 = lambda *s: torch.zeros(*s, device=eng.dev, dtype=eng.dtype)
+        bias = eng._rel_table(hp, wp) if use_tab else eng._rel_bias(hp, wp, Sp)
+        xn = z16(MT, Hd * m2)
         QN = NB * c.heads * Sp * 64
         q, k, vt = z16((2 if corr else 1) * NB, c.heads, Sp, 64), z16((2 if corr else 1) * NB, c.heads, Sp, 64), z16((2 if corr else 1) * NB, c.heads, 64, Sp)
         ao = z16(MT, Hd * m2)
         hid = z16(MT, c.intermediate * m2)
-        def PE(C):
-            """elements between consecutive pixels / rows of a neck activation with C channels"""
-            return C * m2
-
-        taps16 = [z16(MT, PE(Hd)) for _ in c.taps]
-
-        f8s = eng.f8s
-
-        single = eng.single_keys
-
-        def fmt(*wkeys):
-            """producer format flag of an activation: 32 = (hi16 | hi8 | lo8) when every consumer GEMM runs its corrections on
-            the FP8 MFMA, 16 = (hi | lo) 16-bit pairs otherwise (accurate mode), 0 = single (fast mode, or every consumer is a
-            single-pass GEMM)."""
-            if not acc or all(k_ in single for k_ in wkeys):
-                return 0
-            return 32 if all(k_ in f8s for k_ in wkeys) else 16
-
-        def am(wkey):
-            """row multiplier of the activation a backbone GEMM reads: 1 = single rows, 2 = pair rows"""
-            return 2 if fmt(wkey) else 1
-
-        def prow(wkey):
-            """dtype-argument bits of a producer whose consumer GEMM runs no FP8 stage on the patch rows ("wmean"): only the rows
-            below CP (the cls tile) need their FP8 planes.  bs_layernorm: rows << 8"""
-            return (CP << 8) if (acc and grouped and fmt(wkey) == 32 and eng.mode_of(wkey) in ("wmean", "wstat")) else 0
-
-        MEAN_STEP = 8      # the rank-1 correction's token mean uses every 8th patch row (probe: same depth result as the full mean)
-
-        def bgemm(name, A, wkey, out, M, N, K, **kw):
-            """backbone GEMM.  Accurate mode: A_hi W_hi + A_hi W_lo + A_lo W_hi in one launch -- the two corrections on the
-            block-scaled FP8 MFMA where the weight was packed for it (A = [hi16 | hi8 | lo8], 2 pass-equivalents), else as
-            K segments of 16-bit (hi | lo) pairs (3 passes)."""
-            if acc and grouped and wkey in f8s and wkey[0] == "l":
-                # (calibrate(): the channel means of the product's patch rows, what "wstat"'s static correction is formed from)
-                P.mark("in:" + wkey, A, ("chanmean", CP * 2 * K, NB * T0, 2 * K, K))
-            if acc and wkey in single:
-                P.gemm(name, A, w[wkey], out, M=M, N=N, K=K, lda=K, precision_passes=1, **kw)
-            elif acc and wkey in f8s and eng.mode_of(wkey) == "w":
-                # weight-rounding correction only: the FP8 segment is A_hi8 x W_lo8 (K bytes per row, both halves on the same scales)
-                sb0, _ = f8s[wkey]
-                P.gemm(name, A, w[wkey], out, M=M, N=N, K=K, lda=2 * K, f8_seg=K,
-                       f8_scales=(127 - L.F8_ACT_HI_EXP, sb0, 127 - L.F8_ACT_HI_EXP, sb0), precision_passes=1, **kw)
-            elif acc and wkey in f8s and eng.mode_of(wkey) == "wstat" and grouped and wkey in eng.backbone_bias_corr:
-                # "wmean" with the calibration frames' channel means in place of the image's own: the correction is a constant row, added to the
-                # patch rows through the bias2 path as ONE group (the cls tile runs both FP8 corrections and must not get it)
-                sb0, sb1 = f8s[wkey]
-                P.gemm(name, A, w[wkey], out, M=M, N=N, K=K, lda=2 * K, f8_seg=2 * K, f8_skip_from=CP, bias2=(eng.backbone_bias_corr[wkey], CP, NB * T0),
-                       f8_scales=(127 - L.F8_ACT_HI_EXP, sb0, 127 - L.F8_ACT_LO_EXP, sb1), precision_passes=1, **kw)
-            elif acc and wkey in f8s and eng.mode_of(wkey) in ("wmean", "wstat") and grouped:
-                # cls tile: both FP8 corrections.  Patch tiles: ONE 16-bit pass; the weight-rounding error A dW^T is replaced by its
-                # token-independent part 1 (mean_tokens(A) dW^T), a per-image bias formed by a column-mean kernel over a sample of
-                # the image's patch rows and bs_rank1_bias, a [NB, K] x [K, N] product (DESIGN.md, Numerics)
-                sb0, sb1 = f8s[wkey]
-                abar = pool.alloc((NB, K), torch.bfloat16)
-                b2 = e32(NB, N)
-                P.add(name + ".cm", "bs_col_mean", A, 2 * K, CP, T0, NB, MEAN_STEP, K, abar, b2, NB * N, L.dt(A))
-                P.add(name + ".r1", "bs_rank1_bias", abar, w[wkey + ".lo"], b2, NB, N, K)
-                P.gemm(name, A, w[wkey], out, M=M, N=N, K=K, lda=2 * K, f8_seg=2 * K, f8_skip_from=CP, bias2=(b2, CP, T0),
-                       f8_scales=(127 - L.F8_ACT_HI_EXP, sb0, 127 - L.F8_ACT_LO_EXP, sb1), precision_passes=1, **kw)
-                free(abar, b2)
-            elif acc and wkey in f8s:
-                sb0, sb1 = f8s[wkey]
-                wonly = CP if (eng.mode_of(wkey) == "wcls" and grouped) else 0      # tiles past the cls group: weight correction only
-                P.gemm(name, A, w[wkey], out, M=M, N=N, K=K, lda=2 * K, f8_seg=2 * K, f8_wonly_from=wonly,
-                       f8_scales=(127 - L.F8_ACT_HI_EXP, sb0, 127 - L.F8_ACT_LO_EXP, sb1), precision_passes=1, **kw)
-            else:
-                P.gemm(name, A, w[wkey], out, M=M, N=N, K=K * np3, lda=K * m2, seg1=K if acc else 0, precision_passes=np3, **kw)
-
-        # ---- Z1 + Z2: pre-processing fused with the patch gather, patch embedding, cls token
-        PK = 3 * c.patch * c.patch
-        P.add("preprocess", "bs_preprocess_patches", self.frames, patches, B, H, W, nh_, nw_, int(flip), L.dt(patches) | fmt("pe.w"))
-        TOK = ("tokens_grouped" if grouped else "tokens", NB, S, Hd, CP)
-        if grouped:
-            P.add("cls", "bs_fill_rows", x, w["cls"], NB, 1, Hd)                 # rows 0 .. NB-1
-            bgemm("patch_embed", patches, "pe.w", x, NB * T0, Hd, PK, bias=w["pe.b"], out_group=(NB * T0, 0, CP))   # rows CP ..
-        else:
-            P.add("cls", "bs_fill_rows", x, w["cls"], NB, S, Hd)
-            bgemm("patch_embed", patches, "pe.w", x, NB * T0, Hd, PK, bias=w["pe.b"], out_group=(T0, S, 1))
-        free(patches)
-        P.mark("embed", x, TOK)
-        # ---- Z3: BEiT layers
+        taps16 = [z16(MT, Hd * m2) for _ in c.taps]
         ti = 0
         for l in range(c.layers):
             P.add(f"l{l}.ln1", "bs_layernorm", x, w[f"l{l}.ln1.g"], w[f"l{l}.ln1.b"], xn, None, MT, Hd, c.ln_eps,
@@ -989,132 +1081,54 @@ class _ZoePlan:
                   L.dt(xn) | fmt(f"l{l}.fc1.w") | prow(f"l{l}.fc1.w"))
             hfmt = fmt(f"l{l}.fc2.w")
             bgemm(f"l{l}.fc1", xn, f"l{l}.fc1.w", hid, MT, c.intermediate, Hd, bias=w[f"l{l}.fc1.b"], act=L.ACT_GELU,
-                  ldo=c.intermediate * am(f"l{l}.fc2.w"), out_split_off=c.intermediate if hfmt else 0,
-                  out_f8=(L.F8_ACT_HI_EXP, L.F8_ACT_LO_EXP) if hfmt == 32 else None,
+                  ldo=c.intermediate * self.am(f"l{l}.fc2.w"), out_split_off=c.intermediate if hfmt else 0,
+                  out_f8=self.F8O if hfmt == 32 else None,
                   # fc2 in "wcls" mode reads the lo8 plane of its cls tile only
                   out_lo8_rows=CP if (hfmt == 32 and grouped and eng.mode_of(f"l{l}.fc2.w") in ("wcls", "wmean", "wstat")) else 0,
                   out_planes_rows=CP if prow(f"l{l}.fc2.w") else 0)
             bgemm(f"l{l}.fc2", hid, f"l{l}.fc2.w", x, MT, Hd, c.intermediate, bias=w[f"l{l}.fc2.b"], scale=w[f"l{l}.lam2"], res=x, ldr=Hd)
-            P.mark(f"layer{l + 1}", x, TOK)
+            P.mark(f"layer{l + 1}", x, self.TOK)
             if (l + 1) in c.taps:
                 if acc:
                     P.add(f"tap{ti}", "bs_cast_split", x, taps16[ti], MT, Hd, L.dt(xn) | (32 if eng.neck_f8 else 0))
                 else:
                     P.add(f"tap{ti}", "bs_cast", x, taps16[ti], x.numel(), L.dt(xn))
                 ti += 1
+        return taps16
 
-        # ---- neck helpers.  Activations are NHWC 16-bit; in accurate mode every tensor is a pair per pixel:
-        # (hi16 | hi8 | lo8) with them on the FP8 MFMA (nf8: the whole neck, when every K is whole FP8 stages), or (hi | lo) 16-bit
-        # pairs with the product as three K segments.
-        nf8 = eng.neck_f8
-        NSP = (32 if nf8 else 16) if acc else 0          # format flag of the pointwise producers whose output stays (hi16 | hi8 | lo8)
-        RZ = 1 | ((4 if nf8 else 2) if acc else 0)       # bs_resize_bilinear_nhwc flag: align_corners | pair format
-        F8O = (L.F8_ACT_HI_EXP, L.F8_ACT_LO_EXP)
-
-        def mfmt(C):
-            """format code of a marked neck tensor (tests/test_zoedepth_gpu.py to_nchw): 2 = (hi16 | hi8 | lo8), 1 = (hi | lo)"""
-            return (2 if nf8 else 1) if acc else 0
-
-        def f8kw(wkey):
-            sb0, sb1 = f8s[wkey]
-            wonly = eng.neck_site_wonly(wkey)
-            return dict(f8_scales=(127 - L.F8_ACT_HI_EXP, sb0, 127 - L.F8_ACT_LO_EXP, sb1), f8_wonly_from=-1 if wonly else 0,
-                        f8_skip_from=-1 if eng.neck_site_plain(wkey) else 0)
-
-        def okw(Cout, out_pairs, out8):
-            """output-format arguments of a neck GEMM writing Cout channels per row / pixel"""
-            if not (acc and out_pairs):
-                return dict(ldo=Cout, out_split_off=0)
-            return dict(ldo=Cout * m2, out_split_off=Cout, out_f8=F8O if (nf8 and out8) else None)
-
-        def nplain(name, A, wkey, out, M, N, K, shuffle=None, out_pairs=True, **kw):
-            """plain GEMM on pair operands; out_pairs=False leaves the output alone (fp32 or caller-specified)"""
-            out8 = kw.pop("out8", True)
-            ok = okw(shuffle[1] if shuffle else N, out_pairs, out8)
-            if "ldo" in kw:
-                ok["ldo"] = kw.pop("ldo")
-            if "split_off" in kw:
-                ok["out_split_off"] = kw.pop("split_off")
-            if not out_pairs:
-                ok = dict(ldo=ok["ldo"], out_split_off=0)
-            if acc and wkey in f8s:
-                self.site_flops[wkey] = self.site_flops.get(wkey, 0.0) + 2.0 * M * N * K      # (calibrate(): what a site's second product is worth)
-                lda_ = kw.pop("lda", 2 * K)
-                # (calibrate(): the channel means of this product's input, and the static bias correction they give while it runs one pass;
-                # a product with a per-group bias -- the readout's token half -- gets its correction through the product that forms that bias)
-                P.mark("in:" + wkey, A, ("chanmean", kw.get("a_offset", 0), M, lda_, K))
-                if not kw.get("bias_group_rows"):
-                    kw["bias"] = eng.site_bias(wkey, kw.get("bias"))
-                P.gemm(name, A, w[wkey], out, M=M, N=N, K=K, lda=lda_, f8_seg=2 * K, shuffle=shuffle,
-                       precision_passes=1, **ok, **f8kw(wkey), **kw)
-            else:
-                ok.pop("out_f8", None)
-                P.gemm(name, A, w[wkey], out, M=M, N=N, K=K * np3, lda=kw.pop("lda", K * m2), seg1=K if acc else 0,
-                       shuffle=shuffle, precision_passes=np3, **ok, **kw)
-
-        def lo8_rows(*consumer_wkeys):
-            """out_lo8_rows of a producer whose output is read only by the named products: 256 (the first tile alone writes the lo8 plane) when
-            every one of them runs the weight-rounding correction only -- nobody reads that plane then, the epilogue need not form it"""
-            return 256 if (acc and nf8 and all(k_ in f8s and eng.neck_site_wonly(k_) for k_ in consumer_wkeys)) else 0
-
-        def hi8_rows(*consumer_wkeys):
-            """out_planes_rows of a producer whose output is read only by the named products: 256 (the first tile alone writes its planes) when every
-            one of them runs ONE 16-bit pass (the calibration's "plain" sites) -- nobody reads the hi8 plane either"""
-            return 256 if (acc and nf8 and all(k_ in f8s and eng.neck_site_plain(k_) for k_ in consumer_wkeys)) else 0
-
-        def nconv(name, A, wkey, out, hh, ww, Ci, Co, stride=1, **kw):
-            use8 = acc and wkey in f8s
-            g_ = L.conv_geom(hh, ww, Ci if use8 else Ci * m2, 3, 3, stride, 1)
-            ho, wo = g_[3], g_[4]
-            has_res = "res" in kw
-            out_relu = kw.pop("out_relu", None)
-            assert out_relu is None or use8
-            if use8:
-                if out_relu is not None:
-                    kw["out_relu"] = out_relu
-                self.site_flops[wkey] = self.site_flops.get(wkey, 0.0) + 2.0 * NB * ho * wo * Co * 9 * Ci
-                P.mark("in:" + wkey, A, ("chanmean", 0, NB * hh * ww, 2 * Ci, Ci))
-                kw["bias"] = eng.site_bias(wkey, kw.get("bias"))
-                P.gemm(name, A, w[wkey], out, M=NB * ho * wo, N=Co, K=9 * Ci, lda=2 * Ci, conv=g_, f8_seg=2 * Ci, ldo=2 * Co,
-                       ldr=2 * Co if has_res else 0, res_f8=has_res, out_split_off=Co, out_f8=F8O, precision_passes=1, **f8kw(wkey), **kw)
-            else:
-                if has_res and acc:
-                    kw["res_split_off"] = Co
-                P.gemm(name, A, w[wkey], out, M=NB * ho * wo, N=Co, K=9 * Ci * np3, lda=Ci * m2, conv=g_, seg1=Ci if acc else 0,
-                       ldo=Co * m2, ldr=Co * m2 if has_res else 0, out_split_off=Co if acc else 0, precision_passes=np3, **kw)
-            return ho, wo
-
-        # ---- Z4: reassemble (readout project, 1x1 projection, resize) + neck 3x3 convs
-        feats, fshape, feats_relu = [], [], []
-        # (bs_gemm_desc.out2_relu, see the residual units below: measured a wash -- the seven bs_relu_split launches cost 1.55 ms per step, the second
-        # output adds 1.1-1.8 ms to the producing convolutions' epilogues, profiles/r05_plan_call_times.txt -- and left off; BS_RELU_OUT=1 turns it on)
-        relu_out = bool(acc and nf8 and os.environ.get("BS_RELU_OUT", "0") == "1")
-        cb = e32(NB, Hd)
-        r16 = e16(NB * T0, PE(Hd))
+    def _reassemble(self, taps16):
+        """Z4: reassemble (readout project, 1x1 projection, resize) + neck 3x3 convs; returns the four feature maps [NB, fh, fw, fusion * m2],
+        finest first, and their (fh, fw)"""
+        c, w, P, eng, NB, T0, S, CP, hp, wp = self.c, self.w, self.plan, self.eng, self.NB, self.T0, self.S, self.CP, self.hp, self.wp
+        acc, grouped, m2, np3, nf8, Hd = self.acc, self.grouped, self.m2, self.np3, self.nf8, c.hidden
+        e16, free, nplain, nconv = self.e16, self.pool.free, self.nplain, self.nconv
+        feats, fshape = [], []
+        cb = self.e32(NB, Hd)
+        r16 = e16(NB * T0, Hd * m2)
         for i, ch in enumerate(c.neck_hidden):
             t16 = taps16[i]
             # cls half of the readout: per-image bias vector  c_b = cls_b @ W_cls^T + b   (A rows = the cls row of every image)
             # (its bias also carries the token half's static correction while that product runs one pass: c_b is added to every token row)
-            nplain(f"ro{i}.cls", t16, f"ro{i}.w_cls", cb, NB, Hd, Hd, out_pairs=False, lda=(1 if grouped else S) * PE(Hd),
+            nplain(f"ro{i}.cls", t16, f"ro{i}.w_cls", cb, NB, Hd, Hd, out_pairs=False, lda=(1 if grouped else S) * Hd * m2,
                    bias=eng.site_bias(f"ro{i}.w_tok", w[f"ro{i}.b"]))
             # token half: the patch rows of every image, + c_b, GELU.  Grouped rows: a plain GEMM over rows NB..; image-major rows:
-            # rows 1..S-1 of every image (a 1-row "conv" with a -1 column crop)
+            # rows 1..S-1 of every image (a 1-row "conv" with a -1 column crop; unlike nplain it records no site_flops and no "in:" mark)
             if grouped:
-                nplain(f"ro{i}.tok", t16, f"ro{i}.w_tok", r16, NB * T0, Hd, Hd, a_offset=CP * PE(Hd), bias=cb, bias_group_rows=T0,
+                nplain(f"ro{i}.tok", t16, f"ro{i}.w_tok", r16, NB * T0, Hd, Hd, a_offset=CP * Hd * m2, bias=cb, bias_group_rows=T0,
                        act=L.ACT_GELU)
-            elif acc and f"ro{i}.w_tok" in f8s:
+            elif acc and f"ro{i}.w_tok" in eng.f8s:
                 P.gemm(f"ro{i}.tok", t16, w[f"ro{i}.w_tok"], r16, M=NB * T0, N=Hd, K=Hd, lda=2 * Hd, conv=(1, S, Hd, 1, T0, 1, 1, 1, 0, -1),
-                       f8_seg=2 * Hd, bias=cb, bias_group_rows=T0, act=L.ACT_GELU, ldo=2 * Hd, out_split_off=Hd, out_f8=F8O if nf8 else None,
-                       precision_passes=1, **f8kw(f"ro{i}.w_tok"))
+                       f8_seg=2 * Hd, bias=cb, bias_group_rows=T0, act=L.ACT_GELU, ldo=2 * Hd, out_split_off=Hd, out_f8=self.F8O if nf8 else None,
+                       precision_passes=1, **self.f8kw(f"ro{i}.w_tok"))
             else:
                 P.gemm(f"ro{i}.tok", t16, w[f"ro{i}.w_tok"], r16, M=NB * T0, N=Hd, K=Hd * np3, lda=Hd * m2, conv=(1, S, Hd * m2, 1, T0, 1, 1, 1, 0, -1),
                        seg1=Hd if acc else 0, bias=cb, bias_group_rows=T0, act=L.ACT_GELU, ldo=Hd * m2, out_split_off=Hd if acc else 0,
                        precision_passes=np3)
-            pr = e16(NB * T0, PE(ch))
+            pr = e16(NB * T0, ch * m2)
             nplain(f"ra{i}.proj", r16, f"ra{i}.proj.w", pr, NB * T0, ch, Hd, bias=w[f"ra{i}.proj.b"])
             if i == 0 or i == 1:
                 s_ = 4 if i == 0 else 2
-                up = e16(NB, hp * s_, wp * s_, PE(ch))
+                up = e16(NB, hp * s_, wp * s_, ch * m2)
                 nplain(f"ra{i}.up", pr, f"ra{i}.up.w", up, NB * T0, s_ * s_ * ch, ch, shuffle=(s_, ch, hp, wp), bias=w[f"ra{i}.up.b"])
                 free(pr)
                 fh, fw, src = hp * s_, wp * s_, up
@@ -1122,310 +1136,324 @@ class _ZoePlan:
                 fh, fw, src = hp, wp, pr
             else:
                 fh, fw = (hp + 2 - 3) // 2 + 1, (wp + 2 - 3) // 2 + 1
-                src = e16(NB, fh, fw, PE(ch))
+                src = e16(NB, fh, fw, ch * m2)
                 nconv(f"ra{i}.down", pr, f"ra{i}.down.w", src, hp, wp, ch, ch, stride=2, bias=w[f"ra{i}.down.b"])
                 free(pr)
-            P.mark(f"reassemble{i}", src, ("nhwc", NB, fh, fw, ch, mfmt(ch)))
-            f16_ = e16(NB, fh, fw, PE(c.fusion))
-            # Round 5: the fusion stage's residual units read x (the skip) AND relu(x) (their first convolution's input): the producing
-            # convolution's epilogue can write both (bs_gemm_desc.out2_relu) instead of a bs_relu_split launch re-reading x (off by default, see relu_out).
-            fr_ = e16(NB, fh, fw, PE(c.fusion)) if relu_out else None
-            nconv(f"nc{i}", src, f"nc{i}.w", f16_, fh, fw, ch, c.fusion, out_relu=fr_)
-            feats_relu.append(fr_)
+            P.mark(f"reassemble{i}", src, ("nhwc", NB, fh, fw, ch, self.mfmt()))
+            f16_ = e16(NB, fh, fw, c.fusion * m2)
+            nconv(f"nc{i}", src, f"nc{i}.w", f16_, fh, fw, ch, c.fusion)
             free(src)                                                  # (level 2: src is pr)
-            P.mark(f"neckconv{i}", f16_, ("nhwc", NB, fh, fw, c.fusion, mfmt(c.fusion)))
+            P.mark(f"neckconv{i}", f16_, ("nhwc", NB, fh, fw, c.fusion, self.mfmt()))
             feats.append(f16_)
             fshape.append((fh, fw))
         free(r16, cb)
-        bott, (bh_, bw_) = feats[3], fshape[3]
-        # The router and the seed regressors depend only on the bottleneck map.  Rounds 2-4 issued them on a side stream beside the fusion stage;
-        # measured in round 5 (bench, alternating runs: 413.0 / 411.9 frames/s with the side lane, 413.1 / 406.0 without) that lane hides nothing
-        # that can be seen -- the launches fill the chip -- and it is gone: one lane, and these intermediates are pooled like all others.
-        # ---- Z7: metric-bins head
+        return feats, fshape
+
+    def _bins_seed(self, bott, bh_, bw_):
+        """Z7, first half: the metric head's conv2 on the bottleneck map, the router, the seed bins and the seed projector; returns the
+        seed bins fp32 [NB, bh, bw, 2 * n_bins] and the seed embedding [NB * bh * bw, bin_dim * m2]"""
+        c, w, P, NB, acc, m2, np3, dev = self.c, self.w, self.plan, self.NB, self.acc, self.m2, self.np3, self.eng.dev
+        e16, e32 = self.e16, self.e32
         Mb = NB * bh_ * bw_
         xb = e16(Mb, c.bottleneck * m2)                                   # (hi | lo) pairs in accurate mode
-        nplain("mh.conv2", bott, "mh.conv2.w", xb, Mb, c.bottleneck, c.bottleneck, bias=w["mh.conv2.b"], out8=False)
+        self.nplain("mh.conv2", bott, "mh.conv2.w", xb, Mb, c.bottleneck, c.bottleneck, bias=w["mh.conv2.b"], out8=False)
         self.logits = torch.empty(NB, 4, device=dev, dtype=torch.float32)      # (a plan output: not pooled)
         self.route = torch.zeros(NB, dtype=torch.int32, device=dev)       # single-head models: every image stays on slot 0
         if not c.single_head:
-            # router: 4-layer post-norm transformer over (1 + bh*bw) tokens, classifier on token 0
-            D, St = c.pt_hidden, bh_ * bw_ + 1
-            pos = torch.arange(0, St, dtype=torch.float32).unsqueeze(1)
-            div = torch.exp(torch.arange(0, D, 2, dtype=torch.float32).unsqueeze(0) * (-torch.log(torch.full((), 10000.0)) / D))
-            pe_tab = torch.cat([torch.sin(pos * div), torch.cos(pos * div)], dim=1).to(dev)          # [St, D]
-            self._pe_src = pe_tab.unsqueeze(0).expand(NB, St, D).contiguous().view(NB * St, D)
-            e32b = e32(NB * St, D)
-            e16b = e16(NB * St, D)
-            self._router_init = (e32b, self._pe_src)
-            # e = pos_enc (token 0 is the zero "cls" pad) ; tokens 1.. += embedding conv
-            P.add("rt.init", "bs_copy_f32", self._pe_src, e32b, e32b.numel())
-            P.gemm("rt.emb", xb, w["rt.emb.w"], e32b, M=Mb, N=D, K=c.bottleneck, lda=c.bottleneck * m2, bias=w["rt.emb.b"], res=e32b, ldr=D,
-                   out_group=(bh_ * bw_, St, 1))
-            P.add("rt.cast", "bs_cast", e32b, e16b, e32b.numel(), L.dt(e16b))
-            qkv32 = e32(NB * St, 3 * D)
-            at16 = e16(NB * St, D)
-            tmp32 = e32(NB * St, D)
-            h16 = e16(NB * St, c.pt_inter)
-            for l in range(c.pt_layers):
-                P.gemm(f"rt{l}.qkv", e16b, w[f"rt{l}.qkv.w"], qkv32, M=NB * St, N=3 * D, K=D, lda=D, bias=w[f"rt{l}.qkv.b"])
-                P.add(f"rt{l}.attn", "bs_small_attention", qkv32, at16, NB, St, c.pt_heads, L.dt(at16))
-                P.gemm(f"rt{l}.o", at16, w[f"rt{l}.o.w"], tmp32, M=NB * St, N=D, K=D, lda=D, bias=w[f"rt{l}.o.b"], res=e32b, ldr=D)
-                P.add(f"rt{l}.n1", "bs_layernorm", tmp32, w[f"rt{l}.n1.g"], w[f"rt{l}.n1.b"], e16b, e32b, NB * St, D, 1e-5, L.dt(e16b))
-                P.gemm(f"rt{l}.l1", e16b, w[f"rt{l}.l1.w"], h16, M=NB * St, N=c.pt_inter, K=D, lda=D, bias=w[f"rt{l}.l1.b"], act=L.ACT_RELU)
-                P.gemm(f"rt{l}.l2", h16, w[f"rt{l}.l2.w"], tmp32, M=NB * St, N=D, K=c.pt_inter, lda=c.pt_inter, bias=w[f"rt{l}.l2.b"], res=e32b, ldr=D)
-                P.add(f"rt{l}.n2", "bs_layernorm", tmp32, w[f"rt{l}.n2.g"], w[f"rt{l}.n2.b"], e16b, e32b, NB * St, D, 1e-5, L.dt(e16b))
-            c1 = e16(NB, D)
-            P.gemm("cl.l1", e16b, w["cl.l1.w"], c1, M=NB, N=D, K=D, lda=St * D, bias=w["cl.l1.b"], act=L.ACT_RELU)
-            P.gemm("cl.l2", c1, w["cl.l2.w"], self.logits, M=NB, N=4, K=D, lda=D, bias=w["cl.l2.b"])
-            P.add("route", "bs_route_argmax", self.logits, 4, self.route, NB)
-            P.mark("logits", self.logits, ("raw",))
+            self._router(xb, bh_, bw_)
         # seeds + seed projector
-        E, nb = c.bin_dim, c.n_bins
-        SM, PM, HID = c.seed_mlp, c.proj_mlp, c.clb_hidden          # hidden widths: 64 / 64 / 40 (NK head), 256 / 128 / 80 (single head)
-        KB = c.bottleneck
+        E, nb, SM, PM, KB = c.bin_dim, c.n_bins, c.seed_mlp, c.proj_mlp, c.bottleneck      # hidden widths: 64 / 64 (NK head), 256 / 128 (single head)
         sh = e16(Mb, 2 * SM * m2)                                  # [seed regressor slot 0 | slot 1] hidden units, pairs in accurate mode
         P.gemm("seed.c1", xb, w["seed.c1.w"], sh, M=Mb, N=2 * SM, K=KB * np3, lda=KB * m2, seg1=KB if acc else 0, bias=w["seed.c1.b"], act=L.ACT_RELU,
                ldo=2 * SM * m2, out_split_off=2 * SM if acc else 0, precision_passes=np3)
-        bins_prev = e32(NB, bh_, bw_, 2 * nb)
-        P.gemm("seed.c2", sh, w["seed.c2.w"], bins_prev, M=Mb, N=2 * nb, K=2 * SM * np3, lda=2 * SM * m2, seg1=2 * SM if acc else 0, bias=w["seed.c2.b"],
+        bins = e32(NB, bh_, bw_, 2 * nb)
+        P.gemm("seed.c2", sh, w["seed.c2.w"], bins, M=Mb, N=2 * nb, K=2 * SM * np3, lda=2 * SM * m2, seg1=2 * SM if acc else 0, bias=w["seed.c2.b"],
                act=L.ACT_SOFTPLUS, precision_passes=np3)
         # seed projector: its own small GEMM pair (1.3e-6 m as single products: stays single); the projector embeddings feed the last
         # 1x1 convs of the head almost directly, so accurate mode keeps them as (hi | lo) pairs
         shp = e16(Mb, PM)
         P.gemm("seedproj.c1", xb, w["seedproj.c1.w"], shp, M=Mb, N=PM, K=KB, lda=KB * m2, bias=w["seedproj.c1.b"], act=L.ACT_RELU)
-        emb_prev = e16(Mb, E * m2)
-        P.gemm("seedproj.c2", shp, w["seedproj.c2.w"], emb_prev, M=Mb, N=E, K=PM, lda=PM, bias=w["seedproj.c2.b"],
+        emb = e16(Mb, E * m2)
+        P.gemm("seedproj.c2", shp, w["seedproj.c2.w"], emb, M=Mb, N=E, K=PM, lda=PM, bias=w["seedproj.c2.b"],
                ldo=E * m2, out_split_off=E if acc else 0)
-        # ---- Z5: fusion stage (pre-activation residual units, x2 bilinear, 1x1 projection)
-        Fc = c.fusion
+        return bins, emb
 
-        def res_unit(name, xin, hh, ww, other=None, xin_relu=None, want_relu=False):
-            """y = conv2(relu(conv1(relu(x)))) + x (+ other).  xin_relu: relu(x) as its producer wrote it (else a bs_relu_split launch forms it);
-            want_relu: also return relu(y), written by conv2's epilogue, for the next unit."""
-            t = e16(NB, hh, ww, PE(Fc))
-            y = e16(NB, hh, ww, PE(Fc))
-            yr = e16(NB, hh, ww, PE(Fc)) if (want_relu and relu_out) else None
-            if acc:
-                xr = xin_relu
-                if xr is None:
-                    xr = e16(NB, hh, ww, PE(Fc))
-                    # (bit 6: no lo8 plane when the first convolution, the only reader, is weight-only)
-                    P.add(name + ".relu", "bs_relu_split", xin, xr, NB * hh * ww, Fc, L.dt(xr) | (32 if nf8 else 0) | (64 if lo8_rows(name + ".c1.w") else 0) | (128 if hi8_rows(name + ".c1.w") else 0))
-                nconv(name + ".c1", xr, name + ".c1.w", t, hh, ww, Fc, Fc, bias=w[name + ".c1.b"], act=L.ACT_RELU, out_lo8_rows=lo8_rows(name + ".c2.w"),
-                      out_planes_rows=hi8_rows(name + ".c2.w"))
-                free(xr)
-            else:
-                nconv(name + ".c1", xin, name + ".c1.w", t, hh, ww, Fc, Fc, relu_a=True, bias=w[name + ".c1.b"], act=L.ACT_RELU)
-            nconv(name + ".c2", t, name + ".c2.w", y, hh, ww, Fc, Fc, bias=w[name + ".c2.b"], res=xin, res2=other, out_relu=yr)
-            free(t)
-            return y, yr
+    def _router(self, xb, bh_, bw_):
+        """the router of the two-head model: a 4-layer post-norm transformer over (1 + bh*bw) tokens, classifier on token 0 -> self.logits, self.route"""
+        c, w, P, NB, e16, e32 = self.c, self.w, self.plan, self.NB, self.e16, self.e32
+        D, St, Mb = c.pt_hidden, bh_ * bw_ + 1, NB * bh_ * bw_
+        pos = torch.arange(0, St, dtype=torch.float32).unsqueeze(1)
+        div = torch.exp(torch.arange(0, D, 2, dtype=torch.float32).unsqueeze(0) * (-torch.log(torch.full((), 10000.0)) / D))
+        pe_tab = torch.cat([torch.sin(pos * div), torch.cos(pos * div)], dim=1).to(self.eng.dev)          # [St, D]
+        pe_src = pe_tab.unsqueeze(0).expand(NB, St, D).contiguous().view(NB * St, D)
+        e32b = e32(NB * St, D)
+        e16b = e16(NB * St, D)
+        # e = pos_enc (token 0 is the zero "cls" pad) ; tokens 1.. += embedding conv
+        P.add("rt.init", "bs_copy_f32", pe_src, e32b, e32b.numel())
+        P.gemm("rt.emb", xb, w["rt.emb.w"], e32b, M=Mb, N=D, K=c.bottleneck, lda=c.bottleneck * self.m2, bias=w["rt.emb.b"], res=e32b, ldr=D,
+               out_group=(bh_ * bw_, St, 1))
+        P.add("rt.cast", "bs_cast", e32b, e16b, e32b.numel(), L.dt(e16b))
+        qkv32 = e32(NB * St, 3 * D)
+        at16 = e16(NB * St, D)
+        tmp32 = e32(NB * St, D)
+        h16 = e16(NB * St, c.pt_inter)
+        for l in range(c.pt_layers):
+            P.gemm(f"rt{l}.qkv", e16b, w[f"rt{l}.qkv.w"], qkv32, M=NB * St, N=3 * D, K=D, lda=D, bias=w[f"rt{l}.qkv.b"])
+            P.add(f"rt{l}.attn", "bs_small_attention", qkv32, at16, NB, St, c.pt_heads, L.dt(at16))
+            P.gemm(f"rt{l}.o", at16, w[f"rt{l}.o.w"], tmp32, M=NB * St, N=D, K=D, lda=D, bias=w[f"rt{l}.o.b"], res=e32b, ldr=D)
+            P.add(f"rt{l}.n1", "bs_layernorm", tmp32, w[f"rt{l}.n1.g"], w[f"rt{l}.n1.b"], e16b, e32b, NB * St, D, 1e-5, L.dt(e16b))
+            P.gemm(f"rt{l}.l1", e16b, w[f"rt{l}.l1.w"], h16, M=NB * St, N=c.pt_inter, K=D, lda=D, bias=w[f"rt{l}.l1.b"], act=L.ACT_RELU)
+            P.gemm(f"rt{l}.l2", h16, w[f"rt{l}.l2.w"], tmp32, M=NB * St, N=D, K=c.pt_inter, lda=c.pt_inter, bias=w[f"rt{l}.l2.b"], res=e32b, ldr=D)
+            P.add(f"rt{l}.n2", "bs_layernorm", tmp32, w[f"rt{l}.n2.g"], w[f"rt{l}.n2.b"], e16b, e32b, NB * St, D, 1e-5, L.dt(e16b))
+        c1 = e16(NB, D)
+        P.gemm("cl.l1", e16b, w["cl.l1.w"], c1, M=NB, N=D, K=D, lda=St * D, bias=w["cl.l1.b"], act=L.ACT_RELU)
+        P.gemm("cl.l2", c1, w["cl.l2.w"], self.logits, M=NB, N=4, K=D, lda=D, bias=w["cl.l2.b"])
+        P.add("route", "bs_route_argmax", self.logits, 4, self.route, NB)
+        P.mark("logits", self.logits, ("raw",))
 
-        # Round 5: the bins head's projectors (pj{i}.c1: 1x1 conv 256 -> 64 + ReLU on the fused maps, HF modeling_zoedepth.py:749-772) read an
-        # UPSAMPLED map too: their convolution runs on the low-resolution projection output (a quarter of the pixels; the product is kept as
-        # (hi | lo) pairs) and bs_resize_bias_relu_nhwc upsamples it, adds the bias and applies the ReLU where the level needs it -- instead of
-        # reading the 256-channel fused map at full resolution (pj3.c1: 6.4 GB in for 1.6 GB out, 1.36 ms).  BS_PJ_LOWRES=0: the direct form.
-        pj_lowres = os.environ.get("BS_PJ_LOWRES", "1") != "0"
-        pj_low = []
-        fused_list = []
+    def res_unit(self, name, xin, hh, ww, other=None):
+        """y = conv2(relu(conv1(relu(x)))) + x (+ other).  relu(x) comes from a bs_relu_split launch: writing it from the producing convolution's
+        epilogue instead (bs_gemm_desc.out2_relu) was measured a wash -- the seven launches cost 1.55 ms per step, the second output adds 1.1-1.8 ms
+        to the producers' epilogues (profiles/r05_plan_call_times.txt)."""
+        w, P, NB, Fc, nf8, e16, free, nconv = self.w, self.plan, self.NB, self.c.fusion, self.nf8, self.e16, self.pool.free, self.nconv
+        t = e16(NB, hh, ww, Fc * self.m2)
+        y = e16(NB, hh, ww, Fc * self.m2)
+        if self.acc:
+            xr = e16(NB, hh, ww, Fc * self.m2)
+            # (bit 6: no lo8 plane when the first convolution, the only reader, is weight-only)
+            P.add(name + ".relu", "bs_relu_split", xin, xr, NB * hh * ww, Fc, L.dt(xr) | (32 if nf8 else 0) | (64 if self.lo8_rows(name + ".c1.w") else 0) | (128 if self.hi8_rows(name + ".c1.w") else 0))
+            nconv(name + ".c1", xr, name + ".c1.w", t, hh, ww, Fc, Fc, bias=w[name + ".c1.b"], act=L.ACT_RELU, out_lo8_rows=self.lo8_rows(name + ".c2.w"),
+                  out_planes_rows=self.hi8_rows(name + ".c2.w"))
+            free(xr)
+        else:
+            nconv(name + ".c1", xin, name + ".c1.w", t, hh, ww, Fc, Fc, relu_a=True, bias=w[name + ".c1.b"], act=L.ACT_RELU)
+        nconv(name + ".c2", t, name + ".c2.w", y, hh, ww, Fc, Fc, bias=w[name + ".c2.b"], res=xin, res2=other)
+        free(t)
+        return y
+
+    def _fusion(self, feats, fshape):
+        """Z5: fusion stage (pre-activation residual units, x2 bilinear, 1x1 projection), coarsest level first.  Returns per level the fused
+        map (tensor, height, width) -- read after this stage for its shape and, at level 3, by the relative head -- and the low-resolution
+        input of the bins head's projector (z, height, width)."""
+        w, P, eng, NB, m2, Fc, PM = self.w, self.plan, self.eng, self.NB, self.m2, self.c.fusion, self.c.proj_mlp
+        e16, free, nplain = self.e16, self.pool.free, self.nplain
+        rh_in = "rh.projection.w" if eng.add_projection else "rh.conv1.w"
+        pj_low, fused_list = [], []
         fused = None
         for li in range(4):
             feat = feats[3 - li]
             fh, fw = fshape[3 - li]
             if fused is None:
-                cur, cur_relu = feat, feats_relu[3 - li]                    # (the bottleneck map)
-                own = False
+                cur = feat                                              # (the bottleneck map)
             else:
-                cur, cur_relu = res_unit(f"fu{li}.r1", feat, fh, fw, other=fused, xin_relu=feats_relu[3 - li], want_relu=True)     # fused + residual_layer1(feat)
+                cur = self.res_unit(f"fu{li}.r1", feat, fh, fw, other=fused)     # fused + residual_layer1(feat)
                 free(feat)
-                if pj_lowres:
-                    free(fused)                                             # (its projector input was taken at the low resolution)
-                own = True
+                free(fused)                                             # (its projector input was taken at the low resolution)
             cur_in = cur
-            cur, _ = res_unit(f"fu{li}.r2", cur, fh, fw, xin_relu=cur_relu)
-            if own:
+            cur = self.res_unit(f"fu{li}.r2", cur, fh, fw)
+            if fused is not None:
                 free(cur_in)
             # HF upsamples, then applies the 1x1 projection (modeling_zoedepth.py:316-322).  Both are linear and the bilinear weights
             # sum to 1, so projection(interpolate(x)) = interpolate(projection(x)) exactly in real arithmetic: the projection runs at
             # the LOW resolution (a quarter of the FLOPs and of the bytes), the resize writes the fused map directly.
-            lowp = e16(NB, fh, fw, PE(Fc))
+            lowp = e16(NB, fh, fw, Fc * m2)
             nplain(f"fu{li}.proj", cur, f"fu{li}.proj.w", lowp, NB * fh * fw, Fc, Fc, bias=w[f"fu{li}.proj.b"])
             free(cur)
-            if pj_lowres:
-                z = e16(NB * fh * fw, PM * m2)
-                nplain(f"pj{li}.c1", lowp, f"pj{li}.c1.w", z, NB * fh * fw, PM, Fc, out8=False)
-                pj_low.append((z, fh, fw))
-            fused = e16(NB, 2 * fh, 2 * fw, PE(Fc))
+            # The bins head's projectors (pj{i}.c1: 1x1 conv 256 -> 64 + ReLU on the fused maps, HF modeling_zoedepth.py:749-772) read an
+            # UPSAMPLED map too: their convolution runs here, on the low-resolution projection output (a quarter of the pixels; the product
+            # is kept as (hi | lo) pairs), and the level upsamples it, adds the bias and applies the ReLU.  Reading the 256-channel fused map at
+            # full resolution instead moved 6.4 GB in for 1.6 GB out at pj3.c1 (1.36 ms).
+            z = e16(NB * fh * fw, PM * m2)
+            nplain(f"pj{li}.c1", lowp, f"pj{li}.c1.w", z, NB * fh * fw, PM, Fc, out8=False)
+            pj_low.append((z, fh, fw))
+            fused = e16(NB, 2 * fh, 2 * fw, Fc * m2)
             # (the last fused map is read by the relative head's first convolution only: when that product is weight-only the resize does not
             # form the lo8 plane -- flag bit 3 -- and the tap's format code says so: 3 = (hi16 | hi8 | -))
-            nolo = bool(li == 3 and pj_lowres and lo8_rows("rh.projection.w" if eng.add_projection else "rh.conv1.w"))
-            nopl = bool(nolo and hi8_rows("rh.projection.w" if eng.add_projection else "rh.conv1.w"))
-            P.add(f"fu{li}.up", "bs_resize_bilinear_nhwc", lowp, fused, NB, fh, fw, Fc, 2 * fh, 2 * fw, RZ | (8 if nolo else 0) | (16 if nopl else 0), L.dt(fused))
+            nolo = bool(li == 3 and self.lo8_rows(rh_in))
+            nopl = bool(nolo and self.hi8_rows(rh_in))
+            P.add(f"fu{li}.up", "bs_resize_bilinear_nhwc", lowp, fused, NB, fh, fw, Fc, 2 * fh, 2 * fw, self.RZ | (8 if nolo else 0) | (16 if nopl else 0), L.dt(fused))
             free(lowp)
-            P.mark(f"fused{li}", fused, ("nhwc", NB, 2 * fh, 2 * fw, Fc, 3 if nolo else mfmt(Fc)))
+            P.mark(f"fused{li}", fused, ("nhwc", NB, 2 * fh, 2 * fw, Fc, 3 if nolo else self.mfmt()))
             fused_list.append((fused, 2 * fh, 2 * fw))
-        # ---- Z6: relative head (conv3 + ReLU -> relative depth is dead code for the NK output and not launched)
-        f3, h3, w3 = fused_list[3]
+        return fused_list, pj_low
+
+    def _relative_head(self, f3, h3, w3):
+        """Z6: relative head on the last fused map f3 [NB, h3, w3, fusion * m2] (conv3 + ReLU -> relative depth is dead code for the NK output
+        and not launched); returns the relative features [NB, 2 h3, 2 w3, rel_features * m2]"""
+        c, w, P, eng, NB, acc, m2, nf8, Fc = self.c, self.w, self.plan, self.eng, self.NB, self.acc, self.m2, self.nf8, self.c.fusion
+        e16, free, nconv = self.e16, self.pool.free, self.nconv
         if eng.add_projection:
-            rp = e16(NB, h3, w3, PE(Fc))
-            nconv("rh.projection", f3, "rh.projection.w", rp, h3, w3, Fc, Fc, bias=w["rh.projection.b"], act=L.ACT_RELU, out_lo8_rows=lo8_rows("rh.conv1.w"))
+            rp = e16(NB, h3, w3, Fc * m2)
+            nconv("rh.projection", f3, "rh.projection.w", rp, h3, w3, Fc, Fc, bias=w["rh.projection.b"], act=L.ACT_RELU, out_lo8_rows=self.lo8_rows("rh.conv1.w"))
+            free(f3)
         else:
             rp = f3
-        if eng.add_projection and pj_lowres:
-            free(f3)
         r1 = e16(NB, h3, w3, (Fc // 2) * m2)
-        nconv("rh.conv1", rp, "rh.conv1.w", r1, h3, w3, Fc, Fc // 2, bias=w["rh.conv1.b"], out_lo8_rows=lo8_rows("rh.conv2.w"))
-        if eng.add_projection or pj_lowres:
-            free(rp)
+        nconv("rh.conv1", rp, "rh.conv1.w", r1, h3, w3, Fc, Fc // 2, bias=w["rh.conv1.b"], out_lo8_rows=self.lo8_rows("rh.conv2.w"))
+        free(rp)
         # HF: interpolate x2 (align_corners), conv2 3x3 128 -> 32, ReLU (modeling_zoedepth.py:358-362).  Both are linear and the resize acts
         # per channel, so conv2(up(x))(p) = sum_tap up(W_tap x)(p + d_tap): the nine 1x1 tap products run as ONE plain GEMM at the low
         # resolution (N = 9 * 32, a quarter of the conv's FLOPs; the N = 32 conv ran at 20 % of the MFMA peak, bound by the LDS fill
         # rate) and bs_upconv_tapsum gathers / interpolates / sums them -- the upsampled map is never materialised.
-        # Round 5: one launch (bs_upconv_fused, csrc/upconv_fused.hip) -- the tap products of a 16 x 16 output tile's low-resolution window are
+        # In one launch (bs_upconv_fused, csrc/upconv_fused.hip) the tap products of a 16 x 16 output tile's low-resolution window are
         # formed by MFMA into LDS and interpolated from there, the 7.2 GB fp32 tap-product tensor of the two-launch path (bs_gemm +
         # bs_upconv_tapsum, kept for the (hi | lo) pair formats and for A / B runs: BS_UPCONV_FUSED=0) never exists.
         fused_up = (os.environ.get("BS_UPCONV_FUSED", "1") != "0" and Fc // 2 == 128 and c.rel_features == 32
-                    and ((not acc) or (nf8 and "rh.conv2.w" in f8s)))
-        last = None
+                    and ((not acc) or (nf8 and "rh.conv2.w" in eng.f8s)))
         if fused_up:
             last = e16(NB, 2 * h3, 2 * w3, c.rel_features * m2)
             if acc:
-                sb0, sb1 = f8s["rh.conv2.w"]
-                umode, usc = (1 if eng.neck_site_wonly("rh.conv2.w") else 2), (127 - L.F8_ACT_HI_EXP, sb0, 127 - L.F8_ACT_LO_EXP, sb1)
+                umode, usc = (1 if eng.neck_site_wonly("rh.conv2.w") else 2), self.f8_scales("rh.conv2.w")
+                # (set, where nplain adds: this launch is the site's only product)
                 self.site_flops["rh.conv2.w"] = 2.0 * NB * h3 * w3 * 9 * c.rel_features * (Fc // 2)
             else:
                 umode, usc = 0, (127, 127, 127, 127)
             P.add("rh.conv2", "bs_upconv_fused", r1, w["rh.conv2.w"], w["rh.conv2.b"], last, NB, h3, w3, Fc // 2, c.rel_features, 2 * h3, 2 * w3,
-                  RZ, 1, umode, *usc, L.dt(last))
+                  self.RZ, 1, umode, *usc, L.dt(last))
             # the reference's product: conv 3x3 (Fc/2 -> rel_features) at the UPSAMPLED resolution; what runs: nine tap products at the low one,
             # plus their FP8 correction stage(s)
             f_low = 2.0 * NB * h3 * w3 * 9 * c.rel_features * (Fc // 2)
             P.tag_stack(4.0 * f_low, f_low * (1.0, 1.5, 2.0)[umode])       # (executed: bs_gemm's convention, an FP8 stage = half a pass)
             free(r1)
         else:
-            y9 = e32(NB, h3, w3, 9 * c.rel_features)
+            y9 = self.e32(NB, h3, w3, 9 * c.rel_features)
             # (K = 128: a block's main loop is four K steps, the launch is bound by block turnover -- the 128x64 tile, 3 blocks per CU,
             # takes 3.8 ms where the 128x128 one takes 5.9, tools/probes/rh_conv2_tiles.py)
-            nplain("rh.conv2", r1, "rh.conv2.w", y9, NB * h3 * w3, 9 * c.rel_features, Fc // 2, out_pairs=False, tile=2)
+            self.nplain("rh.conv2", r1, "rh.conv2.w", y9, NB * h3 * w3, 9 * c.rel_features, Fc // 2, out_pairs=False, tile=2)
             free(r1)
             last = e16(NB, 2 * h3, 2 * w3, c.rel_features * m2)
-            P.add("rh.tapsum", "bs_upconv_tapsum", y9, w["rh.conv2.b"], last, NB, h3, w3, c.rel_features, 2 * h3, 2 * w3, RZ, 1, L.dt(last))
+            P.add("rh.tapsum", "bs_upconv_tapsum", y9, w["rh.conv2.b"], last, NB, h3, w3, c.rel_features, 2 * h3, 2 * w3, self.RZ, 1, L.dt(last))
             free(y9)
-        P.mark("rel_features", last, ("nhwc", NB, 2 * h3, 2 * w3, c.rel_features, (2 if nf8 else 1) if acc else 0))
-        # ---- Z7 (continued): projector / attractor levels on the fusion outputs
-        ph_, pw_ = bh_, bw_
-        clb_composed = os.environ.get("BS_CLB_COMPOSED", "1") != "0"       # (A / B switch: 0 = the embedding product on the 128-channel embedding)
-        # Round 6: the level's projector path in ONE launch (csrc/projector.hip, bs_projector_level): e1 = relu(resize(z) + b), emb = W_c2 e1 + b,
-        # x = round16(emb + resize(emb_prev)) and -- at the last level -- the composed log-binomial embedding product, with e1 and emb never
-        # in memory (rounds 2-5: bs_resize_bias_relu_nhwc + a 3-pass bs_gemm + the sum inside bs_mlp2_add + another 3-pass bs_gemm: 2 368 B
-        # through HBM per finest-level pixel where this moves 640).  BS_PROJECTOR_LEVEL=0: the four launches (A / B, and the path of every
-        # geometry / format the kernel is not built for: rows that are no multiple of 32 pixels, single 16-bit operands).
-        proj_level = (os.environ.get("BS_PROJECTOR_LEVEL", "1") != "0" and acc and pj_lowres and clb_composed and PM == 64 and E == 128
-                      and 2 * HID <= 80 and (2 * HID) % 16 == 0 and eng.fuse_mlp
-                      and all(fw_ % 32 == 0 and 2 * zw_ == fw_ and 2 * zh_ == fh_ for (_, fh_, fw_), (_, zh_, zw_) in zip(fused_list, pj_low))
-                      and all(tuple(w[f"at{i_}.c1.w"].shape) == (256, 128) and 2 * eng.na_eff[i_] <= 32 for i_ in range(4)))
+        P.mark("rel_features", last, ("nhwc", NB, 2 * h3, 2 * w3, c.rel_features, self.mfmt()))
+        return last
+
+    # ---- Z7, second half: projector / attractor levels on the fusion outputs, in one of two forms chosen once per plan.  Both take the fused
+    # maps' shapes, the projectors' low-resolution inputs, the seed bins / embedding on the (ph, pw) grid and return the finest level's bins, the
+    # log-binomial embedding product Eh fp32 [NB * ph * pw, 2 * clb_hidden] and that level's grid.
+    def _projector_level_fits(self, fused_list, pj_low):
+        """is bs_projector_level built for this plan's formats and geometry?  (Not: rows that are no multiple of 32 pixels, single 16-bit
+        operands, the single-head models' wider hidden layers; BS_PROJECTOR_LEVEL=0 forces the four launches: A / B.)"""
+        c, w, eng = self.c, self.w, self.eng
+        return (os.environ.get("BS_PROJECTOR_LEVEL", "1") != "0" and self.acc and c.proj_mlp == 64 and c.bin_dim == 128
+                and 2 * c.clb_hidden <= 80 and (2 * c.clb_hidden) % 16 == 0 and eng.fuse_mlp
+                and all(fw_ % 32 == 0 and 2 * zw_ == fw_ and 2 * zh_ == fh_ for (_, fh_, fw_), (_, zh_, zw_) in zip(fused_list, pj_low))
+                and all(tuple(w[f"at{i_}.c1.w"].shape) == (256, 128) and 2 * eng.na_eff[i_] <= 32 for i_ in range(4)))
+
+    def _attractor_step(self, i, A, bins_prev, ph_, pw_, fh, fw):
+        """the level's attractor step on the attractor points A; frees A and the previous level's bins, returns the level's bins"""
+        NB, nb = self.NB, self.c.n_bins
+        bins = self.e32(NB, fh, fw, 2 * nb)
+        self.plan.add(f"at{i}.step", "bs_attractor_step", A, bins_prev, bins, self.route, NB, ph_, pw_, fh, fw, 2, nb, self.eng.na_eff[i])
+        self.pool.free(A, bins_prev)
+        self.plan.mark(f"bins{i}", bins, ("nhwc_route", NB, fh, fw, 2 * nb))
+        return bins
+
+    def _levels_fused(self, fused_list, pj_low, bins_prev, emb_prev, ph_, pw_):
+        """The level's projector path in ONE launch (csrc/projector.hip, bs_projector_level): e1 = relu(resize(z) + b), emb = W_c2 e1 + b,
+        x = round16(emb + resize(emb_prev)) and -- at the last level -- the composed log-binomial embedding product, with e1 and emb never
+        in memory (the four-launch form moves 2 368 B through HBM per finest-level pixel where this moves 640)."""
+        c, w, P, eng, NB, m2 = self.c, self.w, self.plan, self.eng, self.NB, self.m2
+        e16, e32, free = self.e16, self.e32, self.pool.free
+        E, PM, HID = c.bin_dim, c.proj_mlp, c.clb_hidden
         Eh = None
         for i in range(4):
-            feat, fh, fw = fused_list[i]
+            _, fh, fw = fused_list[i]
             Mi = NB * fh * fw
-            if proj_level:
-                z, zh, zw = pj_low[i]
-                assert (zh, zw) == (ph_, pw_), "the projector's low-resolution map and the previous level's embedding share a grid"
-                last_lv = i == 3
-                x16 = e16(Mi, E)
-                emb = None if last_lv else e16(Mi, E * m2)
-                if last_lv:
-                    Eh = e32(Mi, 2 * HID)
-                P.add(f"pj{i}.level", "bs_projector_level", z, w[f"pj{i}.c1.b"], emb_prev, w[f"pj{i}.c2.w"], w[f"pj{i}.c2.b"],
-                      w["clb.e1.w"] if last_lv else None, w["clb.e1.b"] if last_lv else None, x16, emb, Eh, NB, zh, zw, fh, fw, PM, E, 2 * HID,
-                      L.dt(x16))
-                f_alg = 2.0 * Mi * PM * (E + (2 * HID if last_lv else 0))
-                P.tag_stack(f_alg, 3.0 * f_alg)                          # (three 16-bit passes on (hi | lo) pairs, as the bs_gemm launches it replaces)
-                free(z, emb_prev)
-                na = eng.na_eff[i]
-                A = e32(Mi, 2 * na)
-                P.add(f"at{i}.mlp", "bs_mlp2", x16, E, w[f"at{i}.c1.w"], w[f"at{i}.c1.b"], w[f"at{i}.c2.w"], w[f"at{i}.c2.b"], A, Mi, E, 2 * E,
-                      2 * na, L.ACT_SOFTPLUS_FAST, L.dt(x16))
-                P.tag_stack(2.0 * Mi * (E * 2 * E + 2 * E * 2 * na), 2.0 * Mi * (E * 2 * E + 2 * E * 2 * na))      # the attractor's two 1x1 convolutions
-                free(x16)
-                bins = e32(NB, fh, fw, 2 * nb)
-                P.add(f"at{i}.step", "bs_attractor_step", A, bins_prev, bins, self.route, NB, ph_, pw_, fh, fw, 2, nb, na)
-                free(A, bins_prev)
-                P.mark(f"bins{i}", bins, ("nhwc_route", NB, fh, fw, 2 * nb))
-                bins_prev, emb_prev, ph_, pw_ = bins, emb, fh, fw
-                continue
+            z, zh, zw = pj_low[i]
+            assert (zh, zw) == (ph_, pw_), "the projector's low-resolution map and the previous level's embedding share a grid"
+            last_lv = i == 3
+            x16 = e16(Mi, E)
+            emb = None if last_lv else e16(Mi, E * m2)
+            if last_lv:
+                Eh = e32(Mi, 2 * HID)
+            P.add(f"pj{i}.level", "bs_projector_level", z, w[f"pj{i}.c1.b"], emb_prev, w[f"pj{i}.c2.w"], w[f"pj{i}.c2.b"],
+                  w["clb.e1.w"] if last_lv else None, w["clb.e1.b"] if last_lv else None, x16, emb, Eh, NB, zh, zw, fh, fw, PM, E, 2 * HID,
+                  L.dt(x16))
+            f_alg = 2.0 * Mi * PM * (E + (2 * HID if last_lv else 0))
+            P.tag_stack(f_alg, 3.0 * f_alg)                          # (three 16-bit passes on (hi | lo) pairs, as the bs_gemm launches it replaces)
+            free(z, emb_prev)
+            na = eng.na_eff[i]
+            A = e32(Mi, 2 * na)
+            P.add(f"at{i}.mlp", "bs_mlp2", x16, E, w[f"at{i}.c1.w"], w[f"at{i}.c1.b"], w[f"at{i}.c2.w"], w[f"at{i}.c2.b"], A, Mi, E, 2 * E,
+                  2 * na, L.ACT_SOFTPLUS_FAST, L.dt(x16))
+            P.tag_stack(2.0 * Mi * (E * 2 * E + 2 * E * 2 * na), 2.0 * Mi * (E * 2 * E + 2 * E * 2 * na))      # the attractor's two 1x1 convolutions
+            free(x16)
+            bins_prev = self._attractor_step(i, A, bins_prev, ph_, pw_, fh, fw)
+            emb_prev, ph_, pw_ = emb, fh, fw
+        return bins_prev, Eh, ph_, pw_
+
+    def _levels_four(self, fused_list, pj_low, bins_prev, emb_prev, ph_, pw_):
+        """The levels as separate launches (every geometry / format bs_projector_level is not built for): bs_resize_bias_relu_nhwc, the
+        projector's second convolution as a 3-pass bs_gemm, the attractor MLP in the form BS_MLP2 selects, and after the last level the
+        composed log-binomial embedding product."""
+        c, w, P, eng, NB, acc, m2, np3 = self.c, self.w, self.plan, self.eng, self.NB, self.acc, self.m2, self.np3
+        e16, e32, free = self.e16, self.e32, self.pool.free
+        E, PM, HID = c.bin_dim, c.proj_mlp, c.clb_hidden
+        for i in range(4):
+            _, fh, fw = fused_list[i]
+            Mi = NB * fh * fw
             e1 = e16(Mi, PM * m2)
-            if pj_lowres:
-                z, zh, zw = pj_low[i]
-                P.add(f"pj{i}.up", "bs_resize_bias_relu_nhwc", z, w[f"pj{i}.c1.b"], e1, NB, zh, zw, PM, fh, fw, 1 | (2 if acc else 0), L.dt(e1))
-                free(z)
-            else:
-                nplain(f"pj{i}.c1", feat, f"pj{i}.c1.w", e1, Mi, PM, Fc, bias=w[f"pj{i}.c1.b"], act=L.ACT_RELU, out8=False)
-                free(feat)                                         # the fused map's last reader (fused 3 fed the relative head earlier)
+            z, zh, zw = pj_low[i]
+            P.add(f"pj{i}.up", "bs_resize_bias_relu_nhwc", z, w[f"pj{i}.c1.b"], e1, NB, zh, zw, PM, fh, fw, 1 | (2 if acc else 0), L.dt(e1))
+            free(z)
             emb = e16(Mi, E * m2)
             P.gemm(f"pj{i}.c2", e1, w[f"pj{i}.c2.w"], emb, M=Mi, N=E, K=PM * np3, lda=PM * m2, seg1=PM if acc else 0,
                    ldo=E * m2, out_split_off=E if acc else 0, bias=w[f"pj{i}.c2.b"], precision_passes=np3)
-            if i == 3 and clb_composed:
-                e1_last = e1                                       # (read once more by the composed log-binomial embedding product below)
-            else:
-                free(e1)
+            if i < 3:
+                free(e1)                                           # (the last level's is read once more by the composed embedding product below)
             na = eng.na_eff[i]                                     # attractors of this level (replicated up to a multiple of 4)
             A = e32(Mi, 2 * na)
             fuse = E == 128 and 2 * na <= 32 and eng.fuse_mlp and tuple(w[f"at{i}.c1.w"].shape) == (256, 128)
+            f_mlp = 2.0 * Mi * (E * 2 * E + 2 * E * 2 * na)        # the attractor's two 1x1 convolutions
             if fuse and eng.fuse_mlp > 1:
                 # the level in ONE launch: emb + resize(emb_prev) is formed inside the MLP kernel (its hi half is all the MLP reads) and
                 # never stored -- bit-identical to bs_add_resized + bs_mlp2 (csrc/mlp2.hip, FUSE)
                 P.add(f"at{i}.mlp", "bs_mlp2_add", emb, emb_prev, w[f"at{i}.c1.w"], w[f"at{i}.c1.b"], w[f"at{i}.c2.w"], w[f"at{i}.c2.b"], A, NB, ph_,
                       pw_, fh, fw, E, 2 * E, 2 * na, L.ACT_SOFTPLUS_FAST, L.dt(emb) | (16 if acc else 0))
-                P.tag_stack(2.0 * Mi * (E * 2 * E + 2 * E * 2 * na), 2.0 * Mi * (E * 2 * E + 2 * E * 2 * na))      # the attractor's two 1x1 convolutions
+                P.tag_stack(f_mlp, f_mlp)
                 free(emb_prev)
-                y = None
             else:
                 y = e16(Mi, E * m2)
                 P.add(f"at{i}.add", "bs_add_resized", emb, emb_prev, y, NB, ph_, pw_, fh, fw, E, L.dt(y) | (16 if acc else 0))
                 free(emb_prev)
-            if y is None:
-                pass
-            elif fuse:
-                # both 1x1 convolutions in one launch: the 256-channel hidden map (3.2 GB at the finest level) never reaches memory;
-                # bit-identical to the two launches below (bs_mlp2, csrc/mlp2.hip)
-                P.add(f"at{i}.mlp", "bs_mlp2", y, E * m2, w[f"at{i}.c1.w"], w[f"at{i}.c1.b"], w[f"at{i}.c2.w"], w[f"at{i}.c2.b"], A, Mi, E, 2 * E,
-                      2 * na, L.ACT_SOFTPLUS_FAST, L.dt(y))
-                P.tag_stack(2.0 * Mi * (E * 2 * E + 2 * E * 2 * na), 2.0 * Mi * (E * 2 * E + 2 * E * 2 * na))
-                free(y)
-            else:
-                a1 = e16(Mi, 2 * E)
-                P.gemm(f"at{i}.c1", y, w[f"at{i}.c1.w"], a1, M=Mi, N=2 * E, K=E, lda=E * m2, bias=w[f"at{i}.c1.b"], act=L.ACT_RELU)
-                free(y)
-                P.gemm(f"at{i}.c2", a1, w[f"at{i}.c2.w"], A, M=Mi, N=2 * na, K=2 * E, lda=2 * E, bias=w[f"at{i}.c2.b"], act=L.ACT_SOFTPLUS_FAST)
-                free(a1)
-            bins = e32(NB, fh, fw, 2 * nb)
-            P.add(f"at{i}.step", "bs_attractor_step", A, bins_prev, bins, self.route, NB, ph_, pw_, fh, fw, 2, nb, na)
-            free(A, bins_prev)
-            P.mark(f"bins{i}", bins, ("nhwc_route", NB, fh, fw, 2 * nb))
-            bins_prev, emb_prev, ph_, pw_ = bins, emb, fh, fw
-        if proj_level:
-            pass                                                   # (Eh came out of the last level's launch)
-        elif clb_composed:
-            Eh = e32(NB * ph_ * pw_, 2 * HID)
-            P.gemm("clb.emb", e1_last, w["clb.e1.w"], Eh, M=NB * ph_ * pw_, N=2 * HID, K=PM * np3, lda=PM * m2, seg1=PM if acc else 0, bias=w["clb.e1.b"],
-                   precision_passes=np3)
-            free(e1_last)
-        else:
-            Eh = e32(NB * ph_ * pw_, 2 * HID)
-            P.gemm("clb.emb", emb_prev, w["clb.emb.w"], Eh, M=NB * ph_ * pw_, N=2 * HID, K=E * np3, lda=E * m2, seg1=E if acc else 0, bias=w["clb.emb.b"],
-                   precision_passes=np3)
+                if fuse:
+                    # both 1x1 convolutions in one launch: the 256-channel hidden map (3.2 GB at the finest level) never reaches memory;
+                    # bit-identical to the two launches below (bs_mlp2, csrc/mlp2.hip)
+                    P.add(f"at{i}.mlp", "bs_mlp2", y, E * m2, w[f"at{i}.c1.w"], w[f"at{i}.c1.b"], w[f"at{i}.c2.w"], w[f"at{i}.c2.b"], A, Mi, E, 2 * E,
+                          2 * na, L.ACT_SOFTPLUS_FAST, L.dt(y))
+                    P.tag_stack(f_mlp, f_mlp)
+                    free(y)
+                else:
+                    a1 = e16(Mi, 2 * E)
+                    P.gemm(f"at{i}.c1", y, w[f"at{i}.c1.w"], a1, M=Mi, N=2 * E, K=E, lda=E * m2, bias=w[f"at{i}.c1.b"], act=L.ACT_RELU)
+                    free(y)
+                    P.gemm(f"at{i}.c2", a1, w[f"at{i}.c2.w"], A, M=Mi, N=2 * na, K=2 * E, lda=2 * E, bias=w[f"at{i}.c2.b"], act=L.ACT_SOFTPLUS_FAST)
+                    free(a1)
+            bins_prev = self._attractor_step(i, A, bins_prev, ph_, pw_, fh, fw)
+            emb_prev, ph_, pw_ = emb, fh, fw
+        # The embedding half of the log-binomial MLP's first layer reads the LAST projector's output emb = W_c2 e1 + b_c2: two linear maps in
+        # a row, composed at ingestion (clb.e1.*) -- the product reads the projector's 64-channel hidden map e1 instead of the 128-channel embedding
+        Eh = e32(NB * ph_ * pw_, 2 * HID)
+        P.gemm("clb.emb", e1, w["clb.e1.w"], Eh, M=NB * ph_ * pw_, N=2 * HID, K=PM * np3, lda=PM * m2, seg1=PM if acc else 0, bias=w["clb.e1.b"],
+               precision_passes=np3)
+        free(e1)
         free(emb_prev)
+        return bins_prev, Eh, ph_, pw_
+
+    def _depth(self, last, Eh, bins, ph_, pw_):
+        """Z8: log-binomial depth from the relative features, the embedding product and the finest bins; flip average + bicubic + crop +
+        x256 -> uint16"""
+        c, w, P, NB, B, H, W, nh_, nw_, dev = self.c, self.w, self.plan, self.NB, self.B, self.H, self.W, self.nh, self.nw, self.eng.dev
         self.depth_net = torch.empty(NB, nh_, nw_, device=dev, dtype=torch.float32)        # plan outputs are not pooled
-        assert (nh_, nw_) == (2 * h3, 2 * w3)
+        assert tuple(last.shape[1:3]) == (nh_, nw_)
         P.mark("clb_eh", Eh, ("raw",))
-        P.add("logbinom", "bs_logbinom_depth_ex", last, Eh, bins_prev, w["clb.w0_last"], w["clb.w2"], w["clb.b2"], w.get("clb.rel"), HID,
-              self.route, self.depth_net, NB, nh_, nw_, ph_, pw_, c.min_temp, c.max_temp, L.dt(last) | NSP)
+        P.add("logbinom", "bs_logbinom_depth_ex", last, Eh, bins, w["clb.w0_last"], w["clb.w2"], w["clb.b2"], w.get("clb.rel"), c.clb_hidden,
+              self.route, self.depth_net, NB, nh_, nw_, ph_, pw_, c.min_temp, c.max_temp, L.dt(last) | self.NSP)
         P.mark("depth_net", self.depth_net, ("raw",))
-        # ---- Z8: flip average + bicubic + crop + x256 -> uint16
-        free(last, Eh, bins_prev)
+        self.pool.free(last, Eh, bins)
         self.depth_m = torch.empty(B, H, W, device=dev, dtype=torch.float32)
         self.depth_u16 = torch.empty(B, H, W, device=dev, dtype=torch.int16)   # uint16 payload
-        P.add("postprocess", "bs_postprocess_depth", self.depth_net, self.depth_m, self.depth_u16, B, H, W, nh_, nw_, int(flip))
+        P.add("postprocess", "bs_postprocess_depth", self.depth_net, self.depth_m, self.depth_u16, B, H, W, nh_, nw_, int(self.flip))
 
     def run(self, taps: Optional[dict] = None):
         self.plan.run(taps)

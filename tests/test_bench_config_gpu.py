@@ -1,7 +1,7 @@
 """The configurations bench.py times, verified at their stated size (BASELINE.json configs 2-4):
 
   * the B = 64 full-size ZoeD_NK plan (NB = 128 network inputs: 256x256x64 tiles with the FP8 correction stages, the
-    side-stream tail split of o_proj / fc2, the two-lane plan under load) against the B = 1 plan -- the plan that
+    side-stream tail split of o_proj / fc2, the whole plan under load) against the B = 1 plan -- the plan that
     tests/test_zoedepth_gpu.py compares with the fp32 oracle tap by tap -- on sampled frames, bit for bit;
   * a 256-frame run_sequence on batch 64 against the same sequence cut into world = 2 contiguous blocks, the two ranks
     emulated one after the other on this GPU (relatives stitched on the host in place of the RCCL all-gather);

@@ -181,7 +181,7 @@ def test_small_without_relative_head_projection(precision):
 
 
 def test_hip_graph_replay_equals_eager():
-    """Plan.capture(): the two-lane launch sequence as one HIP graph; replays give the eager result bit for bit, for new inputs too."""
+    """Plan.capture(): the launch sequence as one HIP graph; replays give the eager result bit for bit, for new inputs too."""
     from bodyslam_amd.synthetic import make_sequence
     from bodyslam_amd.zoedepth import ZoeDepthEngine
     from oracle import zoedepth_ref as Z
