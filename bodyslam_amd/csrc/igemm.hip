@@ -18,9 +18,12 @@ BS_DECL_TILE(2, 0) BS_DECL_TILE(2, 1)
 BS_DECL_TILE(3, 0) BS_DECL_TILE(3, 1)
 BS_DECL_TILE(9, 0) BS_DECL_TILE(9, 1)
 BS_DECL_TILE(10, 0) BS_DECL_TILE(11, 0)
+BS_DECL_TILE(9s8, 0) BS_DECL_TILE(9s8, 1)      // tile 9 with the 8-phase main loop (igemm_tile9_*_s8.hip)
 #undef BS_DECL_TILE
 
-// tile ids (BMxBNxBK, LDS stages): 1 128x128x64 s2 (2 blocks/CU) | 2 128x64x64 s2 | 3 128x32x64 s2 | 9 256x256x64 s2 (128 KiB)
+// tile ids (BMxBNxBK, LDS stages): 1 128x128x64 s2 (2 blocks/CU) | 2 128x64x64 s2 | 3 128x32x64 s2 | 9 256x256x64 s2 (128 KiB; main loop:
+//   the 8-phase schedule -- four quadrant phases per K tile, counted vmcnt(8), the two wave rows a barrier apart -- or, with ablation
+//   bit 32, the one-barrier-per-K-tile loop of the other tiles)
 //   10 256x256x32 s4 ping-pong (two wave groups alternate MFMA / load phases) | 11 256x128x32 s3, 4 waves (2 blocks/CU)
 static int auto_tile(int M, int N, int K, int tile, bool conv) {
     if (tile != 0) return tile;
@@ -59,6 +62,12 @@ static int launch_tile(IgemmParams& p, int dtype, bool conv, int tile, hipStream
     // correction mode of the instantiation: 1 = FP8 stages / (hi16 | hi8 | lo8) formats, 0 = plain
     const int cm = (p.f8_stages > 0 || p.out_f8 || p.res_f8) ? 1 : 0;
     const bool h = dtype == BS_F16;
+    // Main-loop schedule of tile 9 (an implementation detail of "256x256x64s2": the tile id stays 9): the 8-phase loop for every site class,
+    // because it won in every one and in every round (profiles/gemm_8phase_sched.txt; tools/bench_kernels.py --nb 256, tile 9 against 3209,
+    // 4 rounds of 3): accurate-mode plain products qkv -10.8 %, fc1 -7.6 %, o_proj -9.6 %, fc2 (K = 4096) -14.2 %; 3x3 convolutions 256 -> 256
+    // -6.1 ... -8.1 %; without epilogue 1 316-1 376 against 1 180-1 232 TFLOP/s.  Same bits (tests/test_gemm_sched_gpu.py).  Ablation bit 32
+    // (tile = 3209) forces the one-barrier-per-K-tile loop.
+    const bool sched8 = tile == 9 && !(p.ablate & 32);
 #define BS_TILE(t, c) (h ? igemm_launch_tile##t##_f16_cm##c(p, conv, st) : igemm_launch_tile##t##_bf16_cm##c(p, conv, st))
     switch (tile * 10 + cm) {
         case 10: return BS_TILE(1, 0);
@@ -67,8 +76,8 @@ static int launch_tile(IgemmParams& p, int dtype, bool conv, int tile, hipStream
         case 21: return BS_TILE(2, 1);
         case 30: return BS_TILE(3, 0);
         case 31: return BS_TILE(3, 1);
-        case 90: return BS_TILE(9, 0);
-        case 91: return BS_TILE(9, 1);
+        case 90: return sched8 ? BS_TILE(9s8, 0) : BS_TILE(9, 0);
+        case 91: return sched8 ? BS_TILE(9s8, 1) : BS_TILE(9, 1);
         case 100: return BS_TILE(10, 0);
         case 110: return BS_TILE(11, 0);
 #undef BS_TILE

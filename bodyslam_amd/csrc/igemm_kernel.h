@@ -18,7 +18,8 @@
 //   * accurate mode: K segments / FP8 correction stages evaluate a split-precision product in one launch
 //     (IgemmParams::cin1, f8_stages; the F8 template flag keeps that code out of the fast-mode kernels).
 //   * double-buffered LDS, one barrier per K tile: the DMA of tile t+1 is in flight while tile t
-//     is multiplied.
+//     is multiplied.  The 256x256x64 tile runs the 8-phase schedule instead (SCHED = 1): quarter-stage DMA pieces
+//     stay in flight across the barriers under a counted vmcnt that never drains inside the loop.
 //   * 1-D grid with the bijective XCD remap: the N-tiles of one M-tile (which share the gathered
 //     activations) are consecutive work ids and land on one XCD's L2.
 // Epilogue fuses bias (optionally per row group), ReLU/GELU/softplus, per-channel scale
@@ -80,7 +81,7 @@ struct IgemmParams {
     const float* bias2;  // optional fp32 [groups, N] added to rows >= bias2_row0, group = (m - bias2_row0) / bias2_group_rows
     int bias2_row0, bias2_group_rows;
     int strip;    // work id -> tile order: 0 = row-major (N fastest over the whole width), w > 0 = strips of w N-tiles
-    int ablate;   // diagnostics only (tools/bench_kernels.py): 1 = no DMA after the prologue, 2 = no LDS fragment reads after tile 0, 4 = no epilogue, 8 = no tail split (host side), 128 = the Q / K epilogue without its stores, 256 = no fast Q / K patch-tile path, 512 = no fast V^T patch-tile path, 1024 = no LDS-staged full-line stores (Q / K tiles, fc1's hi16 tiles), 2048 = no lean (hi16 | hi8 | lo8) epilogue (neck),
+    int ablate;   // diagnostics only (tools/bench_kernels.py): 1 = no DMA after the prologue, 2 = no LDS fragment reads after tile 0, 4 = no epilogue, 8 = no tail split (host side), 128 = the Q / K epilogue without its stores, 256 = no fast Q / K patch-tile path, 512 = no fast V^T patch-tile path, 1024 = no LDS-staged full-line stores (Q / K tiles, fc1's hi16 tiles), 2048 = no lean (hi16 | hi8 | lo8) epilogue (neck), 32 = tile 9 with the one-barrier-per-K-tile main loop instead of the 8-phase one (host side; the 8-phase loop knows bit 1 only, not bit 2)
 };
 
 template <typename T>
@@ -216,7 +217,10 @@ __device__ __forceinline__ void wait_vmcnt() {
 // (accurate mode); 0 = the plain instantiation, which carries none of that code, so fast-mode launches are not affected by its
 // register pressure.  (CM = 2, FP4 correction stages with per-block scales, existed in round 3: +1.4 % frames/s for 1.5x the depth error --
 // removed in round 4, profiles/r03_fp4_corrections.txt keeps the measurements.)
-template <typename T, int BM, int BN, int WM, int WN, int BK, int STAGES, int MODE, bool PP = false, int CM = 0>
+// SCHED (ring loop of the 256x256x64 two-stage tile only): 0 = one barrier per K tile, the whole next stage issued behind it after a
+// vmcnt(0) drain; 1 = the 8-phase schedule (four quadrant phases per K tile, quarter-stage DMA pieces that stay in flight across the
+// barriers under a counted vmcnt, the two wave rows one barrier apart) -- see the SCHED == 1 branch of the main loop.
+template <typename T, int BM, int BN, int WM, int WN, int BK, int STAGES, int MODE, bool PP = false, int CM = 0, int SCHED = 0>
 __global__ __launch_bounds__(WM* WN * 64, 2) void igemm_kernel(const IgemmParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the buffer-descriptor builtins exist in the device pass only; the host pass needs just the stub
     constexpr bool CONV = MODE != 0;
@@ -321,7 +325,10 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void igemm_kernel(const IgemmParams
     unsigned w_off[RB];
 #pragma unroll
     for (int j = 0; j < RB; ++j) {
-        const int r = j * RPR + srow;
+        int r = j * RPR + srow;
+        // 8-phase schedule: the W image is stored as two 128-row halves, half h = the h-th 32 rows of every wave column's 64
+        // (LDS row h*128 + wn*32 + x holds tile row wn*64 + h*32 + x), so that one half is one pair of DMA rounds
+        if (SCHED == 1) r = (((r >> 5) & 3) << 6) | ((r >> 7) << 5) | (r & 31);
         int n = tn * BN + ((r & ~31) | ((r & 12) << 1) | ((r & 16) >> 2) | (r & 3));
         n = n < p.N ? n : p.N - 1;
         w_off[j] = (unsigned)(n * w_pitch + cs16);
@@ -340,25 +347,8 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void igemm_kernel(const IgemmParams
     const int ntaps = CONV ? p.KH * p.KW : 1;
     int s_tap = 0, s_kx = 0, s_tapoff = 0, s_cb = 0, s_sub = 0, s_k = 0, s_seg = seg0;
 
-    auto stage = [&](int buf) {
-        char* sa = smem + buf * STAGE;
-        char* sb = sa + A_BYTES;
-        const int s_c0 = s_cb + s_sub;
-#pragma unroll
-        for (int j = 0; j < RA; ++j) {
-            unsigned vo;
-            if (CONV) {
-                vo = ((a_mask[j] >> s_tap) & 1u) ? a_off[j] + (unsigned)s_tapoff : OOB;
-            } else {
-                vo = a_off[j];
-            }
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(sa + (j * RPR + wave * RPW) * ROWB), 16, vo,
-                                                     s_c0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < RB; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(sb + (j * RPR + wave * RPW) * ROWB), 16, w_off[j],
-                                                     s_k, 0, 0);
+    // the K walk: called once per staged tile, after its last DMA piece
+    auto stage_advance = [&]() {
         s_k += BK * 2;
         if (BK == 32) {
             s_sub ^= 64;                       // second half of the 64-channel chunk, same tap
@@ -383,6 +373,27 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void igemm_kernel(const IgemmParams
             }
         }
     };
+    auto stage = [&](int buf) {
+        char* sa = smem + buf * STAGE;
+        char* sb = sa + A_BYTES;
+        const int s_c0 = s_cb + s_sub;
+#pragma unroll
+        for (int j = 0; j < RA; ++j) {
+            unsigned vo;
+            if (CONV) {
+                vo = ((a_mask[j] >> s_tap) & 1u) ? a_off[j] + (unsigned)s_tapoff : OOB;
+            } else {
+                vo = a_off[j];
+            }
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(sa + (j * RPR + wave * RPW) * ROWB), 16, vo,
+                                                     s_c0, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < RB; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(sb + (j * RPR + wave * RPW) * ROWB), 16, w_off[j],
+                                                     s_k, 0, 0);
+        stage_advance();
+    };
 
     f32x4 acc[FM][FN];
 #pragma unroll
@@ -403,7 +414,206 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void igemm_kernel(const IgemmParams
     const bool wonly = F8 && p.f8_wonly_from != 0 && (p.f8_wonly_from < 0 || m0 >= p.f8_wonly_from);
     const bool skip8 = F8 && p.f8_skip_from != 0 && (p.f8_skip_from < 0 || m0 >= p.f8_skip_from);
     const int nt = skip8 ? nt16 : (wonly ? nt_all - (ncorr >> 1) : nt_all);
-    if constexpr (!PP) {
+    if constexpr (!PP && SCHED == 1) {
+        // ---- 8-phase schedule of the 256x256x64 two-stage ring.  A K tile is multiplied in four PHASES, one 64 x 32 quadrant of the
+        // wave's 128 x 64 tile each (8 accumulators x the full BK: 16 MFMAs, or 8 of the FP8 16x16x128), and staged in four PIECES of
+        // two DMA instructions per wave: A0 / A1 = activation rows [h*64, h*64+64) of both wave rows (DMA rounds h and h+2),
+        // W0 / W1 = the h-th 32 rows of every wave column (rounds 2h, 2h+1 of the regrouped W image, see w_off).  Quadrant (a, b)
+        // needs exactly the pieces Aa and Wb.  Per tile t, ring slot t & 1:
+        //   phase 1: read W0, A0 (12 ds_read_b128) | issue W1(t+1) | (A0,W0)      phase 3: read A1 (8) | issue A0(t+2) | (A1,W1)
+        //   phase 2: read W1 (4) | issue A1(t+1), K walk | (A0,W1)                phase 4: no read (W0 is kept) | issue W0(t+2) | (A1,W0)
+        // Every phase is  reads, issue, counted wait | barrier | MFMAs | barrier;  the wave row wm = 1 runs one barrier behind wm = 0,
+        // so on every SIMD one wave multiplies while its partner reads and issues.  With global phase numbers P = 4t + q - 1 the
+        // pieces form one stream k = 4u + (A0, W0, W1, A1); piece k is ISSUED in phase k - 6 and first READ in phase 4u (A0, W0),
+        // 4u + 1 (W1), 4u + 2 (A1).  The placement rules, by count and not by observation:
+        //   WAR  a slot's piece is restaged no sooner than two phases after its last read, because the other wave row finishes a
+        //        phase's reads one barrier later (last reads of tile t: A0, W0 in phase 1, W1 in 2, A1 in 3; their slots are
+        //        restaged in phases 3 and 4 of t and 1 and 2 of t+1: two, three, three and three phases later).
+        //   RAW  a piece is read one phase or more after a counted wait that retires it in every wave: the wait of phase P (after
+        //        its own issue, before its first barrier) must retire piece P + 2, while pieces up to min(P + 6, 4 nt - 1) are
+        //        issued: vmcnt(2 x min(4, 4 nt - 3 - P)).  That is vmcnt(8) -- four pieces, one whole tile, in flight across the
+        //        barriers -- in the steady state, and 4, 2, 0 in phase 4 of the last but one tile and phases 1, 2 of the last.
+        //        Phase 3 needs no wait (phase 4 reads nothing).  Never 0 before the last tile's second phase.
+        // Each accumulator still receives its products in the order of the SCHED 0 loop (tiles ascending, kk = 0 then 1, the same
+        // operands): the results are the same bits.
+        static_assert(BM == 256 && BN == 256 && WM == 2 && WN == 4 && BK == 64 && STAGES == 2, "the 8-phase schedule is laid out for 256x256x64, 2 x 4 waves, two stages");
+        static_assert(RA == 4 && RB == 4 && FM == 8 && FN == 4, "piece / quadrant geometry");
+        const bool dma = !(p.ablate & 1);
+        auto stage_piece = [&](int buf, auto piece_tag) {
+            constexpr int PC = decltype(piece_tag)::value;   // stream order: 0 = A0, 1 = W0, 2 = W1, 3 = A1
+            char* sa = smem + buf * STAGE;
+            char* sb = sa + A_BYTES;
+            if constexpr (PC == 0 || PC == 3) {
+                const int s_c0 = s_cb + s_sub;
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj) {
+                    constexpr int h = PC == 3 ? 1 : 0;
+                    const int j = h + 2 * jj;
+                    unsigned vo;
+                    if (CONV) {
+                        vo = ((a_mask[j] >> s_tap) & 1u) ? a_off[j] + (unsigned)s_tapoff : OOB;
+                    } else {
+                        vo = a_off[j];
+                    }
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(sa + (j * RPR + wave * RPW) * ROWB), 16,
+                                                             vo, s_c0, 0, 0);
+                }
+            } else {
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj) {
+                    constexpr int h = PC == 2 ? 1 : 0;
+                    const int j = 2 * h + jj;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(sb + (j * RPR + wave * RPW) * ROWB), 16,
+                                                             w_off[j], s_k, 0, 0);
+                }
+            }
+        };
+        using PA0 = std::integral_constant<int, 0>;
+        using PW0 = std::integral_constant<int, 1>;
+        using PW1 = std::integral_constant<int, 2>;
+        using PA1 = std::integral_constant<int, 3>;
+        auto phase_barrier = [&]() {
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        const int b_base8 = (wn * 32 + frow) * ROWB;     // row of fragment (h, jj) in the regrouped W image: h*128 + wn*32 + jj*16 + frow
+        v8 af[4][2], bf[2][2][2];                        // af[i][kk]: the current A half; bf[h][jj][kk]: both W halves
+        auto read_a = [&](const char* sa, int h) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) af[i][kk] = *reinterpret_cast<const v8*>(sa + a_base + (h * 4 + i) * 16 * ROWB + (kk ? koff1 : koff0));
+        };
+        auto read_w = [&](const char* sb, auto h_tag) {
+            constexpr int h = decltype(h_tag)::value;
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk)
+                    bf[h][jj][kk] = *reinterpret_cast<const v8*>(sb + b_base8 + (h * 128 + jj * 16) * ROWB + (kk ? koff1 : koff0));
+        };
+        using H0 = std::integral_constant<int, 0>;
+        using H1 = std::integral_constant<int, 1>;
+        int cbuf = 0;
+        int sca = 0, scb = 0;
+        auto multiply = [&](auto f8_tag, auto a_tag, auto b_tag) {
+            constexpr bool F8S = decltype(f8_tag)::value == 1;
+            constexpr int ah = decltype(a_tag)::value, bh = decltype(b_tag)::value;
+            __builtin_amdgcn_s_setprio(1);
+            if constexpr (F8S) {
+                typedef int i32x4 __attribute__((ext_vector_type(4)));
+                typedef int i32x8 __attribute__((ext_vector_type(8)));
+                auto op8 = [&](const v8& lo, const v8& hi) {
+                    return __builtin_shufflevector(__builtin_bit_cast(i32x4, lo), __builtin_bit_cast(i32x4, hi), 0, 1, 2, 3, 4, 5, 6, 7);
+                };
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const i32x8 a8 = op8(af[i][0], af[i][1]);
+#pragma unroll
+                    for (int jj = 0; jj < 2; ++jj)
+                        acc[ah * 4 + i][bh * 2 + jj] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(op8(bf[bh][jj][0], bf[bh][jj][1]), a8,
+                                                                                                        acc[ah * 4 + i][bh * 2 + jj], 0, 0, 0, scb, 0, sca);
+                }
+            } else {
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int jj = 0; jj < 2; ++jj)
+                            acc[ah * 4 + i][bh * 2 + jj] = T16<T>::mfma16(bf[bh][jj][kk], af[i][kk], acc[ah * 4 + i][bh * 2 + jj]);
+            }
+            __builtin_amdgcn_s_setprio(0);
+        };
+        auto relu_a = [&]() {
+            if constexpr (RELU_A) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int kk = 0; kk < 2; ++kk) af[i][kk] = relu8<T>(af[i][kk]);
+            }
+        };
+        // one K tile = four phases.  STEADY: at least two tiles follow (every issue happens, every wait is vmcnt(8)): the loop body
+        // without a branch; otherwise the issues and the counts follow `left`, the number of tiles behind this one.
+        auto tile = [&](int t, auto f8_tag, auto steady_tag) {
+            constexpr bool F8S = decltype(f8_tag)::value == 1;
+            constexpr bool STEADY = decltype(steady_tag)::value == 1;
+            const int left = nt - 1 - t;
+            const char* sa = smem + cbuf * STAGE;
+            const char* sb = sa + A_BYTES;
+            if constexpr (F8S) {
+                const bool second = t >= nt16 + ((nt_all - nt16) >> 1);
+                sca = (second ? p.f8_sa1 : p.f8_sa0) * 0x01010101;
+                scb = (second ? p.f8_sb1 : p.f8_sb0) * 0x01010101;
+            }
+            // phase 1
+            read_w(sb, H0{});
+            __builtin_amdgcn_sched_barrier(0);
+            read_a(sa, 0);
+            if ((STEADY || left >= 1) && dma) stage_piece(cbuf ^ 1, PW1{});
+            if (STEADY || left >= 1) wait_vmcnt<8>();
+            else wait_vmcnt<2>();
+            phase_barrier();
+            relu_a();
+            multiply(f8_tag, H0{}, H0{});
+            phase_barrier();
+            // phase 2
+            read_w(sb, H1{});
+            if (STEADY || left >= 1) {
+                if (dma) stage_piece(cbuf ^ 1, PA1{});
+                stage_advance();
+                wait_vmcnt<8>();
+            } else {
+                wait_vmcnt<0>();
+            }
+            phase_barrier();
+            multiply(f8_tag, H0{}, H1{});
+            phase_barrier();
+            // phase 3
+            read_a(sa, 1);
+            if ((STEADY || left >= 2) && dma) stage_piece(cbuf, PA0{});
+            phase_barrier();
+            relu_a();
+            multiply(f8_tag, H1{}, H1{});
+            phase_barrier();
+            // phase 4
+            if ((STEADY || left >= 2) && dma) stage_piece(cbuf, PW0{});
+            if (STEADY || left >= 2) wait_vmcnt<8>();
+            else if (left == 1) wait_vmcnt<4>();
+            phase_barrier();
+            multiply(f8_tag, H1{}, H0{});
+            phase_barrier();
+            cbuf ^= 1;
+        };
+        // prologue: pieces 0..5 (tile 0 and the first two of tile 1); tile 0's A0, W0 are retired with four (nt = 1: two) pieces behind them
+        stage_piece(0, PA0{});
+        stage_piece(0, PW0{});
+        stage_piece(0, PW1{});
+        stage_piece(0, PA1{});
+        stage_advance();
+        if (nt >= 2) {
+            stage_piece(1, PA0{});
+            stage_piece(1, PW0{});
+            wait_vmcnt<8>();
+        } else {
+            wait_vmcnt<4>();
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);        // lgkmcnt(0) alone: the kernel-argument loads (see the SCHED 0 loop)
+        phase_barrier();
+        if (wm == 1) phase_barrier();              // the second wave row runs one barrier behind
+        using S16 = std::integral_constant<int, 0>;
+        using S8 = std::integral_constant<int, 1>;
+        int t = 0;
+        const int n16 = nt16 < nt ? nt16 : nt;
+        for (; t < n16 && t < nt - 2; ++t) tile(t, S16{}, std::integral_constant<int, 1>{});
+        for (; t < n16; ++t) tile(t, S16{}, std::integral_constant<int, 0>{});
+        if constexpr (F8 && !RELU_A) {
+            for (; t < nt - 2; ++t) tile(t, S8{}, std::integral_constant<int, 1>{});
+            for (; t < nt; ++t) tile(t, S8{}, std::integral_constant<int, 0>{});
+        }
+        if (wm == 0) phase_barrier();
+    } else if constexpr (!PP) {
 #pragma unroll
         for (int s = 0; s < STAGES - 1; ++s)
             if (s < nt) stage(s);
@@ -1275,11 +1485,11 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void igemm_kernel(const IgemmParams
 #endif
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int BK, int STAGES, int MODE, bool PP = false, int CM = 0>
+template <typename T, int BM, int BN, int WM, int WN, int BK, int STAGES, int MODE, bool PP = false, int CM = 0, int SCHED = 0>
 inline int launch_mode(const IgemmParams& p, hipStream_t st) {
     constexpr int smem = STAGES * (BM + BN) * BK * 2;
     dim3 grid(p.ntm * p.ntn), block(WM * WN * 64);
-    auto k = igemm_kernel<T, BM, BN, WM, WN, BK, STAGES, MODE, PP, CM>;
+    auto k = igemm_kernel<T, BM, BN, WM, WN, BK, STAGES, MODE, PP, CM, SCHED>;
     BS_MAX_DYNAMIC_LDS(reinterpret_cast<const void*>(k), smem);
     hipLaunchKernelGGL(k, grid, block, smem, st, p);
     BS_CHECK_LAUNCH();
@@ -1287,16 +1497,16 @@ inline int launch_mode(const IgemmParams& p, hipStream_t st) {
 }
 
 // One (tile, operand type, correction mode) per translation unit (igemm_tile*_cm*.hip): they build in parallel.
-template <typename T, int BM, int BN, int WM, int WN, int BK, int STAGES, bool PP, int CM>
+template <typename T, int BM, int BN, int WM, int WN, int BK, int STAGES, bool PP, int CM, int SCHED = 0>
 inline int launch_cm(const IgemmParams& p, bool conv, hipStream_t st) {
     if constexpr (CM == 0) {
-        if (!conv) return launch_mode<T, BM, BN, WM, WN, BK, STAGES, 0, PP, 0>(p, st);
-        if (p.relu_a) return launch_mode<T, BM, BN, WM, WN, BK, STAGES, 2, PP, 0>(p, st);
-        return launch_mode<T, BM, BN, WM, WN, BK, STAGES, 1, PP, 0>(p, st);
+        if (!conv) return launch_mode<T, BM, BN, WM, WN, BK, STAGES, 0, PP, 0, SCHED>(p, st);
+        if (p.relu_a) return launch_mode<T, BM, BN, WM, WN, BK, STAGES, 2, PP, 0, SCHED>(p, st);
+        return launch_mode<T, BM, BN, WM, WN, BK, STAGES, 1, PP, 0, SCHED>(p, st);
     } else {
         static_assert(BK == 64 && !PP, "the correction instantiations are built for the BK = 64 ring tiles");
-        if (!conv) return launch_mode<T, BM, BN, WM, WN, BK, STAGES, 0, PP, CM>(p, st);
-        return launch_mode<T, BM, BN, WM, WN, BK, STAGES, 1, PP, CM>(p, st);
+        if (!conv) return launch_mode<T, BM, BN, WM, WN, BK, STAGES, 0, PP, CM, SCHED>(p, st);
+        return launch_mode<T, BM, BN, WM, WN, BK, STAGES, 1, PP, CM, SCHED>(p, st);
     }
 }
 

@@ -152,7 +152,8 @@ typedef struct bs_gemm_desc {
                                     * bs_relu_split launch re-reading x (HF modeling_zoedepth.py:262-297) */
 } bs_gemm_desc;
 int bs_gemm(const bs_gemm_desc* d, void* stream);
-/* the tile variant bs_gemm will pick for this descriptor (1: 128x128, 2: 128x64, 3: 128x32, 4: 256x128) */
+/* the tile variant bs_gemm will pick for this descriptor (BM x BN x BK: 1: 128x128x64, 2: 128x64x64, 3: 128x32x64, 9: 256x256x64,
+ * 10: 256x256x32 ping-pong, 11: 256x128x32; csrc/igemm.hip).  The main-loop schedule of tile 9 is not part of the id. */
 int bs_gemm_tile(const bs_gemm_desc* d);
 
 /* column means over a sample of the rows of each group: out[g, k] = mean_{j < rows_per_group, j % row_step == 0} A[row0 + g*rows_per_group + j, k]

@@ -17,8 +17,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nb", type=int, default=32)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--tiles", default="1,9,10", help="tile ids (igemm.hip); + 100 x ablation bits for diagnostics, e.g. 409 = tile 9 without epilogue")
+    ap.add_argument("--tiles", default="1,9,10", help="tile ids (igemm.hip); + 100 x ablation bits for diagnostics, e.g. 409 = tile 9 without epilogue, 3209 = tile 9 with the one-barrier main loop")
     ap.add_argument("--only", default="")
+    ap.add_argument("--rounds", type=int, default=1, help="also print the mean of each of this many consecutive groups of --reps / rounds repetitions (an A/B is judged round by round)")
     ap.add_argument("--variants", default="wcls,wmean,wmean-compactA", help="f8 shapes: which class modes to run")
     a = ap.parse_args()
     L.init(0)
@@ -135,7 +136,7 @@ def main():
     for _, _, _, fn in results:
         fn()
     torch.cuda.synchronize()
-    times = [0.0] * len(results)
+    times = [[] for _ in results]
     for r in range(a.reps):
         for i, (_, _, _, fn) in enumerate(results):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -143,10 +144,14 @@ def main():
             fn()
             e1.record()
             e1.synchronize()
-            times[i] += e0.elapsed_time(e1)
+            times[i].append(e0.elapsed_time(e1))
+    per = max(1, a.reps // max(1, a.rounds))
     for i, (name, t, fl, _) in enumerate(results):
-        ms = times[i] / a.reps
-        print(f"{name:28s} tile{t}: {ms * 1e3:9.1f} us  {fl / ms / 1e9:8.1f} TFLOP/s")
+        ms = sum(times[i]) / a.reps
+        rounds = ""
+        if a.rounds > 1:
+            rounds = "  rounds [us]: " + " ".join(f"{sum(times[i][r * per:(r + 1) * per]) / per * 1e3:.1f}" for r in range(a.rounds))
+        print(f"{name:28s} tile{t}: {ms * 1e3:9.1f} us  {fl / ms / 1e9:8.1f} TFLOP/s{rounds}")
 
 
 if __name__ == "__main__":
