@@ -316,6 +316,110 @@ static void launch_accumulate_flags(int flags, dim3 nblocks, hipStream_t st, con
     }
 }
 
+// ---- frame-to-model tracking: point-to-plane against the ray-cast model depth ---------------------------------------------------------
+// The role of Open3D's Model::TrackFrameToModel (point-to-plane, 6 / 3 / 1 iterations) behind the reference's MAP
+// (BodySLAM_not_refactored/3DM/tsdf.py:56-107).  Open3D is un-vendored: parity unpinned; the algorithm is the statement in
+// tests/_point_to_plane_ref.py.  The target of a level is ONE 16-byte record per pixel, (nx, ny, nz, z): the forward-difference
+// normal of the depth map's vertices and the depth itself, so a source pixel's scattered nearest-pixel read is one aligned load
+// (the hybrid step reads six maps there); the target vertex is rebuilt from (u, v, z).  The sums go through the same [blocks, 29]
+// partials, the same pixel-to-block walk and the same finish / solve kernels as the hybrid step.
+
+// depth in metres -> the pyramid's level 0: <= 0 or > depth_max -> NaN
+__global__ __launch_bounds__(256) void odo_p2p_prepare_kernel(const float* __restrict__ depth, int64_t n, float depth_max, float* __restrict__ dout) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float d = depth[i];
+    dout[i] = (d > 0.0f && d <= depth_max) ? d : __builtin_nanf("");
+}
+
+// V(u, v) = ((u - cx) z / fx, (v - cy) z / fy, z); n = normalise((V(u+1, v) - V(u, v)) x (V(u, v+1) - V(u, v))), NaN on the last row
+// and column, where one of the three depths is invalid, or where the cross product has zero length
+__global__ __launch_bounds__(256) void odo_p2p_target_kernel(const float* __restrict__ depth, int H, int W, double fx, double fy, double cx, double cy,
+                                                             float4* __restrict__ rec) {
+    const int u = blockIdx.x * 16 + (threadIdx.x & 15), v = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (u >= W || v >= H) return;
+    depth += (int64_t)blockIdx.z * H * W;
+    rec += (int64_t)blockIdx.z * H * W;
+    const int64_t o = (int64_t)v * W + u;
+    const float zf = depth[o];
+    const float nanf_ = __builtin_nanf("");
+    float4 out = make_float4(nanf_, nanf_, nanf_, zf);
+    if (u + 1 < W && v + 1 < H) {
+        const double z = (double)zf, zr = (double)depth[o + 1], zd = (double)depth[o + W];
+        if (z == z && zr == zr && zd == zd) {
+            const double x0 = ((double)u - cx) * z / fx, y0 = ((double)v - cy) * z / fy;
+            const double ax = ((double)(u + 1) - cx) * zr / fx - x0, ay = ((double)v - cy) * zr / fy - y0, az = zr - z;
+            const double bx = ((double)u - cx) * zd / fx - x0, by = ((double)(v + 1) - cy) * zd / fy - y0, bz = zd - z;
+            const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+            const double len = sqrt(nx * nx + ny * ny + nz * nz);
+            if (len > 0.0) out = make_float4((float)(nx / len), (float)(ny / len), (float)(nz / len), zf);
+        }
+    }
+    rec[o] = out;
+}
+
+// one point-to-plane Gauss-Newton step's sums, per block: A = sum J J^T unweighted, b = sum J clip(r, +-huber), cost = sum huber(r)
+__global__ __launch_bounds__(256) void odo_p2p_accumulate_kernel(const float* __restrict__ Ds, const float4* __restrict__ rec, int H, int W, OdoPose P,
+                                                                 const double* __restrict__ T_dev, double depth_diff, double huber,
+                                                                 double* __restrict__ partial) {
+    {                     // pair blockIdx.y of a batch, as in odo_accumulate_kernel
+        const int64_t o = (int64_t)blockIdx.y * H * W;
+        Ds += o; rec += o;
+        partial += (int64_t)blockIdx.y * gridDim.x * ODO_TERMS;
+    }
+    if (T_dev) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) P.t[i] = T_dev[(int64_t)blockIdx.y * 12 + i];
+    }
+    double tot[ODO_TERMS];
+#pragma unroll
+    for (int k = 0; k < ODO_TERMS; ++k) tot[k] = 0.0;
+    for (int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x; pix < (int64_t)H * W; pix += (int64_t)gridDim.x * 256) {
+        const int v = (int)(pix / W), u = (int)(pix % W);
+        const double z = (double)Ds[pix];
+        if (!(z == z)) continue;
+        const double X = ((double)u - P.cx) * z / P.fx, Y = ((double)v - P.cy) * z / P.fy;
+        const double px = P.t[0] * X + P.t[1] * Y + P.t[2] * z + P.t[3];
+        const double py = P.t[4] * X + P.t[5] * Y + P.t[6] * z + P.t[7];
+        const double pz = P.t[8] * X + P.t[9] * Y + P.t[10] * z + P.t[11];
+        if (!(pz > 0.0)) continue;
+        const double ur = round(P.fx * px / pz + P.cx), vr = round(P.fy * py / pz + P.cy);           // round half away from zero
+        if (!(ur >= 0.0 && ur <= (double)(W - 1) && vr >= 0.0 && vr <= (double)(H - 1))) continue;    // (false for NaN: the index below is in range)
+        const float4 t = rec[(int64_t)(int)vr * W + (int)ur];
+        const double nx = (double)t.x, ny = (double)t.y, nz = (double)t.z, zt = (double)t.w;
+        if (!(nx == nx && zt == zt)) continue;
+        const double qx = (ur - P.cx) * zt / P.fx, qy = (vr - P.cy) * zt / P.fy;
+        const double r = ((px - qx) * nx + (py - qy) * ny) + (pz - zt) * nz;
+        if (!(fabs(r) <= depth_diff)) continue;
+        const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+        const double q = fabs(r) < huber ? r : copysign(huber, r);
+        int k = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) tot[k++] += J[a] * J[b];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) tot[21 + a] += J[a] * q;
+        tot[27] += fabs(r) < huber ? 0.5 * r * r : huber * (fabs(r) - 0.5 * huber);
+        tot[28] += 1.0;
+    }
+    __shared__ double red[4][ODO_TERMS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < ODO_TERMS; ++k) {
+        double s = tot[k];
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        if (lane == 0) red[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < ODO_TERMS) partial[(int64_t)blockIdx.x * ODO_TERMS + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+static int odo_grid(int H, int W) {
+    const int64_t b = cdiv64((int64_t)H * W, 256);
+    return (int)(b < ODO_GRID ? b : ODO_GRID);
+}
+
 }  // namespace bs
 
 using namespace bs;
@@ -403,6 +507,65 @@ extern "C" int bs_odo_step(const float* src_intensity, const float* src_depth, c
     for (int it = 0; it < iterations; ++it) {
         launch_accumulate_flags(flags, dim3(nblocks, batch), st, src_intensity, src_depth, tgt_intensity, tgt_depth, tgt_dIx, tgt_dIy, tgt_dDx, tgt_dDy, H, W,
                                 P, (const double*)T_dev, depth_outlier_trunc, depth_huber, intensity_huber, partial);
+        BS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(odo_finish_solve_kernel, dim3(batch), dim3(1024), 0, st, partial, nblocks, out29, T_dev);
+        BS_CHECK_LAUNCH();
+    }
+    return BS_OK;
+}
+
+extern "C" int bs_odo_p2p_prepare(const float* depth, int32_t batch, int32_t H, int32_t W, double depth_max, float* depth_out, void* stream) {
+    ODO_ENTRY("bs_odo_p2p_prepare");
+    BS_REQUIRE(depth && depth_out && H > 0 && W > 0 && batch > 0, "bs_odo_p2p_prepare: bad argument");
+    const int64_t n = (int64_t)batch * H * W;
+    hipLaunchKernelGGL(odo_p2p_prepare_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), depth, n,
+                       (float)depth_max, depth_out);
+    BS_CHECK_LAUNCH();
+    return BS_OK;
+}
+
+extern "C" int bs_odo_p2p_target(const float* depth, int32_t batch, int32_t H, int32_t W, const double* K, float* target, void* stream) {
+    ODO_ENTRY("bs_odo_p2p_target");
+    BS_REQUIRE(depth && K && target && H > 1 && W > 1 && batch > 0 && batch <= 65535, "bs_odo_p2p_target: bad argument");
+    BS_REQUIRE((reinterpret_cast<uintptr_t>(target) & 15) == 0, "bs_odo_p2p_target: target must be 16-byte aligned");
+    hipLaunchKernelGGL(odo_p2p_target_kernel, dim3(cdiv(W, 16), cdiv(H, 16), batch), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), depth, H, W, K[0],
+                       K[1], K[2], K[3], reinterpret_cast<float4*>(target));
+    BS_CHECK_LAUNCH();
+    return BS_OK;
+}
+
+extern "C" int bs_odo_p2p_accumulate(const float* src_depth, const float* target, int32_t H, int32_t W, const double* K, const double* T,
+                                     double depth_diff, double depth_huber, double* partial, double* out29, void* stream) {
+    ODO_ENTRY("bs_odo_p2p_accumulate");
+    BS_REQUIRE(src_depth && target && K && T && partial && out29, "bs_odo_p2p_accumulate: null argument");
+    BS_REQUIRE(H > 1 && W > 1 && (reinterpret_cast<uintptr_t>(target) & 15) == 0, "bs_odo_p2p_accumulate: bad geometry or unaligned target");
+    OdoPose P;
+    for (int i = 0; i < 12; ++i) P.t[i] = T[i];
+    P.fx = K[0]; P.fy = K[1]; P.cx = K[2]; P.cy = K[3];
+    const int nblocks = odo_grid(H, W);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(odo_p2p_accumulate_kernel, dim3(nblocks), dim3(256), 0, st, src_depth, reinterpret_cast<const float4*>(target), H, W, P,
+                       (const double*)nullptr, depth_diff, depth_huber, partial);
+    BS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(odo_finish_kernel, dim3(ODO_TERMS), dim3(64), 0, st, partial, nblocks, out29);
+    BS_CHECK_LAUNCH();
+    return BS_OK;
+}
+
+extern "C" int bs_odo_p2p_step(const float* src_depth, const float* target, int32_t batch, int32_t H, int32_t W, const double* K, double* T_dev,
+                               int32_t iterations, double depth_diff, double depth_huber, double* partial, double* out29, void* stream) {
+    ODO_ENTRY("bs_odo_p2p_step");
+    BS_REQUIRE(src_depth && target && K && T_dev && partial && out29, "bs_odo_p2p_step: null argument");
+    BS_REQUIRE(H > 1 && W > 1 && iterations >= 0 && batch > 0 && batch <= 65535 && (reinterpret_cast<uintptr_t>(target) & 15) == 0,
+               "bs_odo_p2p_step: bad geometry or unaligned target");
+    OdoPose P;
+    for (int i = 0; i < 12; ++i) P.t[i] = 0.0;
+    P.fx = K[0]; P.fy = K[1]; P.cx = K[2]; P.cy = K[3];
+    const int nblocks = odo_grid(H, W);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    for (int it = 0; it < iterations; ++it) {
+        hipLaunchKernelGGL(odo_p2p_accumulate_kernel, dim3(nblocks, batch), dim3(256), 0, st, src_depth, reinterpret_cast<const float4*>(target), H, W, P,
+                           (const double*)T_dev, depth_diff, depth_huber, partial);
         BS_CHECK_LAUNCH();
         hipLaunchKernelGGL(odo_finish_solve_kernel, dim3(batch), dim3(1024), 0, st, partial, nblocks, out29, T_dev);
         BS_CHECK_LAUNCH();

@@ -21,7 +21,10 @@ Everything runs in the kernels of csrc/odometry.hip.  Three ways to call it:
   * ``track_block(colors, depths)`` -- a block of consecutive frames at once.  The pairs of a sequence do not depend on each other
     (the reference starts every pair from the identity, visual_odometry.py:100), so n frames are n simultaneous pairs: every stage is
     ONE launch over the whole block (~100 launches per block instead of 81 per frame) and the work is HBM streaming instead of a
-    chain of 10-microsecond launches.  Pair for pair the same sums in the same order as the other two: bit-equal results."""
+    chain of 10-microsecond launches.  Pair for pair the same sums in the same order as the other two: bit-equal results.
+
+``PointToPlaneOdometry`` (below) is the other registration of the reference's Open3D models: a depth frame against the map's
+ray-cast depth, point-to-plane, what ``MAP.track_frame_to_model`` runs."""
 from __future__ import annotations
 
 import ctypes as C
@@ -300,3 +303,135 @@ class RGBDOdometry:
             return float(m)
         d = rgbd.depth
         return float(d.max()) if isinstance(d, torch.Tensor) else float(np.nanmax(np.asarray(d)))
+
+
+P2P_ITERATIONS, P2P_DEPTH_DIFF = (6, 3, 1), 0.07      # o3d.t.pipelines.slam.Model.track_frame_to_model defaults, restated (parity unpinned)
+
+
+class PointToPlaneOdometry:
+    """Frame-to-model tracking: where a depth frame sits relative to a model depth image, by point-to-plane Gauss-Newton on a
+    3-level pyramid -- the role of Open3D's ``Model.track_frame_to_model(input_frame, raycast_frame, depth_scale=1000,
+    depth_max=3.0, depth_diff=0.07)`` (point-to-plane, criteria 6 / 3 / 1) behind the reference's MAP (3DM/tsdf.py:56-107).
+    Open3D is not available: those defaults restate its published interface, the algorithm is the statement in
+    tests/_point_to_plane_ref.py (and include/bodyslam_hip.h, bs_odo_p2p_*), and parity with Open3D itself is unpinned.
+
+    The source is the input frame's depth (metres; <= 0 or > depth_max invalid), the target the model's ray-cast depth (0 = no
+    surface).  Both get the hybrid odometry's depth pyramid; every target level becomes one (normal, depth) record per pixel, and
+    the 10 steps run on the device through the hybrid path's reduction, solve and pose update."""
+
+    def __init__(self, K: Sequence[float], device: int = 0, iterations: Sequence[int] = P2P_ITERATIONS, depth_diff: float = P2P_DEPTH_DIFF,
+                 depth_huber: float = DEPTH_HUBER):
+        self.K = tuple(float(v) for v in K)
+        self.dev = torch.device("cuda", device)
+        self.iterations = tuple(int(i) for i in iterations)
+        self.depth_diff, self.depth_huber = float(depth_diff), float(depth_huber)
+        L.init(device)
+        self.last_trace = None
+        self.last_sums = None        # [n, 29] float64 on the device: the sums of the last step of the last call (27 = cost, 28 = inliers)
+        self._buf = None
+
+    def _buffers(self, n: int, H: int, W: int) -> dict:
+        """per (H, W): the depth levels of both sides as one [2, n, h, w] stack each (0 = source, 1 = target: a pyramid stage is one
+        launch over both), the target records, poses and reduction scratch; grown when a larger batch arrives"""
+        k = self._buf
+        if k is not None and k["hw"] == (H, W) and k["n"] >= n:
+            return k
+        levels, (h, w, kk) = [], (H, W, self.K)
+        for _ in range(len(self.iterations)):
+            levels.append(dict(H=h, W=w, Kc=np.array(kk, dtype=np.float64), D=torch.empty(2, n, h, w, device=self.dev, dtype=torch.float32),
+                               rec=torch.empty(n, h, w, 4, device=self.dev, dtype=torch.float32)))
+            h, w, kk = (h + 1) // 2, (w + 1) // 2, tuple(v / 2.0 for v in kk)
+        nblk = min((H * W + 255) // 256, 256)
+        k = self._buf = dict(hw=(H, W), n=n, levels=levels, T=torch.empty(n, 12, dtype=torch.float64, device=self.dev),
+                             T0=torch.tensor([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], dtype=torch.float64, device=self.dev),
+                             partial=torch.empty(n, nblk, 29, dtype=torch.float64, device=self.dev),
+                             out=torch.zeros(n, 29, dtype=torch.float64, device=self.dev))
+        return k
+
+    def _build(self, k: dict, src: torch.Tensor, tgt: torch.Tensor, depth_max: float) -> None:
+        """pyramids of both sides and the target records of every level: 2 + (levels - 1) + levels launches"""
+        lib, st = L.load_library(), L.stream_ptr()
+        n, m = src.shape[0], k["n"]
+        lv = k["levels"]
+        l0 = lv[0]
+        L.check(lib.bs_odo_p2p_prepare(L.p(src), n, l0["H"], l0["W"], float(depth_max), L.p(l0["D"][0]), st), "bs_odo_p2p_prepare")
+        L.check(lib.bs_odo_p2p_prepare(L.p(tgt), n, l0["H"], l0["W"], 3.0e38, L.p(l0["D"][1]), st), "bs_odo_p2p_prepare")
+        for p_, n_ in zip(lv[:-1], lv[1:]):
+            if n == m:           # the stack is full: source and target images are contiguous, one launch
+                L.check(lib.bs_odo_pyrdown(L.p(p_["D"]), 2 * n, p_["H"], p_["W"], L.p(n_["D"]), 1, 2.0 * self.depth_diff, st), "bs_odo_pyrdown")
+            else:
+                for side in (0, 1):
+                    L.check(lib.bs_odo_pyrdown(L.p(p_["D"][side]), n, p_["H"], p_["W"], L.p(n_["D"][side]), 1, 2.0 * self.depth_diff, st), "bs_odo_pyrdown")
+        for l_ in lv:
+            L.check(lib.bs_odo_p2p_target(L.p(l_["D"][1]), n, l_["H"], l_["W"], l_["Kc"].ctypes.data_as(C.c_void_p), L.p(l_["rec"]), st), "bs_odo_p2p_target")
+
+    @staticmethod
+    def _init12(init, n: int) -> Optional[np.ndarray]:
+        if init is None:
+            return None
+        a = init.detach().cpu().numpy() if isinstance(init, torch.Tensor) else np.asarray(init)
+        a = np.asarray(a, dtype=np.float64)
+        a = np.broadcast_to(a, (n, 4, 4)) if a.ndim == 2 else a
+        assert a.shape == (n, 4, 4), "init: one 4x4 or [n, 4, 4]"
+        return np.array(a[:, :3], dtype=np.float64).reshape(n, 12)       # (a fresh, writable copy: torch.from_numpy takes it)
+
+    def estimate_batch(self, src_depths: torch.Tensor, tgt_depths: torch.Tensor, init=None, depth_max: float = 3.0) -> torch.Tensor:
+        """n independent pairs at once (device tensors fp32 [n, H, W], metres): every stage is one launch over the batch.  Returns a
+        fresh device tensor [n, 12] (float64): rows 0..2 of T(source -> target) per pair; nothing is read back (``last_sums`` keeps
+        the last step's sums on the device).  Pair for pair bit-equal to ``estimate``.  init: None (identity), one 4x4 or [n, 4, 4]."""
+        assert src_depths.is_cuda and tgt_depths.is_cuda and src_depths.dtype == torch.float32 and tgt_depths.dtype == torch.float32
+        assert src_depths.dim() == 3 and src_depths.shape == tgt_depths.shape
+        n, H, W = src_depths.shape
+        if n == 0:
+            return torch.empty(0, 12, dtype=torch.float64, device=self.dev)
+        k = self._buffers(n, H, W)
+        self._build(k, src_depths.contiguous(), tgt_depths.contiguous(), depth_max)
+        T = k["T"][:n]
+        i12 = self._init12(init, n)
+        T.copy_(k["T0"].expand(n, 12) if i12 is None else torch.from_numpy(i12).to(self.dev))
+        lib, st = L.load_library(), L.stream_ptr()
+        lv = k["levels"]
+        for level, iters in zip(range(len(lv) - 1, -1, -1), self.iterations):
+            l_ = lv[level]
+            L.check(lib.bs_odo_p2p_step(L.p(l_["D"][0]), L.p(l_["rec"]), n, l_["H"], l_["W"], l_["Kc"].ctypes.data_as(C.c_void_p), L.p(T), iters,
+                                        self.depth_diff, self.depth_huber, L.p(k["partial"]), L.p(k["out"]), st), "bs_odo_p2p_step")
+        self.last_sums = k["out"][:n].clone()
+        self.last_trace = None
+        return T.clone()
+
+    def estimate(self, src_depth, tgt_depth, depth_max: float = 3.0, init: Optional[np.ndarray] = None, trace: bool = False) -> np.ndarray:
+        """T (4x4 float64): source points -> target frame.  Depths: numpy, host or device tensors, metres.  trace=True walks the same
+        steps from the host through bs_odo_p2p_accumulate and keeps (level, A, b, cost, inliers) per step in ``last_trace``."""
+        src, tgt = self._dev(src_depth)[None], self._dev(tgt_depth)[None]
+        T = np.eye(4) if init is None else np.array(init, dtype=np.float64)
+        if not trace:
+            T[:3] = self.estimate_batch(src, tgt, init=init, depth_max=depth_max).cpu().numpy().reshape(3, 4)
+            return T
+        lib, st = L.load_library(), L.stream_ptr()
+        k = self._buffers(1, *src.shape[1:])
+        self._build(k, src, tgt, depth_max)
+        iu = np.triu_indices(6)
+        log = []
+        lv = k["levels"]
+        for level, iters in zip(range(len(lv) - 1, -1, -1), self.iterations):
+            l_ = lv[level]
+            for _ in range(iters):
+                T12 = np.ascontiguousarray(T[:3].reshape(12))
+                L.check(lib.bs_odo_p2p_accumulate(L.p(l_["D"][0]), L.p(l_["rec"]), l_["H"], l_["W"], l_["Kc"].ctypes.data_as(C.c_void_p),
+                                                  T12.ctypes.data_as(C.c_void_p), self.depth_diff, self.depth_huber, L.p(k["partial"]), L.p(k["out"]),
+                                                  st), "bs_odo_p2p_accumulate")
+                r = k["out"][0].cpu().numpy()
+                A = np.zeros((6, 6))
+                A[iu] = r[:21]
+                A = A + np.triu(A, 1).T
+                b, cost, cnt = r[21:27], float(r[27]), int(round(r[28]))
+                log.append((level, A.copy(), b.copy(), cost, cnt))
+                if cnt >= 6:         # (fewer: the pose stays, the schedule goes on -- as the device loop does)
+                    T = se3_exp(np.linalg.solve(A + 1e-12 * np.eye(6), -b)) @ T
+        self.last_sums = k["out"][:1].clone()
+        self.last_trace = log
+        return T
+
+    def _dev(self, x) -> torch.Tensor:
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+        return t.to(device=self.dev, dtype=torch.float32).contiguous()

@@ -16,7 +16,8 @@ vertices of shared cube edges on the host.
 
 ``TSDF.raycast`` asks the map what a camera at a given pose sees (depth, colour, vertices, normals; bs_tsdf_raycast, one thread
 per pixel through the unit table, every view of a call in one launch), and ``MAP`` is the drop-in for the reference's second class
-(tsdf.py:56-107), which synthesises such a model frame after every integration.
+(tsdf.py:56-107), which synthesises such a model frame after every integration and tracks the next frame against it
+(``MAP.track_frame_to_model`` / ``track_and_integrate``: point-to-plane odometry on the ray-cast depth, rgbd_odometry.py).
 """
 from __future__ import annotations
 
@@ -99,6 +100,16 @@ class RaycastFrame:
         evaluation.evaluate_depth reads, 0 = no surface"""
         v = torch.clamp(torch.round(self.depth.to(torch.float64) * float(depth_scale)), 0.0, 65535.0).to(torch.int32)
         return torch.where(v >= 32768, v - 65536, v).to(torch.int16)
+
+
+@dataclass
+class TrackingResult:
+    """What ``MAP.track_frame_to_model`` returns (Open3D: OdometryResult)"""
+    transformation: np.ndarray                  # 4x4 float64: the input frame -> the camera raycast_frame was cast from
+    pose: np.ndarray                            # 4x4 float64: that camera's pose composed with it = the frame's camera -> world
+    inliers: int                                # of the last step (the finest level)
+    cost: float                                 # sum of huber(r) over them
+    fitness: float                              # inliers / (H * W)
 
 
 BATCH_MAX = 64              # frames per pass of build_3D_map_batch (BS_TSDF_BATCH_MAX: one bit per frame in a unit's mask)
@@ -462,16 +473,20 @@ class MAP:
                           max_units=int(block_count))
         self.frame_poses = []                                               # (i, camera -> world) per integrate call
         self.raycast_frame: Optional[RaycastFrame] = None
+        self.last_tracking: Optional[TrackingResult] = None                 # of the last track_frame_to_model call
+        self._tracker = None                                                # ((iterations, depth_diff), PointToPlaneOdometry)
 
-    def integrate(self, curr_rgbd, i, curr_global_pose) -> None:
-        depth = curr_rgbd.depth
+    def _depth_m(self, depth) -> torch.Tensor:
+        """a frame's depth as fp32 metres on the device: an integer depth image is divided by ``depth_scale``"""
         if isinstance(depth, torch.Tensor):
             depth = depth.to(self.model.dev)
-            depth = depth.to(torch.float32) if depth.is_floating_point() else depth.to(torch.float32) / self.depth_scale
-        else:
-            depth = np.asarray(depth)
-            depth = depth.astype(np.float32) if depth.dtype.kind == "f" else depth.astype(np.float32) / np.float32(self.depth_scale)
-            depth = torch.from_numpy(np.ascontiguousarray(depth)).to(self.model.dev)
+            return depth.to(torch.float32) if depth.is_floating_point() else depth.to(torch.float32) / self.depth_scale
+        depth = np.asarray(depth)
+        depth = depth.astype(np.float32) if depth.dtype.kind == "f" else depth.astype(np.float32) / np.float32(self.depth_scale)
+        return torch.from_numpy(np.ascontiguousarray(depth)).to(self.model.dev)
+
+    def integrate(self, curr_rgbd, i, curr_global_pose) -> None:
+        depth = self._depth_m(curr_rgbd.depth)
         pose = np.asarray(TSDF._np(curr_global_pose), dtype=np.float64)
         E = np.linalg.inv(pose)
         self.frame_poses.append((i, pose))
@@ -481,6 +496,44 @@ class MAP:
             lo, hi = (float(v) for v in torch.stack([depth.min(), depth.max()]).cpu())
         lo, hi = max(float(lo) - self.model.sdf_trunc, 0.0), float(hi) + self.model.sdf_trunc
         self.raycast_frame = self.model.raycast(self.intrinsic, E, depth_min=lo, depth_max=hi, color=True)
+
+    def track_frame_to_model(self, curr_rgbd, depth_max: Optional[float] = None, depth_diff: float = 0.07, iterations: Sequence[int] = (6, 3, 1),
+                             init=None) -> TrackingResult:
+        """Where ``curr_rgbd`` sits relative to the map: its depth is registered against ``raycast_frame.depth`` (the model as the
+        last integrated pose sees it) by point-to-plane odometry -- the role of Open3D's ``Model.track_frame_to_model(input_frame,
+        raycast_frame, depth_scale, depth_max=3.0, depth_diff=0.07)``; parity with Open3D unpinned, the algorithm is
+        ``rgbd_odometry.PointToPlaneOdometry``'s.  Depth conventions as in ``integrate``; depth_max: the frame's ``depth_max``
+        attribute when it has one, else 3.0 m.  init: a first guess of the transformation (default: the identity)."""
+        if self.raycast_frame is None:
+            raise RuntimeError("MAP.track_frame_to_model: the map has no raycast_frame yet -- integrate a frame first")
+        from .rgbd_odometry import PointToPlaneOdometry
+        key = (tuple(int(v) for v in iterations), float(depth_diff))
+        if self._tracker is None or self._tracker[0] != key:
+            K = (self.intrinsic.fx, self.intrinsic.fy, self.intrinsic.cx, self.intrinsic.cy)
+            self._tracker = (key, PointToPlaneOdometry(K, device=self.model.dev.index or 0, iterations=key[0], depth_diff=key[1]))
+        odo = self._tracker[1]
+        if depth_max is None:
+            depth_max = getattr(curr_rgbd, "depth_max", None)
+        depth = self._depth_m(curr_rgbd.depth)
+        T = np.eye(4)
+        T[:3] = odo.estimate_batch(depth[None], self.raycast_frame.depth[None], init=init,
+                                   depth_max=3.0 if depth_max is None else float(depth_max)).cpu().numpy().reshape(3, 4)
+        sums = odo.last_sums[0].cpu().numpy()             # the last step's: at the finest level, at the pose before its update
+        inliers = int(round(sums[28]))
+        self.last_tracking = TrackingResult(T, self.frame_poses[-1][1] @ T, inliers, float(sums[27]), inliers / float(depth.shape[0] * depth.shape[1]))
+        return self.last_tracking
+
+    def track_and_integrate(self, curr_rgbd, i, init=None) -> np.ndarray:
+        """Track the frame against the map, then integrate it at the tracked pose; returns that pose (camera -> world).  init: a
+        first guess of the frame's pose.  On an empty map there is nothing to track against: the frame is integrated at ``init``,
+        or at the identity."""
+        guess = None if init is None else np.asarray(TSDF._np(init), dtype=np.float64)
+        if self.raycast_frame is None:
+            pose = np.eye(4) if guess is None else guess
+        else:
+            pose = self.track_frame_to_model(curr_rgbd, init=None if guess is None else np.linalg.inv(self.frame_poses[-1][1]) @ guess).pose
+        self.integrate(curr_rgbd, i, pose)
+        return pose
 
     def extract_pcd(self) -> PointCloud:
         return self.model.extract_pcd()

@@ -511,6 +511,35 @@ int bs_odo_accumulate(const float* src_intensity, const float* src_depth, const 
                       const double* K, const double* T, double depth_outlier_trunc, double depth_huber, double intensity_huber,
                       double* partial, double* out29, int32_t flags, void* stream);
 
+/* frame-to-model tracking: point-to-plane odometry on the ray-cast map --------------------------- *
+ * The role of Open3D's Model.track_frame_to_model(input_frame, raycast_frame, depth_scale = 1000, depth_max = 3.0, depth_diff = 0.07)
+ * (point-to-plane, 6 / 3 / 1 iterations) behind the reference's MAP (BodySLAM_not_refactored/3DM/tsdf.py:56-107).  Open3D is not
+ * vendored: those defaults restate its published interface, the algorithm is stated in tests/_point_to_plane_ref.py, and parity with
+ * Open3D itself is UNPINNED.  The source is the input frame's depth pyramid, the target the pyramid of the model's ray-cast depth
+ * (bs_tsdf_raycast); both use bs_odo_pyrdown in depth mode with threshold 2 * depth_diff, intrinsics halved per level.
+ *   bs_odo_p2p_prepare     level 0 of a pyramid: depth metres fp32 [batch, H, W], <= 0 or > depth_max -> NaN (the ray cast's 0 = no
+ *                          surface becomes NaN with any depth_max)
+ *   bs_odo_p2p_target      the target maps of one level: target = fp32 [batch, H, W, 4], 16-byte aligned, one record (nx, ny, nz, z)
+ *                          per pixel: z = the depth as given (NaN = invalid) and n = the unit normal of the vertex map
+ *                          V(u, v) = ((u - cx) z / fx, (v - cy) z / fy, z), n = normalise((V(u+1, v) - V(u, v)) x (V(u, v+1) - V(u, v))),
+ *                          computed in fp64 and stored as fp32; NaN on the last row and column, where one of the three depths is
+ *                          invalid, or where the cross product has zero length.  The step rebuilds the target vertex from (u, v, z),
+ *                          so its scattered nearest-pixel read is one aligned 16-byte load.  K = (fx, fy, cx, cy) of the level, host
+ *   bs_odo_p2p_accumulate  the sums of one step at the host pose T (rows 0..2 of source -> target), bs_odo_accumulate's out29 layout:
+ *                          for every valid source pixel p = T v_s (p.z > 0), the NEAREST target pixel of its projection (round half
+ *                          away from zero, inside the image), q and n there (both valid), r = (p - q) . n with |r| <= depth_diff,
+ *                          J = [p x n, n] for the left twist (omega, nu); out29 = [sum J J^T (21, unweighted), sum J clip(r, +-depth_huber)
+ *                          (6), sum huber(r), the inlier count]; partial = scratch double [min(ceil(H*W/256), 256), 29]; deterministic
+ *   bs_odo_p2p_step        `iterations` such steps of one level on the device, as bs_odo_step: pair p of `batch` reads source image p,
+ *                          target record image p, pose T_dev[12 p ..], scratch partial[p][.][29], sums out29[29 p ..]; the same finish,
+ *                          6x6 solve and pose update kernels as bs_odo_step; fewer than 6 inliers leave the pose alone */
+int bs_odo_p2p_prepare(const float* depth, int32_t batch, int32_t H, int32_t W, double depth_max, float* depth_out, void* stream);
+int bs_odo_p2p_target(const float* depth, int32_t batch, int32_t H, int32_t W, const double* K, float* target, void* stream);
+int bs_odo_p2p_accumulate(const float* src_depth, const float* target, int32_t H, int32_t W, const double* K, const double* T,
+                          double depth_diff, double depth_huber, double* partial, double* out29, void* stream);
+int bs_odo_p2p_step(const float* src_depth, const float* target, int32_t batch, int32_t H, int32_t W, const double* K, double* T_dev,
+                    int32_t iterations, double depth_diff, double depth_huber, double* partial, double* out29, void* stream);
+
 /* ---- depth evaluation with the reference's MDEM protocol ----------------------------------------------------------------------------
  * Replaces the per-frame body of compute_metrics_for (BodySLAM_not_refactored/EVALUATION/MDEM_eval.py:179-197 masking and median
  * scaling with compute_median_scale_factor :114-127; the MDEM_Metrics functions of EVALUATION/evaluation_metrics.py:24-102).
