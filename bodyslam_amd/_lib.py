@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BODYSLAM_HIP_LIB") or os.path.join(_HERE, "libbodyslam_hip.so")      # (the override: A/B runs of two builds in one call)
 
 F32, F16, BF16 = 0, 1, 2
+F64 = 3                         # bs_similarity_fit only
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_SOFTPLUS, ACT_SOFTPLUS_FAST = 0, 1, 2, 3, 4
 OUT_PLAIN, OUT_SHUFFLE, OUT_QKV = 0, 1, 2
 
@@ -134,6 +135,8 @@ _SIGS = {
     "bs_depth_metrics_workspace": [C.c_int32, C.c_int32, C.c_int32],
     "bs_depth_metrics": [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_double, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
                                                                        C.c_void_p, C.c_void_p],
+    "bs_similarity_fit": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_trajectory_metrics": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
 }
 EXPORTS = sorted(list(_SIGS) + ["bs_last_error"])
 
@@ -722,3 +725,33 @@ def depth_metrics(pred, gt, gt_lo, gt_hi, scale, workspace, out):
 
 def depth_metrics_workspace(B: int, H: int, W: int) -> int:
     return int(load_library().bs_depth_metrics_workspace(B, H, W))
+
+
+TRAJ_EVO, TRAJ_TRAINING = 0, 1
+TRAJ_ALIGN_ORIGIN, TRAJ_ALIGN, TRAJ_CORRECT_SCALE, TRAJ_ALL_PAIRS = 1, 2, 4, 8
+TRAJ_OK, TRAJ_DEGENERATE, TRAJ_TOO_SHORT, TRAJ_BAD_OFFSETS = 0, 1, 2, 3
+TRAJ_FIELDS = 40
+SIMILARITY_FIT_WORKSPACE_BYTES = 131136
+
+
+def similarity_fit(source, target, workspace, out):
+    """source, target: [n, 3] contiguous device tensors, both fp32 or both fp64; workspace: uint8 device tensor of at least
+    SIMILARITY_FIT_WORKSPACE_BYTES; out: fp64 [16] device tensor (include/bodyslam_hip.h)"""
+    n = source.shape[0]
+    assert tuple(source.shape) == (n, 3) and tuple(target.shape) == (n, 3) and source.is_contiguous() and target.is_contiguous()
+    assert source.dtype == target.dtype and source.dtype in (torch.float32, torch.float64), (source.dtype, target.dtype)
+    assert out.dtype == torch.float64 and out.numel() == 16 and out.is_contiguous()
+    check(load_library().bs_similarity_fit(p(source), p(target), n, F32 if source.dtype == torch.float32 else F64, p(workspace),
+                                           workspace.numel() * workspace.element_size(), p(out), stream_ptr()), "bs_similarity_fit")
+
+
+def trajectory_metrics(gt, pred, offsets, protocol, delta, flags, out):
+    """gt, pred: fp64 [total, 16] (or [total, 4, 4]) contiguous device tensors; offsets: int32 [S + 1] device tensor; out: fp64
+    [S, TRAJ_FIELDS] device tensor (include/bodyslam_hip.h)"""
+    total = gt.shape[0]
+    S = offsets.numel() - 1
+    assert gt.dtype == torch.float64 and pred.dtype == torch.float64 and gt.numel() == total * 16 and pred.numel() == total * 16
+    assert gt.is_contiguous() and pred.is_contiguous() and offsets.dtype == torch.int32 and offsets.is_contiguous()
+    assert out.dtype == torch.float64 and tuple(out.shape) == (S, TRAJ_FIELDS) and out.is_contiguous()
+    check(load_library().bs_trajectory_metrics(p(gt), p(pred), p(offsets), S, total, protocol, delta, flags, p(out), stream_ptr()),
+          "bs_trajectory_metrics")

@@ -5,6 +5,7 @@
 //   RGBD depth constants   BodySLAM_not_refactored/3DM/slam_utils.py:173,212-220,232
 //   compute_curr_estimate_global_pose / ensure_so3_v2   3DM/slam_utils.py:93-122
 #include "common.h"
+#include "svd3.h"
 
 namespace bs {
 
@@ -149,54 +150,16 @@ __global__ __launch_bounds__(BP_THREADS) void bp_write_kernel(const uint16_t* de
 
 // ---------------------------------------------------------------------------------------------
 // pose chain: G_i = G_{i-1} * T_i (fp64), R <- U diag(1, 1, det(U) det(V^T)) V^T.
-// One lane walks the chain (it is a strict recurrence); the 3x3 SVD is a one-sided Jacobi in fp64.
+// One lane walks the chain (it is a strict recurrence); the 3x3 SVD is a one-sided Jacobi in fp64 (svd3.h).
 // ---------------------------------------------------------------------------------------------
 __device__ void svd3_project_so3(double (&M)[3][3]) {
-    // one-sided Jacobi on the columns of A = M: A V = U S
-    double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) A[i][j] = M[i][j];
-    for (int sweep = 0; sweep < 40; ++sweep) {
-        double off = 0.0;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                double alpha = 0, beta = 0, gamma = 0;
-                for (int i = 0; i < 3; ++i) {
-                    alpha += A[i][p] * A[i][p];
-                    beta += A[i][q] * A[i][q];
-                    gamma += A[i][p] * A[i][q];
-                }
-                off = fmax(off, fabs(gamma) / sqrt(alpha * beta + 1e-300));
-                if (fabs(gamma) <= 1e-300) continue;
-                const double zeta = (beta - alpha) / (2.0 * gamma);
-                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-                for (int i = 0; i < 3; ++i) {
-                    const double ap = A[i][p], aq = A[i][q];
-                    A[i][p] = cs * ap - sn * aq;
-                    A[i][q] = sn * ap + cs * aq;
-                    const double vp = V[i][p], vq = V[i][q];
-                    V[i][p] = cs * vp - sn * vq;
-                    V[i][q] = sn * vp + cs * vq;
-                }
-            }
-        if (off < 1e-17) break;
-    }
-    double s[3], U[3][3];
-    for (int j = 0; j < 3; ++j) {
-        s[j] = sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j] + A[2][j] * A[2][j]);
-        const double inv = s[j] > 0 ? 1.0 / s[j] : 0.0;
-        for (int i = 0; i < 3; ++i) U[i][j] = A[i][j] * inv;
-    }
+    double s[3], U[3][3], V[3][3];
+    svd3_jacobi(M, U, s, V);
     // the reflection correction acts on the SMALLEST singular direction (LAPACK orders them descending)
     // (ties -> the last index, which is where a descending LAPACK ordering leaves the flipped direction)
     int kmin = 0;
     if (s[1] <= s[kmin]) kmin = 1;
     if (s[2] <= s[kmin]) kmin = 2;
-    auto det3 = [](const double (&X)[3][3]) {
-        return X[0][0] * (X[1][1] * X[2][2] - X[1][2] * X[2][1]) - X[0][1] * (X[1][0] * X[2][2] - X[1][2] * X[2][0]) +
-               X[0][2] * (X[1][0] * X[2][1] - X[1][1] * X[2][0]);
-    };
     const double dd = det3(U) * det3(V);  // det(V^T) == det(V)
     double D[3] = {1.0, 1.0, 1.0};
     D[kmin] = dd;

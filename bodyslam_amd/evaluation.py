@@ -1,10 +1,17 @@
-"""Depth-map evaluation with the reference's MDEM protocol, on the device.
+"""Evaluation with the reference's two protocols, on the device: depth maps (MDEM) and trajectories (MPEM).
 
-The reference judges its depth module by BodySLAM_not_refactored/EVALUATION/MDEM_eval.py (compute_metrics_for, :130-259) over the
+Depth.  The reference judges its depth module by BodySLAM_not_refactored/EVALUATION/MDEM_eval.py (compute_metrics_for, :130-259) over the
 MDEM_Metrics functions of EVALUATION/evaluation_metrics.py:17-102: per frame the GT is masked by dataset, the prediction is scaled by
-the ratio of the medians, and AbsRel, SqRel, RMSE, RMSE-log and three delta accuracies are averaged over the sequence.  This module
+the ratio of the medians, and AbsRel, SqRel, RMSE, RMSE-log and three delta accuracies are averaged over the sequence.  evaluate_depth
 computes the same numbers with one call of bs_depth_metrics (include/bodyslam_hip.h) over depth maps that can stay in device memory
-(SequenceResult.depth_u16).  There is no CPU fallback: without a GPU the call raises BodySlamHipError.
+(SequenceResult.depth_u16).
+
+Trajectories.  The reference judges its pose module by MPEM_Metrics.compute_pose_metrics (EVALUATION/evaluation_metrics.py:136-165): evo's
+align_origin, align(correct_scale=True), then ATE, RTE and RRE; while training it monitors its own compute_ARE_and_ATE /
+compute_RRE_and_RTE (MPEM/training_utils.py:473-585).  evaluate_trajectory computes either with one call of bs_trajectory_metrics over
+poses that can stay in device memory (SequenceResult.g_abs); similarity_transform is the Umeyama fit on its own (bs_similarity_fit).
+
+There is no CPU fallback: without a GPU the calls raise BodySlamHipError.
 """
 from __future__ import annotations
 
@@ -12,7 +19,7 @@ import csv
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -178,3 +185,248 @@ def evaluate_depth_files(pred_paths: Sequence[str], gt_paths: Sequence[str], pro
     if results_dir is not None:
         res.write_csv(results_dir)
     return res
+
+
+# ---- trajectories -----------------------------------------------------------------------------------------------------------------------
+TRAJECTORY_PROTOCOLS = {"evo": L.TRAJ_EVO, "training": L.TRAJ_TRAINING}
+STAT_NAMES = ("rmse", "mean", "std", "min", "max")
+_TRAJ_STATUS = {L.TRAJ_DEGENERATE: "degenerate alignment (fewer than two singular values of the covariance above eps, or no spread / no "
+                                   "translation in the prediction; evo raises here)",
+                L.TRAJ_TOO_SHORT: "fewer than delta + 1 poses", L.TRAJ_BAD_OFFSETS: "bad offsets"}
+
+
+@dataclass
+class ErrorStats:
+    """The statistics of one error over each sequence, float64 [S] each; std is the population std (np.std)."""
+    rmse: np.ndarray
+    mean: np.ndarray
+    std: np.ndarray
+    min: np.ndarray
+    max: np.ndarray
+
+
+@dataclass
+class TrajectoryMetrics:
+    """Per sequence: ate, are, rte, rre (ErrorStats); the applied scale [S], rotation [S, 3, 3], translation [S, 3]; n_poses and
+    n_pairs [S].  Protocol "evo": ATE and RTE in the units of the ground truth, ARE and RRE in degrees; "training": radians."""
+    ate: ErrorStats
+    are: ErrorStats
+    rte: ErrorStats
+    rre: ErrorStats
+    scale: np.ndarray
+    rotation: np.ndarray
+    translation: np.ndarray
+    n_poses: np.ndarray
+    n_pairs: np.ndarray
+    protocol: str = "evo"
+
+    def __len__(self) -> int:
+        return len(self.scale)
+
+    def as_reference_dict(self, i: int = 0) -> Dict[str, Tuple[float, float]]:
+        """{"ATE": (rmse, std), "RTE": (rmse, std), "RRE": (rmse, std)} of sequence i, what compute_pose_metrics returns
+        (evaluation_metrics.py:159-165), as Python floats."""
+        return {k: (float(e.rmse[i]), float(e.std[i])) for k, e in (("ATE", self.ate), ("RTE", self.rte), ("RRE", self.rre))}
+
+    def write_csv(self, path: str, i: int = 0) -> str:
+        """The Metric,Value file of MPEM_eval.py:274-280 for sequence i: csv.DictWriter rows whose Value is the (rmse, std) tuple.  The
+        tuple is written as Python floats: under numpy 2 the reference's own tuple of numpy scalars prints as
+        "(np.float64(...), np.float64(...))", under numpy 1 as the plain numbers written here."""
+        with open(path, "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=["Metric", "Value"])
+            w.writeheader()
+            for k, v in self.as_reference_dict(i).items():
+                w.writerow({"Metric": k, "Value": v})
+        return path
+
+
+def _metrics_from_records(rec: np.ndarray, protocol: str) -> TrajectoryMetrics:
+    def st(base):
+        return ErrorStats(*(rec[:, base + j].copy() for j in range(5)))
+    return TrajectoryMetrics(ate=st(16), are=st(21), rte=st(26), rre=st(31), scale=rec[:, 3].copy(), rotation=rec[:, 4:13].reshape(-1, 3, 3).copy(),
+                             translation=rec[:, 13:16].copy(), n_poses=rec[:, 0].astype(np.int64), n_pairs=rec[:, 1].astype(np.int64),
+                             protocol=protocol)
+
+
+def _as_poses(x, what: str) -> torch.Tensor:
+    """-> float64 torch tensor [N, 16] (4x4 row-major) on whatever device x is on; ValueError on anything else"""
+    if isinstance(x, np.ndarray):
+        if x.dtype.kind != "f":
+            raise ValueError(f"{what}: dtype {x.dtype}, expected a floating-point array")
+        t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+    elif isinstance(x, torch.Tensor):
+        if not x.dtype.is_floating_point:
+            raise ValueError(f"{what}: dtype {x.dtype}, expected a floating-point tensor")
+        t = x.detach()
+    else:
+        raise ValueError(f"{what}: expected a numpy array or a torch tensor, got {type(x).__name__}")
+    shape = tuple(t.shape)
+    if t.dim() == 3 and shape[1:] == (4, 4):
+        return t.to(torch.float64).reshape(shape[0], 16).contiguous()          # (g_abs itself when it is fp64 and contiguous: no copy)
+    if (t.dim() == 3 and shape[1:] == (3, 4)) or (t.dim() == 2 and shape[1] == 12):
+        full = torch.zeros(shape[0], 16, dtype=torch.float64, device=t.device)
+        full[:, :12] = t.reshape(shape[0], 12)
+        full[:, 15] = 1.0
+        return full
+    raise ValueError(f"{what}: shape {shape}, expected [N, 4, 4], [N, 3, 4] or [N, 12]")
+
+
+def _check_trajectory_args(protocol, delta):
+    if protocol not in TRAJECTORY_PROTOCOLS:
+        raise ValueError(f"unknown protocol {protocol!r}: one of {sorted(TRAJECTORY_PROTOCOLS)}")
+    if isinstance(delta, bool) or not isinstance(delta, (int, np.integer)) or delta < 1:
+        raise ValueError(f"delta {delta!r}: expected an integer >= 1")
+
+
+def evaluate_trajectory(pred, gt, protocol: str = "evo", delta: int = 1, all_pairs: bool = False, align_origin: bool = True,
+                        align: bool = True, correct_scale: bool = True) -> TrajectoryMetrics:
+    """Trajectory metrics of `pred` against `gt`.
+
+    pred, gt: poses as [N, 4, 4], [N, 3, 4] or [N, 12] (a KITTI row per pose), or lists of such for a ragged batch of sequences; torch
+    tensors (device or host) or numpy arrays.  A float64 [N, 4, 4] device tensor (SequenceResult.g_abs) is read where it lies; host
+    inputs are uploaded once.  Nothing is written to the inputs (the reference's compute_ARE_and_ATE scales its predictions in place).
+    protocol "evo": the reference's evaluation -- align_origin, then the similarity alignment (align, correct_scale), then ATE, ARE, RTE,
+    RRE over the pose pairs (i, i + delta), i = 0, delta, 2 delta, ... (every i with all_pairs); angles in degrees.  Restated from evo's
+    published definitions (include/bodyslam_hip.h spells them out); parity with evo itself is unpinned.
+    protocol "training": the reference's training monitors -- the least-squares scale, no alignment (the four flags are not used), every
+    i < n - delta a pair, angles in radians.
+    Raises ValueError naming the sequence for a degenerate alignment (evo raises there too) or a sequence shorter than delta + 1.
+    Degenerate is evo's absolute criterion, fewer than two singular values of the covariance above eps = 2.2e-16; round-off leaves about
+    1e-16 of the largest in place of a vanishing one, so a collinear path with steps of metres sits at the threshold and may pass, in evo as
+    here.  Do not rely on it to detect collinear paths.
+    """
+    _check_trajectory_args(protocol, delta)
+    batched = isinstance(pred, (list, tuple))
+    if batched != isinstance(gt, (list, tuple)):
+        raise ValueError("pred and gt: both a list of sequences or both one sequence")
+    preds, gts = (list(pred), list(gt)) if batched else ([pred], [gt])
+    if len(preds) != len(gts) or not preds:
+        raise ValueError(f"{len(preds)} predicted and {len(gts)} ground-truth sequences: expected the same, non-zero number")
+    P = [_as_poses(x, f"pred[{i}]") for i, x in enumerate(preds)]
+    G = [_as_poses(x, f"gt[{i}]") for i, x in enumerate(gts)]
+    for i, (a, b) in enumerate(zip(P, G)):
+        if a.shape[0] != b.shape[0]:
+            raise ValueError(f"sequence {i}: {a.shape[0]} predicted and {b.shape[0]} ground-truth poses")
+        if a.shape[0] < delta + 1:
+            raise ValueError(f"sequence {i}: {a.shape[0]} poses, fewer than delta + 1 = {delta + 1}")
+    lengths = [int(a.shape[0]) for a in P]
+    if sum(lengths) >= 2 ** 31:
+        raise ValueError(f"{sum(lengths)} poses in all: the offsets are int32")
+    cuda = [t.device for t in P + G if t.is_cuda]
+    if not torch.cuda.is_available():
+        L.init(0)                              # raises BodySlamHipError: no CPU fallback
+    dev = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
+    flags = ((L.TRAJ_ALIGN_ORIGIN if align_origin else 0) | (L.TRAJ_ALIGN if align else 0) | (L.TRAJ_CORRECT_SCALE if correct_scale else 0) |
+             (L.TRAJ_ALL_PAIRS if all_pairs else 0))
+    with torch.cuda.device(dev):
+        L.init(dev.index)
+        P = [t.to(dev) for t in P]
+        G = [t.to(dev) for t in G]
+        p_all = P[0] if len(P) == 1 else torch.cat(P)
+        g_all = G[0] if len(G) == 1 else torch.cat(G)
+        offsets = torch.tensor(np.concatenate([[0], np.cumsum(lengths)]), dtype=torch.int32).to(dev)
+        out = torch.empty(len(lengths), L.TRAJ_FIELDS, dtype=torch.float64, device=dev)
+        L.trajectory_metrics(g_all, p_all, offsets, TRAJECTORY_PROTOCOLS[protocol], int(delta), flags, out)
+        rec = out.cpu().numpy()
+    for i in range(len(lengths)):
+        status = int(rec[i, 2])
+        if status != L.TRAJ_OK:
+            raise ValueError(f"sequence {i}: {_TRAJ_STATUS.get(status, f'status {status}')}")
+    return _metrics_from_records(rec, protocol)
+
+
+def read_kitti_poses(path: str, project_so3: bool = False) -> np.ndarray:
+    """A KITTI pose file -> float64 [N, 4, 4]: 12 numbers per line, the top three rows of a pose (what save_poses_as_kitti writes and
+    evo's read_kitti_poses_file reads).  project_so3: each rotation block goes through ensure_so3_v2 first, the reference's correct_poses
+    for trajectories of other methods (EVALUATION/compute_pose_metrics_for_competitor.py:31-62); that runs on the device, one call and
+    read-back per pose (slow for many thousands of poses)."""
+    rows = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            tok = line.split()
+            if not tok:
+                continue
+            if len(tok) != 12:
+                raise ValueError(f"{path}:{ln}: {len(tok)} numbers, expected 12")
+            try:
+                rows.append([float(v) for v in tok])
+            except ValueError:
+                raise ValueError(f"{path}:{ln}: not a number in {line.strip()!r}") from None
+    if not rows:
+        raise ValueError(f"{path}: no poses")
+    T = np.zeros((len(rows), 4, 4), np.float64)
+    T[:, :3, :] = np.asarray(rows, np.float64).reshape(-1, 3, 4)
+    T[:, 3, 3] = 1.0
+    if project_so3:
+        from .geom3d import ensure_so3_v2
+        for i in range(len(T)):
+            T[i, :3, :3] = ensure_so3_v2(T[i, :3, :3])
+    return T
+
+
+def evaluate_trajectory_files(pred_paths, gt_paths, protocol: str = "evo", delta: int = 1, all_pairs: bool = False, align_origin: bool = True,
+                              align: bool = True, correct_scale: bool = True, project_so3: bool = False,
+                              results_dir: Optional[str] = None) -> TrajectoryMetrics:
+    """KITTI pose files, one (prediction, GT) pair per sequence, in one device call, as compute_metrics walks a dataset
+    (MPEM_eval.py:255-280); a single path each is one sequence.  With results_dir, sequence i's Metric,Value file is written there under
+    the prediction file's base name + ".csv"."""
+    if isinstance(pred_paths, (str, os.PathLike)):
+        pred_paths, gt_paths = [pred_paths], [gt_paths]
+    pred_paths, gt_paths = [os.fspath(q) for q in pred_paths], [os.fspath(q) for q in gt_paths]
+    if len(pred_paths) != len(gt_paths) or not pred_paths:
+        raise ValueError(f"{len(pred_paths)} predictions and {len(gt_paths)} GT files: expected the same, non-zero number")
+    _check_trajectory_args(protocol, delta)
+    preds = [read_kitti_poses(q, project_so3=project_so3) for q in pred_paths]
+    gts = [read_kitti_poses(q) for q in gt_paths]
+    res = evaluate_trajectory(preds, gts, protocol=protocol, delta=delta, all_pairs=all_pairs, align_origin=align_origin, align=align,
+                              correct_scale=correct_scale)
+    if results_dir is not None:
+        os.makedirs(results_dir, exist_ok=True)
+        for i, q in enumerate(pred_paths):
+            res.write_csv(os.path.join(results_dir, os.path.splitext(os.path.basename(q))[0] + ".csv"), i)
+    return res
+
+
+def _as_points(x, what: str) -> torch.Tensor:
+    if isinstance(x, np.ndarray):
+        if x.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{what}: dtype {x.dtype}, expected float32 or float64")
+        t = torch.from_numpy(np.ascontiguousarray(x))
+    elif isinstance(x, torch.Tensor):
+        if x.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{what}: dtype {x.dtype}, expected torch.float32 or torch.float64")
+        t = x.detach()
+    else:
+        raise ValueError(f"{what}: expected a numpy array or a torch tensor, got {type(x).__name__}")
+    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError(f"{what}: shape {tuple(t.shape)}, expected a non-empty [n, 3]")
+    return t
+
+
+def similarity_fit_record(source, target) -> np.ndarray:
+    """The 16 doubles of bs_similarity_fit (include/bodyslam_hip.h): R (9), s, t (3), sigma_x, singular values above eps, n."""
+    a, b = _as_points(source, "source"), _as_points(target, "target")
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"source shape {tuple(a.shape)} and target shape {tuple(b.shape)} differ")
+    if a.dtype != b.dtype:
+        raise ValueError(f"source dtype {a.dtype} and target dtype {b.dtype} differ")
+    cuda = [t.device for t in (a, b) if t.is_cuda]
+    if not torch.cuda.is_available():
+        L.init(0)                              # raises BodySlamHipError: no CPU fallback
+    dev = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        L.init(dev.index)
+        a, b = a.to(dev).contiguous(), b.to(dev).contiguous()
+        ws = torch.empty(L.SIMILARITY_FIT_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
+        out = torch.empty(16, dtype=torch.float64, device=dev)
+        L.similarity_fit(a, b, ws, out)
+        return out.cpu().numpy()
+
+
+def similarity_transform(source, target) -> Tuple[np.ndarray, float, np.ndarray]:
+    """The similarity (R [3, 3], s, t [3]) with target ~ s R source + t in the least-squares sense (Umeyama), over [n, 3] point sets:
+    device or host, fp32 or fp64, arithmetic in fp64 on the device.  What the reference's estimate_similarity_transformation computes
+    (3DM/slam_utils.py:138-169; bodyslam_amd.slam_utils carries its [3, n] signature).  Like the reference it raises nothing for a
+    degenerate point set; similarity_fit_record returns the rank next to the fit."""
+    r = similarity_fit_record(source, target)
+    return r[:9].reshape(3, 3).copy(), float(r[9]), r[10:13].copy()

@@ -27,7 +27,7 @@ typedef enum {
     BS_ERR_NOT_INIT = -3
 } bs_status;
 
-enum { BS_F32 = 0, BS_F16 = 1, BS_BF16 = 2 };
+enum { BS_F32 = 0, BS_F16 = 1, BS_BF16 = 2, BS_F64 = 3 /* bs_similarity_fit only */ };
 /* BS_ACT_SOFTPLUS: torch.nn.Softplus(beta = 1, threshold = 20) through libm (log1pf(expf(x))), what the oracle computes.
  * BS_ACT_SOFTPLUS_FAST: the same function on v_exp / v_log (relative error <= 4e-6): the attractor MLPs only, whose epilogue was bound by
  * libm's arithmetic and whose inputs are 16-bit hidden units anyway; the seed regressors (bin start values) and the reference
@@ -562,6 +562,55 @@ enum { BS_DEPTH_SCALE_MEDIAN = 0, BS_DEPTH_SCALE_FIXED = 1 };
 int64_t bs_depth_metrics_workspace(int32_t B, int32_t H, int32_t W);
 int bs_depth_metrics(const uint16_t* pred, const uint16_t* gt, int32_t B, int32_t H, int32_t W, double gt_lo, double gt_hi, int32_t scale_mode,
                      double scale, void* workspace, int64_t workspace_bytes, double* out, void* stream);
+
+/* ---- trajectory evaluation with the reference's MPEM metrics ------------------------------------------------------------------------
+ * bs_similarity_fit replaces estimate_similarity_transformation (BodySLAM_not_refactored/3DM/slam_utils.py:138-169; evo's
+ * umeyama_alignment is the same arithmetic): the similarity (R, s, t) with target ~ s R source + t, Umeyama's least-squares fit.
+ *   source, target   [n, 3] row-major points (device), both BS_F32 or both BS_F64, 1 <= n <= 2^31 - 1; arithmetic in fp64
+ *   out              16 doubles (device): 0-8 R row-major, 9 s, 10-12 t, 13 sigma_x = mean |x - mean x|^2, 14 the number of singular values
+ *                    of Sxy = mean (y - mean y)(x - mean x)^T above DBL_EPSILON, 15 n.  S = diag(1, 1, -1) when det(Sxy) < 0, as the
+ *                    reference writes it; with exactly two singular values above DBL_EPSILON (planar points), where that determinant is
+ *                    round-off, evo's det(U) det(V) < 0 on a completed U: R is then the proper rotation.  Fewer than two (or sigma_x = 0):
+ *                    the fit is degenerate and R, s, t mean nothing
+ *   workspace        BS_SIMILARITY_FIT_WORKSPACE_BYTES of device memory, reused across calls on one stream
+ * Two passes over the points (means, then moments about them), each a grid that writes per-block partials, each followed by a
+ * one-block kernel that adds the partials in block order: four launches on `stream`, no atomics, the same bits in every run.
+ *
+ * bs_trajectory_metrics replaces MPEM_Metrics.compute_pose_metrics (EVALUATION/evaluation_metrics.py:136-165, which goes through evo) and
+ * TrainingLoss.compute_scale_factor / compute_ARE_and_ATE / compute_RRE_and_RTE (MPEM/training_utils.py:473-585) for S trajectory pairs.
+ *   gt, pred      fp64 [total_poses, 16] (device): 4x4 row-major poses, pair p being rows offsets[p] .. offsets[p + 1] - 1 of both (the
+ *                 layout of bs_pose_chain's g_abs); the bottom row of a pose is not read.  Neither array is written
+ *   offsets       int32 [S + 1] (device), non-decreasing, offsets[S] <= total_poses
+ *   protocol      BS_TRAJ_EVO (Q = gt, P = pred; restated from evo's published definitions):
+ *                   BS_TRAJ_ALIGN_ORIGIN   P_i <- Q_0 P_0^-1 P_i
+ *                   BS_TRAJ_ALIGN / BS_TRAJ_CORRECT_SCALE   (R, s, t) = the similarity fit of the positions of P to those of Q (s = 1
+ *                                          without CORRECT_SCALE; R = I, t = 0 without ALIGN); trans P_i <- s trans P_i, then P_i <- [R|t] P_i
+ *                   ATE_i = |trans Q_i - trans P_i|; ARE_i = the angle of Q_i^-1 P_i in degrees; over the pairs (i, i + delta),
+ *                   i = 0, delta, 2 delta, ... (every i with BS_TRAJ_ALL_PAIRS): E = (Q_i^-1 Q_j)^-1 (P_i^-1 P_j), RTE = |trans E|,
+ *                   RRE = the angle of rot E in degrees.  Inverses are [R^T | -R^T t]; angles are acos(clip((tr - 1) / 2, -1, 1))
+ *                 BS_TRAJ_TRAINING (flags are ignored, every i < n - delta is a pair):
+ *                   s = sum trans Q_i . trans P_i / sum |trans P_i|^2; ATE_i = |trans Q_i - s trans P_i|; ARE_i = the angle of
+ *                   rot Q_i rot P_i^T in radians; RTE / RRE: the same two errors between Q_i^-1 Q_j and P_i^-1 P_j of the unscaled poses
+ *                   (general inverses, as np.linalg.inv)
+ *   out           fp64 [S, BS_TRAJ_FIELDS] (device), per pair: 0 n, 1 the number of pose pairs, 2 status, 3 s, 4-12 R row-major, 13-15 t,
+ *                 then rmse, mean, std (population), min, max of ATE (16-20), ARE (21-25), RTE (26-30), RRE (31-35); 36 sigma_x (training:
+ *                 sum |trans P_i|^2), 37 singular values above DBL_EPSILON, 38-39 zero.  Status BS_TRAJ_DEGENERATE (fewer than two such
+ *                 singular values or sigma_x = 0, where evo raises; training: sum |trans P_i|^2 = 0), BS_TRAJ_TOO_SHORT (n < delta + 1) or
+ *                 BS_TRAJ_BAD_OFFSETS (the pair's offsets leave [0, total_poses]; nothing of it is read): fields 3-35 are NaN
+ * The degenerate criterion is evo's absolute one.  The round-off that stands in for a vanishing singular value is about 1e-16 of the largest,
+ * so a collinear path whose covariance is of order 1 (steps of metres) sits at the threshold and may report BS_TRAJ_OK, in evo as here: the
+ * status is no collinearity test (field 37 and field 36 are there for a caller's own).
+ * One launch on `stream` for any S (one block per pair, which walks its poses in strided loops), no workspace, no allocation, no
+ * synchronisation.  A pair's record has the same bits in every run, alone or at any position of any batch. */
+enum { BS_TRAJ_EVO = 0, BS_TRAJ_TRAINING = 1 };
+enum { BS_TRAJ_ALIGN_ORIGIN = 1, BS_TRAJ_ALIGN = 2, BS_TRAJ_CORRECT_SCALE = 4, BS_TRAJ_ALL_PAIRS = 8 };
+enum { BS_TRAJ_OK = 0, BS_TRAJ_DEGENERATE = 1, BS_TRAJ_TOO_SHORT = 2, BS_TRAJ_BAD_OFFSETS = 3 };
+#define BS_TRAJ_FIELDS 40
+#define BS_SIMILARITY_FIT_WORKSPACE_BYTES 131136
+int bs_similarity_fit(const void* source, const void* target, int64_t n, int32_t dtype, void* workspace, int64_t workspace_bytes, double* out,
+                      void* stream);
+int bs_trajectory_metrics(const double* gt, const double* pred, const int32_t* offsets, int32_t S, int64_t total_poses, int32_t protocol,
+                          int32_t delta, int32_t flags, double* out, void* stream);
 
 /* ---- engine files: the forward of a whole model for a host without Python ------------------------------------
  * The reference's hosts are DepthEstimator.infer_depth_map (BodySLAM_Refactored/src/depth_estimation/interface.py:39-45) and
