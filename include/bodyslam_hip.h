@@ -612,6 +612,60 @@ int bs_similarity_fit(const void* source, const void* target, int64_t n, int32_t
 int bs_trajectory_metrics(const double* gt, const double* pred, const int32_t* offsets, int32_t S, int64_t total_poses, int32_t protocol,
                           int32_t delta, int32_t flags, double* out, void* stream);
 
+/* ---- sparse-feature scale path: ORB match displacement (N3, rgbd_odo = False) ---------------------------------------------------------
+ * The role of scaling_system.compute_scaling_factor (BodySLAM_not_refactored/3DM/scaling_system.py:107-137), which
+ * VO.estimate_relative_pose_between calls with rgbd_odo = False (3DM/visual_odometry.py:70-79): cv2.ORB_create() on both frames,
+ * BFMatcher(NORM_HAMMING, crossCheck = True), the matches sorted by distance, associate_depth twice, calculate_displacements, the mean.
+ * OpenCV is not vendored: ORB (Rublee et al. 2011), FAST-9/16 (Rosten & Drummond 2006), the Harris measure and BRIEF's test pairs
+ * (Calonder et al. 2010) are restated from their publications with cv2.ORB_create()'s default parameters in tests/_orb_ref.py, which also
+ * lists every departure from OpenCV (test pairs, fixed-point resize, 30 orientation bins, tie rules); parity with OpenCV is UNPINNED.
+ * What follows the match is the reference's own code and is restated with its quirks (pinned: tests/golden/sparse_scale.npz).
+ * Every entry takes `batch` frames and runs each of its stages as ONE launch over them; a frame's result does not depend on the batch.
+ *   levels      host int32 [n_levels, 3] = (W_l, H_l, offset_l): the levels of one frame lie in a flat byte buffer of `stride` bytes per
+ *               frame; offsets and stride are multiples of 16 and a level is followed by at least its padding to 16 bytes
+ *   bs_orb_pyramid        color u8 [batch, H, W, 3] (RGB; bgr != 0: BGR) -> grey = (4899 R + 9617 G + 1868 B + 8192) >> 14 at level 0,
+ *                         level l from level l - 1 by a bilinear resize with 11-bit fixed-point weights (pixel centres aligned), and
+ *                         smooth = [1 6 15 20 15 6 1]^2 / 4096 of every level, reflect-101, rounded once
+ *   bs_orb_fast           score u8: the FAST-9/16 score (the largest threshold at which the pixel is still a corner, >= 20) where the
+ *                         pixel beats its 8 neighbours strictly and lies 31 pixels inside the level, else 0; hist int32
+ *                         [batch, BS_ORB_MAX_LEVELS, 256]: the histogram of the non-zero scores (zeroed by the call)
+ *   bs_orb_select         per level the best 2 n_l by score, of those the best n_l by Harris response (7 x 7 block of 3 x 3 Sobel
+ *                         products in int64, det - 0.04 tr^2 in fp64); every ranking key is (value descending, row-major pixel index
+ *                         ascending).  keypoints int32 [batch, BS_ORB_MAX_FEATURES, 8] = (level, x, y, score, m10, m01, bin, 0), fields
+ *                         0-3 written here; response fp64 [batch, BS_ORB_MAX_FEATURES]; counts int32 [batch, BS_ORB_MAX_LEVELS + 1] =
+ *                         keypoints per level and their sum.  features_per_level: host int32 [n_levels], each <= 128, sum <= 500
+ *   bs_orb_describe       fields 4-6: the moments over the radius-15 disc of the grey level and the first maximum of
+ *                         m10 cos_sin[k] + m01 cos_sin[30 + k] over the 30 bins; pt fp32 [batch, BS_ORB_MAX_FEATURES, 2] =
+ *                         (x level_scale[l], y level_scale[l]); desc u32 [batch, BS_ORB_MAX_FEATURES, 8]: bit i = smooth(p + a_i) <
+ *                         smooth(p + b_i) with (a_i, b_i) = pattern[bin][i] (int8 [30, 256, 4] = x1, y1, x2, y2, device; |offset| <= 22)
+ *                         level_scale: host doubles; cos_sin: 60 device doubles
+ *   bs_orb_match          pair p = (query: frame p, train: frame p + 1), p < batch - 1: best train per query and best query per train
+ *                         (the lowest index among equals), cross-check, stable sort by distance.  matches int32
+ *                         [batch - 1, BS_ORB_MAX_FEATURES, 4] = (queryIdx, trainIdx, distance, 0); match_counts int32 [batch - 1]
+ *   bs_orb_displacement   depth fp32 [batch, H, W]; K = (fx, fy, cx, cy) host doubles.  BS_ORB_ASSOC_REFERENCE: the reference's two
+ *                         associate_depth calls (the second indexes the current frame's keypoints by queryIdx) and the zip of the two
+ *                         independently filtered lists; BS_ORB_ASSOC_MATCHED: depth of the current frame at the matched keypoint,
+ *                         pairs kept aligned.  out fp64 [batch - 1, BS_ORB_OUT_FIELDS]: 0-2 the mean of pixel_to_3d(current) -
+ *                         pixel_to_3d(previous) summed in list order (NaN without a pair), 3 / 4 keypoints of the previous / current
+ *                         frame, 5 matches, 6 / 7 associations of the previous / current side, 8 pairs used */
+#define BS_ORB_MAX_FEATURES 500
+#define BS_ORB_MAX_LEVELS 8
+#define BS_ORB_OUT_FIELDS 9
+enum { BS_ORB_ASSOC_REFERENCE = 0, BS_ORB_ASSOC_MATCHED = 1 };
+int bs_orb_pyramid(const uint8_t* color, int32_t batch, int32_t H, int32_t W, int32_t bgr, const int32_t* levels, int32_t n_levels,
+                   int64_t stride, uint8_t* grey, uint8_t* smooth, void* stream);
+int bs_orb_fast(const uint8_t* grey, int32_t batch, int32_t H, int32_t W, const int32_t* levels, int32_t n_levels, int64_t stride,
+                uint8_t* score, int32_t* hist, void* stream);
+int bs_orb_select(const uint8_t* grey, const uint8_t* score, const int32_t* hist, int32_t batch, int32_t H, int32_t W, const int32_t* levels,
+                  int32_t n_levels, int64_t stride, const int32_t* features_per_level, int32_t* keypoints, double* response, int32_t* counts,
+                  void* stream);
+int bs_orb_describe(const uint8_t* grey, const uint8_t* smooth, int32_t batch, int32_t H, int32_t W, const int32_t* levels, int32_t n_levels,
+                    int64_t stride, const double* level_scale, const double* cos_sin, const int8_t* pattern, int32_t* keypoints,
+                    const int32_t* counts, float* pt, uint32_t* desc, void* stream);
+int bs_orb_match(const uint32_t* desc, const int32_t* counts, int32_t batch, int32_t* matches, int32_t* match_counts, void* stream);
+int bs_orb_displacement(const float* pt, const int32_t* counts, const int32_t* matches, const int32_t* match_counts, const float* depth,
+                        int32_t batch, int32_t H, int32_t W, const double* K, int32_t mode, double* out, void* stream);
+
 /* ---- engine files: the forward of a whole model for a host without Python ------------------------------------
  * The reference's hosts are DepthEstimator.infer_depth_map (BodySLAM_Refactored/src/depth_estimation/interface.py:39-45) and
  * MPEMInterface.infer_relative_pose_between (BodySLAM_not_refactored/MPEM/mpem_interface.py:61-99), both Python.  A plan -- the launch
