@@ -126,6 +126,15 @@ class BodySlamPipeline:
         # (the reference never adds any: slam.py:30,80)
         self.posegraph_every = 0
         self.loop_closures = []
+        # the reference's names for the step it declares and never wrote (slam.py:30,41,42; :79-80 calls an undefined _loop_closure):
+        # with perform_loop_closure, run_slam_loop makes every num_closure-th frame a keyframe and first looks for a closure of it
+        # against the older keyframes (loop_closure.LoopCloser).  The edges found join the graph as uncertain edges and are listed in
+        # loop_closures_found.  loop_closure_options: LoopCloser's keyword arguments.  Off: nothing runs and no LoopCloser is built.
+        self.perform_loop_closure = False
+        self.num_closure = 10000
+        self.global_key_frame_indices = []
+        self.loop_closures_found = []
+        self.loop_closure_options = {}
         self.K, self.depth_scale, self.depth_trunc, self.flip = tuple(K), depth_scale, depth_trunc, flip_aug
         self.zoe = ZoeDepthEngine(zoe_weights, zoe_cfg, dtype=dtype, device=device, target_hw=target_hw, precision=precision)
         self.precision = precision
@@ -289,7 +298,11 @@ class BodySlamPipeline:
         if tsdf is not None and tsdf_factory is None:
             tsdf_factory = lambda: TSDF(tsdf.voxel_length, tsdf.sdf_trunc, tsdf.res, tsdf.stride, device=self.dev.index or 0,
                                         slab_bytes=tsdf.slab_units * tsdf.unit_floats * 4, max_units=tsdf.max_units)
-        state = {"tsdf": tsdf}
+        state = {"tsdf": tsdf, "closer": None}
+        if self.perform_loop_closure:
+            from .loop_closure import LoopCloser
+            state["closer"] = LoopCloser(tuple(float(v) for v in self.K), device=self.dev.index or 0, **self.loop_closure_options)
+            self.global_key_frame_indices, self.loop_closures_found = [], []
 
         def tsdf_depth(j0, j1):
             """pseudo-RGBD depth of the map step (slam_utils.py:212-220): depth / depth_scale, values >= depth_trunc dropped"""
@@ -414,6 +427,8 @@ class BodySlamPipeline:
                     pose = np.identity(4, dtype=np.float64)
                     extr.append(pose)
                     pg.add_node(pose)
+                    if state["closer"] is not None:
+                        self._closure_step(state["closer"], 0, fr_dev, depth_all, pg)
                     if state["tsdf"] is not None:
                         actions.append(("int", 0, pose))
                 else:
@@ -426,6 +441,8 @@ class BodySlamPipeline:
                     for (s_, t_, Tl, info) in self.loop_closures:               # (the reference never adds any: slam.py:30,80)
                         if max(s_, t_) == i:
                             pg.add_edge(Tl, s_, t_, True, info)
+                    if state["closer"] is not None and i % self.num_closure == 0:
+                        self._closure_step(state["closer"], i, fr_dev, depth_all, pg)
                     if every > 0 and i % every == 0:
                         before = [p_.copy() for p_ in extr]
                         pg.optimize()
@@ -455,6 +472,23 @@ class BodySlamPipeline:
                 for j in range(b1 - b0):
                     points.append((xyz[j, :c[j]].clone(), idx[j, :c[j]].clone()))
         self._extr_final = list(extr)
+
+    def _closure_step(self, closer, i, fr_dev, depth_all, pg) -> None:
+        """slam.py:79 (i % num_closure == 0): frame i becomes a keyframe; for i > 0 it is first looked up against the older keyframes with
+        its colour and the metric depth the loop holds (raw / depth_scale, not truncated), and what is found joins the graph as
+        uncertain edges"""
+        depth_m = L.depth_u16_to_m(depth_all[i:i + 1].contiguous(), self.depth_scale, 3.0e38)[0]
+        reuse = False
+        if i > 0:
+            for (s_, t_, Tl, info) in closer.detect(i, fr_dev[i], depth_m):
+                pg.add_edge(Tl, s_, t_, True, info)
+                self.loop_closures_found.append((s_, t_, Tl, info))
+            reuse = closer.last_records is not None
+        if reuse:
+            closer.add_keyframe(i)                                              # the features detect extracted
+        else:
+            closer.add_keyframe(i, fr_dev[i], depth_m)
+        self.global_key_frame_indices.append(i)
 
     def fuse_vo(self, frames, depth_u16: torch.Tensor, t_rel: torch.Tensor) -> torch.Tensor:
         """visual_odometry.py:60-93 over the pairs (i-1, i) in order: returns t_rel with each translation replaced by the UKF state"""

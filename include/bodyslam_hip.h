@@ -666,6 +666,41 @@ int bs_orb_match(const uint32_t* desc, const int32_t* counts, int32_t batch, int
 int bs_orb_displacement(const float* pt, const int32_t* counts, const int32_t* matches, const int32_t* match_counts, const float* depth,
                         int32_t batch, int32_t H, int32_t W, const double* K, int32_t mode, double* out, void* stream);
 
+/* ---- loop closure: one frame against many keyframes, RANSAC rigid registration of the matched 3-D points --------------------------------
+ * The reference declares the step (3DM/slam.py:30,41,42: perform_loop_closure, num_closure, global_key_frame_indices) and calls an
+ * undefined self._loop_closure() (:79-80); nothing here is its code.  RANSAC (Fischler & Bolles 1981) over three-point Kabsch fits
+ * (Kabsch 1976; Arun et al. 1987), restated from the publications; the information matrix is the form of Open3D's
+ * get_information_matrix_from_point_clouds, restated from its documentation: sum G^T G, G = [ -[q]x | I3 ] over the inlier points q of
+ * the train frame, rotation parameters first.  Parity with Open3D is UNPINNED.  The statement is tests/_loop_closure_ref.py.
+ *   bs_orb_lift           xyz fp64 [batch, BS_ORB_MAX_FEATURES, 4] = (x, y, z, valid 0.0 / 1.0) of every keypoint: depth fp32 [batch, H, W]
+ *                         at (int(y), int(x)) as bs_orb_displacement reads it; valid = inside the image, depth != 0 and finite;
+ *                         x = (u - cx) depth / fx, y = (v - cy) depth / fy, z = depth in fp64.  K = (fx, fy, cx, cy) host doubles.
+ *                         Invalid rows and rows behind the frame's count are zero.
+ *   bs_orb_match_pairs    bs_orb_match's match (the same device code) for P pairs = device int32 [P, 2] = (query frame, train frame),
+ *                         indices into desc / counts of n_frames frames; a pair with an index outside [0, n_frames) gets 0 matches.
+ *                         matches int32 [P, BS_ORB_MAX_FEATURES, 4], match_counts int32 [P].  bs_orb_match is pairs = (p, p + 1).
+ *   bs_loop_register      per pair, one block: (1) the matches with distance <= max_hamming whose two points are valid, in match
+ *                         order: C correspondences; C < max(3, min_matches) rejects.  (2) hypothesis h < n_hyp: three distinct
+ *                         indices i0 = r0 % C, i1 = r1 % (C - 1), i2 = r2 % (C - 2), each shifted past the earlier picks, with
+ *                         r_d = the high 32 bits of splitmix64's finaliser applied to
+ *                         (seed ^ pair * 0xD6E8FEB86659FD93) + 0x9E3779B97F4A7C15 * (3 h + d + 1)   (64-bit wrap-around);
+ *                         Kabsch in fp64; a sample whose summed 3 x 3 cross-covariance has a second singular value below 1e-12 m^2
+ *                         scores 0; score = #(|R p + t - q| < tau).  (3) the highest score wins, the lowest h among equals; a best
+ *                         score below 3 rejects.  (4) n_refit rounds of Kabsch over the inliers + recount, sums in a fixed order (no
+ *                         atomics: the same bits in every run); fewer than 3 inliers or a collinear inlier set rejects.
+ *                         records fp64 [P, BS_LOOP_FIELDS]: 0-15 T row-major (X_train = T X_query), 16 inliers, 17 C, 18 winning h,
+ *                         19 RMSE over the inliers, 20 status (1 registered, 0 rejected), 21 matches, 22-57 the information matrix
+ *                         row-major, 58-63 zero.  Rejected: T = identity, information zero, inliers 0, h = -1.
+ *                         mask int32 [P, BS_ORB_MAX_FEATURES]: 1 at the match rows that are inliers. */
+#define BS_LOOP_FIELDS 64
+int bs_orb_lift(const float* pt, const int32_t* counts, const float* depth, int32_t batch, int32_t H, int32_t W, const double* K, double* xyz,
+                void* stream);
+int bs_orb_match_pairs(const uint32_t* desc, const int32_t* counts, int32_t n_frames, const int32_t* pairs, int32_t P, int32_t* matches,
+                       int32_t* match_counts, void* stream);
+int bs_loop_register(const double* xyz, int32_t n_frames, const int32_t* pairs, int32_t P, const int32_t* matches, const int32_t* match_counts,
+                     int32_t max_hamming, double tau, int32_t n_hyp, int32_t n_refit, int32_t min_matches, uint64_t seed, double* records,
+                     int32_t* mask, void* stream);
+
 /* ---- engine files: the forward of a whole model for a host without Python ------------------------------------
  * The reference's hosts are DepthEstimator.infer_depth_map (BodySLAM_Refactored/src/depth_estimation/interface.py:39-45) and
  * MPEMInterface.infer_relative_pose_between (BodySLAM_not_refactored/MPEM/mpem_interface.py:61-99), both Python.  A plan -- the launch
