@@ -152,6 +152,12 @@ _SIGS = {
     "bs_orb_match_pairs": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_loop_register": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                          C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
+    # pose graph (csrc/posegraph.hip)
+    "bs_pg_linearise": [C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_double, C.c_int32] + [C.c_void_p] * 8,
+    "bs_pg_assemble": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5,
+    "bs_pg_solve": [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7,
+    "bs_pg_update": [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4,
 }
 EXPORTS = sorted(list(_SIGS) + ["bs_last_error"])
 
@@ -770,3 +776,61 @@ def trajectory_metrics(gt, pred, offsets, protocol, delta, flags, out):
     assert out.dtype == torch.float64 and tuple(out.shape) == (S, TRAJ_FIELDS) and out.is_contiguous()
     check(load_library().bs_trajectory_metrics(p(gt), p(pred), p(offsets), S, total, protocol, delta, flags, p(out), stream_ptr()),
           "bs_trajectory_metrics")
+
+
+PG_LINE_PROCESS, PG_SYSTEM = 1, 2
+PG_STAGE_SWEEP, PG_STAGE_REDUCED, PG_STAGE_DENSE_SOLVE, PG_STAGE_BACKSUB, PG_STAGE_ALL = 1, 2, 4, 8, 15
+PG_MAX_SEPARATORS, PG_NODE_WORKSPACE, PG_SLOT_FIELDS = 128, 114, 120
+
+
+def _f64(*ts):
+    for t in ts:
+        assert t is None or (t.dtype == torch.float64 and t.is_cuda and t.is_contiguous()), "fp64 contiguous device tensors"
+
+
+def _i32(*ts):
+    for t in ts:
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous(), "int32 contiguous device tensors"
+
+
+def pg_linearise(X, T, info, src, tgt, unc, mu, flags, lw, z, q, Hss, g, cterm, cost=None):
+    """X fp64 [N, 4, 4], T [E, 4, 4], info [E, 6, 6], src / tgt / unc int32 [E]; lw, q, cterm [E], z [E, 6], Hss [E, 6, 6], g [E, 6];
+    cost: fp64 [>= 1] or None (include/bodyslam_hip.h)"""
+    N, E = X.shape[0], src.numel()
+    _f64(X, T, info, lw, z, q, Hss, g, cterm, cost)
+    _i32(src, tgt, unc)
+    assert X.numel() == N * 16 and T.numel() == E * 16 and info.numel() == E * 36 and tgt.numel() == E and unc.numel() == E
+    assert lw.numel() == E and z.numel() == E * 6 and q.numel() == E and cterm.numel() == E
+    assert (Hss is None or Hss.numel() == E * 36) and (g is None or g.numel() == E * 6)
+    check(load_library().bs_pg_linearise(p(X), N, p(T), p(info), p(src), p(tgt), p(unc), E, float(mu), int(flags), p(lw), p(z), p(q), p(Hss), p(g),
+                                         p(cterm), p(cost), stream_ptr()), "bs_pg_linearise")
+
+
+def pg_assemble(Hss, g, row_ptr, adj, reference_node, D, b, Cc, maxes=None):
+    """row_ptr int32 [N + 1], adj int32 [nnz, 3]; D [N, 6, 6], b [N, 6], Cc [N, 6, 6]; maxes fp64 [>= 2] or None"""
+    N, E, nnz = row_ptr.numel() - 1, g.numel() // 6, adj.numel() // 3
+    _f64(Hss, g, D, b, Cc, maxes)
+    _i32(row_ptr, adj)
+    assert Hss.numel() == E * 36 and D.numel() == N * 36 and b.numel() == N * 6 and Cc.numel() == N * 36
+    check(load_library().bs_pg_assemble(p(Hss), p(g), E, N, p(row_ptr), p(adj), nnz, int(reference_node), p(D), p(b), p(Cc), p(maxes), stream_ptr()),
+          "bs_pg_assemble")
+
+
+def pg_solve(D, b, Cc, Hss, lam, segments, sep_node, node_slot, adjacent, long_edges, stages, node_ws, slots, M, vec, delta, sums=None):
+    """the plan arrays are int32 device tensors (posegraph.solve_plan); node_ws [N, PG_NODE_WORKSPACE], slots [max(n_segments, 1), PG_SLOT_FIELDS],
+    M [6 S, 6 S], vec [24 S], delta [N, 6]; sums fp64 [>= 2] or None"""
+    N, E, S = b.numel() // 6, Hss.numel() // 36, sep_node.numel()
+    nseg, nadj, nlong = segments.numel() // 2, adjacent.numel(), long_edges.numel() // 3
+    _f64(D, b, Cc, Hss, node_ws, slots, M, vec, delta, sums)
+    _i32(segments, sep_node, node_slot, adjacent, long_edges)
+    assert D.numel() == N * 36 and Cc.numel() == N * 36 and node_slot.numel() == N and delta.numel() == N * 6
+    assert node_ws.numel() >= N * PG_NODE_WORKSPACE and slots.numel() >= nseg * PG_SLOT_FIELDS and M.numel() >= 36 * S * S and vec.numel() >= 24 * S
+    check(load_library().bs_pg_solve(p(D), p(b), p(Cc), p(Hss), N, E, float(lam), p(segments), nseg, p(sep_node), S, p(node_slot), p(adjacent), nadj,
+                                     p(long_edges), nlong, int(stages), p(node_ws), p(slots), p(M), p(vec), p(delta), p(sums), stream_ptr()), "bs_pg_solve")
+
+
+def pg_update(X, delta, Xn, terms, xnorm2=None):
+    N = X.shape[0]
+    _f64(X, delta, Xn, terms, xnorm2)
+    assert X.numel() == N * 16 and Xn.numel() == N * 16 and delta.numel() == N * 6 and terms.numel() >= N
+    check(load_library().bs_pg_update(p(X), p(delta), N, p(Xn), p(terms), p(xnorm2), stream_ptr()), "bs_pg_update")

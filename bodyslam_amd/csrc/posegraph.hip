@@ -1,0 +1,571 @@
+// Pose-graph optimisation on the device: the four numerical pieces of PoseGraph._levenberg_marquardt
+// (bodyslam_amd/posegraph.py) -- edge linearisation with line processes, gather assembly of the block normal equations, the solve of
+// (H + lambda I) delta = b by one level of substructuring, the pose update -- in fp64.  The LM control flow stays on the host.
+//
+// No kernel here uses LDS: every 6 x 6 block lives in the registers (or the private memory) of the one lane that owns the edge, node or
+// segment, and the only cross-lane traffic is the __shfl_xor butterfly of the one-wave reductions.  DESIGN section 7's rule about LDS
+// gathers beside another stream's kernels therefore has nothing to apply to.  No floating-point atomics; every sum has a fixed order, so a
+// call gives the same bits in every run (the rule of trajectory_eval.hip and loop_closure.hip).
+//
+// The per-item arithmetic is __host__ __device__, so a host program that includes this file can run it over the items in a loop (how it was
+// checked against tests/_posegraph_solve_ref.py before it ran on a GPU).
+#include <math.h>
+
+#include "common.h"
+
+namespace bs {
+namespace {
+
+#define PG_HD __host__ __device__
+
+constexpr int PG_THREADS = 128;
+constexpr int PG_DENSE_THREADS = 1024;                 // stage B: one workgroup, one row of the reduced matrix per thread (6 S <= 768)
+constexpr int PG_NODE_WS = BS_PG_NODE_WORKSPACE;       // per interior node: L [36] | GU [36] | GF [36] | gb [6]
+constexpr int PG_SLOT = BS_PG_SLOT_FIELDS;             // per segment: Saa [36] | Sca [36] | Scc [36] | ra [6] | rc [6]
+
+// ---- 4 x 4 rigid transforms (row-major) ----------------------------------------------------------------------------------------------
+PG_HD inline void rigid_inv(const double* T, double* O) {           // [R | t]^-1 = [R^T | -R^T t]: closed form, the bottom row is not read
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) O[r * 4 + c] = T[c * 4 + r];
+        O[r * 4 + 3] = -(T[0 * 4 + r] * T[3] + T[1 * 4 + r] * T[7] + T[2 * 4 + r] * T[11]);
+    }
+    O[12] = 0.0, O[13] = 0.0, O[14] = 0.0, O[15] = 1.0;
+}
+
+PG_HD inline void mul4(const double* A, const double* B, double* C) {
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            double s = A[r * 4] * B[c];
+            for (int k = 1; k < 4; ++k) s += A[r * 4 + k] * B[k * 4 + c];
+            C[r * 4 + c] = s;
+        }
+}
+
+PG_HD inline void lin6(const double* M, double* z) {
+    z[0] = (M[9] - M[6]) / 2, z[1] = (M[2] - M[8]) / 2, z[2] = (M[4] - M[1]) / 2;
+    z[3] = M[3], z[4] = M[7], z[5] = M[11];
+}
+
+// G_i X for the six generators of oracle/posegraph_ref.py: a row selection
+PG_HD inline void gen_mul(int i, const double* X, double* O) {
+    for (int k = 0; k < 16; ++k) O[k] = 0.0;
+    const int a[6] = {1, 2, 0, 0, 1, 2};          // row of O that gets  -X[b]   (i < 3)  /  X[3]  (i >= 3)
+    const int b[6] = {2, 0, 1, 3, 3, 3};
+    for (int c = 0; c < 4; ++c) {
+        if (i < 3) {
+            O[a[i] * 4 + c] = -X[b[i] * 4 + c];
+            O[b[i] * 4 + c] = X[a[i] * 4 + c];
+        } else {
+            O[a[i] * 4 + c] = X[12 + c];
+        }
+    }
+}
+
+// ---- one edge ------------------------------------------------------------------------------------------------------------------------
+PG_HD inline void linearise_edge(int e, const double* X, int N, const double* T, const double* info, const int32_t* src, const int32_t* tgt,
+                                 const int32_t* unc, double mu, int flags, double* lw, double* z_out, double* q_out, double* Hss, double* g,
+                                 double* cterm) {
+    const int s = src[e], t = tgt[e];
+    double z[6], Ti[16], Xi[16], A[16], M[16];
+    if (s < 0 || s >= N || t < 0 || t >= N) {       // (the host checks the edges; nothing outside X is ever read)
+        for (int i = 0; i < 6; ++i) z_out[e * 6 + i] = 0.0;
+        q_out[e] = 0.0, cterm[e] = 0.0;
+        if (flags & BS_PG_LINE_PROCESS) lw[e] = 1.0;
+        if (flags & BS_PG_SYSTEM) {
+            for (int i = 0; i < 36; ++i) Hss[e * 36 + i] = 0.0;
+            for (int i = 0; i < 6; ++i) g[e * 6 + i] = 0.0;
+        }
+        return;
+    }
+    const double* Xs = X + (size_t)s * 16;
+    const double* L = info + (size_t)e * 36;
+    rigid_inv(T + (size_t)e * 16, Ti);
+    rigid_inv(X + (size_t)t * 16, Xi);
+    mul4(Ti, Xi, A);
+    mul4(A, Xs, M);
+    lin6(M, z);
+    double q = 0.0;
+    for (int i = 0; i < 6; ++i) {
+        double r = L[i * 6] * z[0];
+        for (int j = 1; j < 6; ++j) r += L[i * 6 + j] * z[j];
+        q += z[i] * r;
+    }
+    double l;
+    if (flags & BS_PG_LINE_PROCESS) {
+        l = 1.0;
+        if (unc[e]) {
+            const double w = mu / (mu + q);
+            l = w * w;
+        }
+        lw[e] = l;
+    } else {
+        l = lw[e];
+    }
+    for (int i = 0; i < 6; ++i) z_out[e * 6 + i] = z[i];
+    q_out[e] = q;
+    double c = l * q;
+    if (unc[e]) {
+        const double d = sqrt(l) - 1.0;
+        c += mu * (d * d);
+    }
+    cterm[e] = c;
+    if (!(flags & BS_PG_SYSTEM)) return;
+    double Js[36], JtW[36], GX[16], P[16], col[6];
+    for (int i = 0; i < 6; ++i) {                   // column i = lin6(A G_i X_s)
+        gen_mul(i, Xs, GX);
+        mul4(A, GX, P);
+        lin6(P, col);
+        for (int r = 0; r < 6; ++r) Js[r * 6 + i] = col[r];
+    }
+    for (int i = 0; i < 6; ++i)                     // Js^T (l Lambda)
+        for (int j = 0; j < 6; ++j) {
+            double a = Js[i] * (l * L[j]);
+            for (int r = 1; r < 6; ++r) a += Js[r * 6 + i] * (l * L[r * 6 + j]);
+            JtW[i * 6 + j] = a;
+        }
+    for (int i = 0; i < 6; ++i) {
+        for (int j = 0; j < 6; ++j) {
+            double a = JtW[i * 6] * Js[j];
+            for (int r = 1; r < 6; ++r) a += JtW[i * 6 + r] * Js[r * 6 + j];
+            Hss[(size_t)e * 36 + i * 6 + j] = a;
+        }
+        double a = JtW[i * 6] * z[0];
+        for (int r = 1; r < 6; ++r) a += JtW[i * 6 + r] * z[r];
+        g[(size_t)e * 6 + i] = a;
+    }
+}
+
+// ---- one node: gather over its incident edges (CSR, ascending edge index) ------------------------------------------------------------------
+// adj [nnz, 3] = (edge, the other endpoint, -1 when the node is the edge's source / +1 when its target)
+PG_HD inline void assemble_node(int n, int N, int E, const double* Hss, const double* g, const int32_t* row_ptr, const int32_t* adj, int nnz, int ref,
+                                double* D, double* b, double* Cc) {
+    double d[36], c[36], v[6];
+    for (int i = 0; i < 36; ++i) d[i] = 0.0, c[i] = 0.0;
+    for (int i = 0; i < 6; ++i) v[i] = 0.0;
+    int k0 = row_ptr[n], k1 = row_ptr[n + 1];
+    if (k0 < 0) k0 = 0;
+    if (k1 > nnz) k1 = nnz;
+    for (int k = k0; k < k1; ++k) {
+        const int e = adj[k * 3], o = adj[k * 3 + 1], sg = adj[k * 3 + 2];
+        if (e < 0 || e >= E) continue;
+        const double* h = Hss + (size_t)e * 36;
+        for (int i = 0; i < 36; ++i) d[i] += h[i];
+        for (int i = 0; i < 6; ++i) v[i] += sg < 0 ? -g[(size_t)e * 6 + i] : g[(size_t)e * 6 + i];
+        if (o == n + 1)
+            for (int i = 0; i < 36; ++i) c[i] += -h[i];
+    }
+    if (n == ref) {                                 // the reference node stays where it is: identity rows, zero right-hand side
+        for (int i = 0; i < 36; ++i) d[i] = (i % 7 == 0) ? 1.0 : 0.0;
+        for (int i = 0; i < 6; ++i) v[i] = 0.0;
+    }
+    if (n == ref || n + 1 == ref)
+        for (int i = 0; i < 36; ++i) c[i] = 0.0;
+    for (int i = 0; i < 36; ++i) D[(size_t)n * 36 + i] = d[i], Cc[(size_t)n * 36 + i] = c[i];
+    for (int i = 0; i < 6; ++i) b[(size_t)n * 6 + i] = v[i];
+}
+
+// ---- 6 x 6 blocks ------------------------------------------------------------------------------------------------------------------------
+PG_HD inline void chol6(const double* A, double* L) {               // A = L L^T, L lower; a non-positive pivot gives NaN, which the host sees
+    for (int i = 0; i < 36; ++i) L[i] = 0.0;
+    for (int j = 0; j < 6; ++j) {
+        double s = A[j * 6 + j];
+        for (int k = 0; k < j; ++k) s -= L[j * 6 + k] * L[j * 6 + k];
+        const double d = sqrt(s);
+        L[j * 6 + j] = d;
+        for (int i = j + 1; i < 6; ++i) {
+            double a = A[i * 6 + j];
+            for (int k = 0; k < j; ++k) a -= L[i * 6 + k] * L[j * 6 + k];
+            L[i * 6 + j] = a / d;
+        }
+    }
+}
+
+PG_HD inline void lsolve6(const double* L, const double* B, int cols, double* Y) {     // Y = L^-1 B, B and Y [6, cols]
+    for (int c = 0; c < cols; ++c)
+        for (int i = 0; i < 6; ++i) {
+            double a = B[i * cols + c];
+            for (int k = 0; k < i; ++k) a -= L[i * 6 + k] * Y[k * cols + c];
+            Y[i * cols + c] = a / L[i * 6 + i];
+        }
+}
+
+PG_HD inline void atb6(const double* A, const double* B, int cols, double* C) {        // C = A^T B, A [6, 6], B and C [6, cols]
+    for (int i = 0; i < 6; ++i)
+        for (int c = 0; c < cols; ++c) {
+            double a = A[i] * B[c];
+            for (int k = 1; k < 6; ++k) a += A[k * 6 + i] * B[k * cols + c];
+            C[i * cols + c] = a;
+        }
+}
+
+// ---- stage A: the forward sweep of one segment ---------------------------------------------------------------------------------------------
+// Interior nodes p .. p + m - 1, left separator a = p - 1 (none: p = 0), right separator c = p + m (none: c = N).  Block elimination in index
+// order with the fill column F_k = H~[k][a] carried along; Cc[k] = H[k][k + 1] (zero where there is no chain edge, or no node).
+PG_HD inline void sweep_segment(int sidx, const int32_t* seg, int N, const double* D, const double* b, const double* Cc, double lam, double* nodews,
+                                double* slots) {
+    const int p = seg[sidx * 2], m = seg[sidx * 2 + 1];
+    double* slot = slots + (size_t)sidx * PG_SLOT;
+    for (int i = 0; i < PG_SLOT; ++i) slot[i] = 0.0;
+    if (p < 0 || m < 1 || p > N - m) return;
+    double At[36], F[36], bt[6], L[36], U[36], GU[36], GF[36], gb[6], tmp[36], tv[6];
+    for (int i = 0; i < 36; ++i) At[i] = D[(size_t)p * 36 + i] + ((i % 7 == 0) ? lam : 0.0);
+    for (int i = 0; i < 6; ++i) bt[i] = b[(size_t)p * 6 + i];
+    for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) F[r * 6 + c] = p > 0 ? Cc[(size_t)(p - 1) * 36 + c * 6 + r] : 0.0;      // H[p][a] = H[a][p]^T
+    for (int k = p; k < p + m; ++k) {
+        chol6(At, L);
+        for (int i = 0; i < 36; ++i) U[i] = k < N - 1 ? Cc[(size_t)k * 36 + i] : 0.0;
+        lsolve6(L, U, 6, GU);
+        lsolve6(L, F, 6, GF);
+        lsolve6(L, bt, 1, gb);
+        double* w = nodews + (size_t)k * PG_NODE_WS;
+        for (int i = 0; i < 36; ++i) w[i] = L[i], w[36 + i] = GU[i], w[72 + i] = GF[i];
+        for (int i = 0; i < 6; ++i) w[108 + i] = gb[i];
+        atb6(GF, GF, 6, tmp);
+        for (int i = 0; i < 36; ++i) slot[i] -= tmp[i];                          // (a, a) -= GF^T GF
+        atb6(GF, gb, 1, tv);
+        for (int i = 0; i < 6; ++i) slot[108 + i] -= tv[i];                      // r_a -= GF^T gb
+        if (k < p + m - 1) {
+            atb6(GU, GU, 6, tmp);
+            for (int i = 0; i < 36; ++i) At[i] = D[(size_t)(k + 1) * 36 + i] + ((i % 7 == 0) ? lam : 0.0) - tmp[i];
+            atb6(GU, GF, 6, tmp);
+            for (int i = 0; i < 36; ++i) F[i] = -tmp[i];
+            atb6(GU, gb, 1, tv);
+            for (int i = 0; i < 6; ++i) bt[i] = b[(size_t)(k + 1) * 6 + i] - tv[i];
+        } else {
+            atb6(GU, GF, 6, tmp);
+            for (int i = 0; i < 36; ++i) slot[36 + i] = -tmp[i];                 // (c, a) = -GU^T GF
+            atb6(GU, GU, 6, tmp);
+            for (int i = 0; i < 36; ++i) slot[72 + i] = -tmp[i];                 // (c, c) = -GU^T GU
+            atb6(GU, gb, 1, tv);
+            for (int i = 0; i < 6; ++i) slot[114 + i] = -tv[i];                  // r_c = -GU^T gb
+        }
+    }
+}
+
+// ---- stage C: back-substitution of one segment:  L^T x_k = gb - GU x_{k+1} - GF x_a ------------------------------------------------------------
+PG_HD inline void backsub_segment(int sidx, const int32_t* seg, int N, const double* nodews, double* delta) {
+    const int p = seg[sidx * 2], m = seg[sidx * 2 + 1];
+    if (p < 0 || m < 1 || p > N - m) return;
+    double xa[6], xn[6], x[6];
+    for (int i = 0; i < 6; ++i) {
+        xa[i] = p > 0 ? delta[(size_t)(p - 1) * 6 + i] : 0.0;
+        xn[i] = p + m < N ? delta[(size_t)(p + m) * 6 + i] : 0.0;
+    }
+    for (int k = p + m - 1; k >= p; --k) {
+        const double* w = nodews + (size_t)k * PG_NODE_WS;
+        for (int i = 0; i < 6; ++i) {
+            double a = w[108 + i];
+            for (int j = 0; j < 6; ++j) a -= w[36 + i * 6 + j] * xn[j];
+            for (int j = 0; j < 6; ++j) a -= w[72 + i * 6 + j] * xa[j];
+            x[i] = a;
+        }
+        for (int i = 5; i >= 0; --i) {               // L^T x = rhs
+            double a = x[i];
+            for (int j = i + 1; j < 6; ++j) a -= w[j * 6 + i] * x[j];
+            x[i] = a / w[i * 6 + i];
+        }
+        for (int i = 0; i < 6; ++i) delta[(size_t)k * 6 + i] = x[i], xn[i] = x[i];
+    }
+}
+
+// ---- stage B: the reduced system of the separators, one workgroup ------------------------------------------------------------------------------
+// Written over (tid, nt, sync) so that the same code runs as one host thread (nt = 1, sync a no-op).  M [n, n] row-major, n = 6 S; the factor
+// is stored transposed in place (L(i, k) at M[k * n + i]: consecutive rows of a column are consecutive addresses).
+struct pg_dense_args {
+    const double *D, *b, *Cc, *Hss, *slots;
+    const int32_t *seg, *sep_node, *node_slot, *adjacent, *long_edges;
+    int N, E, S, nseg, nadj, nlong, stages;
+    double lam;
+    double *M, *vec, *delta;       // vec [4 n]: the right-hand side | the column scratch | y | x
+};
+
+template <class Sync>
+PG_HD inline void dense_stage(const pg_dense_args& a, int tid, int nt, Sync sync) {
+    const int S = a.S, n = 6 * S;
+    double* M = a.M;
+    double *rv = a.vec, *col = a.vec + n, *y = a.vec + 2 * n, *x = a.vec + 3 * n;
+    if (a.stages & BS_PG_STAGE_REDUCED) {
+        for (int i = tid; i < n * n; i += nt) M[i] = 0.0;
+        for (int i = tid; i < 4 * n; i += nt) a.vec[i] = 0.0;
+        sync();
+        for (int i = tid; i < S * 36; i += nt) {                       // the separators' own D + lambda I
+            const int s = i / 36, r = (i % 36) / 6, c = i % 6, node = a.sep_node[s];
+            if (node >= 0 && node < a.N) M[(6 * s + r) * n + 6 * s + c] = a.D[(size_t)node * 36 + r * 6 + c] + (r == c ? a.lam : 0.0);
+        }
+        for (int i = tid; i < n; i += nt) {
+            const int node = a.sep_node[i / 6];
+            if (node >= 0 && node < a.N) rv[i] = a.b[(size_t)node * 6 + i % 6];
+        }
+        sync();
+        for (int i = tid; i < a.nadj * 36; i += nt) {                  // separators that are index neighbours: the chain coupling
+            const int node = a.adjacent[i / 36], r = (i % 36) / 6, c = i % 6;
+            if (node < 0 || node >= a.N - 1) continue;
+            const int sa = a.node_slot[node], sb = a.node_slot[node + 1];
+            if (sa < 0 || sa >= S || sb < 0 || sb >= S) continue;
+            const double v = a.Cc[(size_t)node * 36 + r * 6 + c];
+            M[(6 * sa + r) * n + 6 * sb + c] = v;
+            M[(6 * sb + c) * n + 6 * sa + r] = v;
+        }
+        sync();
+        for (int k = 0; k < a.nlong; ++k) {                            // long edges in edge order: H[s][t] = H[t][s] = -Hss; entry (r, c) has one owner
+            const int e = a.long_edges[k * 3], ss = a.long_edges[k * 3 + 1], st = a.long_edges[k * 3 + 2];
+            if (e < 0 || e >= a.E || ss < 0 || ss >= S || st < 0 || st >= S || ss == st) continue;
+            for (int i = tid; i < 36; i += nt) {
+                const int r = i / 6, c = i % 6;
+                const double v = -a.Hss[(size_t)e * 36 + i];
+                M[(6 * ss + r) * n + 6 * st + c] += v;
+                M[(6 * st + r) * n + 6 * ss + c] += v;
+            }
+        }
+        sync();
+        for (int k = 0; k < a.nseg; ++k) {                             // the segments' Schur contributions, in segment order
+            const int p = a.seg[k * 2], m = a.seg[k * 2 + 1];
+            if (p < 0 || m < 1 || p > a.N - m) continue;
+            int sa = p > 0 ? a.node_slot[p - 1] : -1, sc = p + m < a.N ? a.node_slot[p + m] : -1;
+            if (sa >= S) sa = -1;
+            if (sc >= S) sc = -1;
+            const double* sl = a.slots + (size_t)k * PG_SLOT;
+            for (int i = tid; i < 36; i += nt) {
+                const int r = i / 6, c = i % 6;
+                if (sa >= 0) M[(6 * sa + r) * n + 6 * sa + c] += sl[i];
+                if (sc >= 0) M[(6 * sc + r) * n + 6 * sc + c] += sl[72 + i];
+                if (sa >= 0 && sc >= 0) {
+                    M[(6 * sc + r) * n + 6 * sa + c] += sl[36 + i];
+                    M[(6 * sa + c) * n + 6 * sc + r] += sl[36 + i];
+                }
+                if (i < 6) {
+                    if (sa >= 0) rv[6 * sa + i] += sl[108 + i];
+                    if (sc >= 0) rv[6 * sc + i] += sl[114 + i];
+                }
+            }
+        }
+        sync();
+    }
+    if (!(a.stages & BS_PG_STAGE_DENSE_SOLVE)) return;
+    for (int j = 0; j < n; ++j) {                                      // left-looking Cholesky, the sum over k ascending
+        for (int i = j + tid; i < n; i += nt) {
+            double s = M[j * n + i];
+            for (int k = 0; k < j; ++k) s -= M[k * n + i] * M[k * n + j];
+            col[i] = s;
+        }
+        sync();
+        const double d = sqrt(col[j]);
+        for (int i = j + tid; i < n; i += nt) M[j * n + i] = i == j ? d : col[i] / d;
+        sync();
+    }
+    for (int j = 0; j < n; ++j) {                                      // L y = r
+        const double yj = rv[j] / M[j * n + j];
+        for (int i = j + tid; i < n; i += nt) {
+            if (i == j) y[j] = yj;
+            else rv[i] -= M[j * n + i] * yj;
+        }
+        sync();
+    }
+    for (int j = n - 1; j >= 0; --j) {                                 // L^T x = y
+        const double xj = y[j] / M[j * n + j];
+        for (int i = tid; i <= j; i += nt) {
+            if (i == j) x[j] = xj;
+            else y[i] -= M[i * n + j] * xj;
+        }
+        sync();
+    }
+    for (int i = tid; i < n; i += nt) {
+        const int node = a.sep_node[i / 6];
+        if (node >= 0 && node < a.N) a.delta[(size_t)node * 6 + i % 6] = x[i];
+    }
+}
+
+// ---- one node: Xn = exp6(delta) X ------------------------------------------------------------------------------------------------------------
+PG_HD inline void update_node(int n, const double* X, const double* delta, double* Xn, double* term) {
+    const double* P = X + (size_t)n * 16;
+    const double* d = delta + (size_t)n * 6;
+    double z[6], R[9];
+    lin6(P, z);
+    double t = 0.0;
+    for (int i = 0; i < 6; ++i) t += z[i] * z[i];
+    term[n] = t;
+    const double cx = cos(d[0]), sx = sin(d[0]), cy = cos(d[1]), sy = sin(d[1]), cz = cos(d[2]), sz = sin(d[2]);
+    R[0] = cz * cy, R[1] = cz * sy * sx - sz * cx, R[2] = cz * sy * cx + sz * sx;
+    R[3] = sz * cy, R[4] = sz * sy * sx + cz * cx, R[5] = sz * sy * cx - cz * sx;
+    R[6] = -sy, R[7] = cy * sx, R[8] = cy * cx;
+    double* O = Xn + (size_t)n * 16;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) O[r * 4 + c] = R[r * 3] * P[c] + R[r * 3 + 1] * P[4 + c] + R[r * 3 + 2] * P[8 + c] + d[3 + r] * P[12 + c];
+    for (int c = 0; c < 4; ++c) O[12 + c] = P[12 + c];
+}
+
+// ---- kernels ---------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PG_THREADS) void pg_linearise_kernel(const double* X, int N, const double* T, const double* info, const int32_t* src,
+                                                                  const int32_t* tgt, const int32_t* unc, int E, double mu, int flags, double* lw,
+                                                                  double* z, double* q, double* Hss, double* g, double* cterm) {
+    const int e = blockIdx.x * PG_THREADS + threadIdx.x;
+    if (e < E) linearise_edge(e, X, N, T, info, src, tgt, unc, mu, flags, lw, z, q, Hss, g, cterm);
+}
+
+__global__ __launch_bounds__(PG_THREADS) void pg_assemble_kernel(int N, int E, const double* Hss, const double* g, const int32_t* row_ptr,
+                                                                 const int32_t* adj, int nnz, int ref, double* D, double* b, double* Cc) {
+    const int n = blockIdx.x * PG_THREADS + threadIdx.x;
+    if (n < N) assemble_node(n, N, E, Hss, g, row_ptr, adj, nnz, ref, D, b, Cc);
+}
+
+__global__ __launch_bounds__(64) void pg_sweep_kernel(const int32_t* seg, int nseg, int N, const double* D, const double* b, const double* Cc, double lam,
+                                                      double* nodews, double* slots) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s < nseg) sweep_segment(s, seg, N, D, b, Cc, lam, nodews, slots);
+}
+
+__global__ __launch_bounds__(64) void pg_backsub_kernel(const int32_t* seg, int nseg, int N, const double* nodews, double* delta) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s < nseg) backsub_segment(s, seg, N, nodews, delta);
+}
+
+struct pg_block_sync {
+    __device__ void operator()() const { __syncthreads(); }
+};
+
+__global__ __launch_bounds__(PG_DENSE_THREADS) void pg_dense_kernel(pg_dense_args a) { dense_stage(a, (int)threadIdx.x, PG_DENSE_THREADS, pg_block_sync()); }
+
+__global__ __launch_bounds__(PG_THREADS) void pg_update_kernel(const double* X, const double* delta, int N, double* Xn, double* term) {
+    const int n = blockIdx.x * PG_THREADS + threadIdx.x;
+    if (n < N) update_node(n, X, delta, Xn, term);
+}
+
+// One-wave reductions: lane l adds its elements l, l + 64, ... in order, then the xor butterfly 32, 16, ..., 1: a fixed order.
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
+
+__global__ __launch_bounds__(64) void pg_sum_kernel(const double* v, int n, double* out) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 64) s += v[i];
+    s = wave_sum(s);
+    if (threadIdx.x == 0) out[0] = s;
+}
+
+// out[0] = max b, out[1] = max diag H (the reference node's rows are in: zeros of b, ones of the diagonal, as on the host)
+__global__ __launch_bounds__(64) void pg_max_kernel(const double* D, const double* b, int N, double* out) {
+    double mb = -INFINITY, md = -INFINITY;
+    for (int i = threadIdx.x; i < 6 * N; i += 64) {
+        mb = fmax(mb, b[i]);
+        md = fmax(md, D[(size_t)(i / 6) * 36 + (i % 6) * 7]);
+    }
+    mb = wave_max(mb), md = wave_max(md);
+    if (threadIdx.x == 0) out[0] = mb, out[1] = md;
+}
+
+// out[0] = |delta|^2, out[1] = delta . (lambda delta + b)
+__global__ __launch_bounds__(64) void pg_step_sums_kernel(const double* delta, const double* b, int n, double lam, double* out) {
+    double s0 = 0.0, s1 = 0.0;
+    for (int i = threadIdx.x; i < n; i += 64) {
+        const double d = delta[i];
+        s0 += d * d;
+        s1 += d * (lam * d + b[i]);
+    }
+    s0 = wave_sum(s0), s1 = wave_sum(s1);
+    if (threadIdx.x == 0) out[0] = s0, out[1] = s1;
+}
+
+}  // namespace
+}  // namespace bs
+
+#define PG_ENTRY(name)                                                                    \
+    using namespace bs;                                                                   \
+    if (!initialized()) { set_error(name ": call bs_init first"); return BS_ERR_NOT_INIT; } \
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream)
+
+extern "C" int bs_pg_linearise(const double* X, int32_t N, const double* T, const double* info, const int32_t* src, const int32_t* tgt,
+                               const int32_t* uncertain, int32_t E, double mu, int32_t flags, double* lw, double* z, double* q, double* Hss, double* g,
+                               double* cterm, double* cost, void* stream) {
+    PG_ENTRY("bs_pg_linearise");
+    BS_REQUIRE(X && T && info && src && tgt && uncertain && lw && z && q && cterm, "bs_pg_linearise: null pointer");
+    BS_REQUIRE(N >= 1 && N <= BS_PG_MAX_NODES && E >= 1 && E <= BS_PG_MAX_EDGES, "bs_pg_linearise: N = %d (1 .. %d), E = %d (1 .. %d)", N, BS_PG_MAX_NODES, E,
+               BS_PG_MAX_EDGES);
+    BS_REQUIRE((flags & ~(BS_PG_LINE_PROCESS | BS_PG_SYSTEM)) == 0, "bs_pg_linearise: flags %d", flags);
+    BS_REQUIRE(!(flags & BS_PG_SYSTEM) || (Hss && g), "bs_pg_linearise: BS_PG_SYSTEM needs Hss and g");
+    BS_REQUIRE(mu >= 0.0 && isfinite(mu), "bs_pg_linearise: mu %g", mu);
+    hipLaunchKernelGGL(pg_linearise_kernel, dim3((unsigned)cdiv(E, PG_THREADS)), dim3(PG_THREADS), 0, st, X, N, T, info, src, tgt, uncertain, E, mu, flags, lw, z,
+                       q, Hss, g, cterm);
+    BS_CHECK_LAUNCH();
+    if (cost) {
+        hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(64), 0, st, cterm, E, cost);
+        BS_CHECK_LAUNCH();
+    }
+    return BS_OK;
+}
+
+extern "C" int bs_pg_assemble(const double* Hss, const double* g, int32_t E, int32_t N, const int32_t* row_ptr, const int32_t* adj, int32_t nnz,
+                              int32_t reference_node, double* D, double* b, double* Cc, double* maxes, void* stream) {
+    PG_ENTRY("bs_pg_assemble");
+    BS_REQUIRE(Hss && g && row_ptr && adj && D && b && Cc, "bs_pg_assemble: null pointer");
+    BS_REQUIRE(N >= 1 && N <= BS_PG_MAX_NODES && E >= 1 && E <= BS_PG_MAX_EDGES, "bs_pg_assemble: N = %d (1 .. %d), E = %d (1 .. %d)", N, BS_PG_MAX_NODES, E,
+               BS_PG_MAX_EDGES);
+    BS_REQUIRE(nnz >= 0 && nnz <= 2 * E, "bs_pg_assemble: %d adjacency entries for %d edges", nnz, E);
+    BS_REQUIRE(reference_node >= 0 && reference_node < N, "bs_pg_assemble: reference node %d of %d", reference_node, N);
+    hipLaunchKernelGGL(pg_assemble_kernel, dim3((unsigned)cdiv(N, PG_THREADS)), dim3(PG_THREADS), 0, st, N, E, Hss, g, row_ptr, adj, nnz, reference_node, D, b,
+                       Cc);
+    BS_CHECK_LAUNCH();
+    if (maxes) {
+        hipLaunchKernelGGL(pg_max_kernel, dim3(1), dim3(64), 0, st, D, b, N, maxes);
+        BS_CHECK_LAUNCH();
+    }
+    return BS_OK;
+}
+
+extern "C" int bs_pg_solve(const double* D, const double* b, const double* Cc, const double* Hss, int32_t N, int32_t E, double lambda, const int32_t* segments,
+                           int32_t n_segments, const int32_t* sep_node, int32_t S, const int32_t* node_slot, const int32_t* adjacent, int32_t n_adjacent,
+                           const int32_t* long_edges, int32_t n_long, int32_t stages, double* node_ws, double* slots, double* M, double* vec, double* delta,
+                           double* sums, void* stream) {
+    PG_ENTRY("bs_pg_solve");
+    BS_REQUIRE(D && b && Cc && Hss && sep_node && node_slot && node_ws && slots && M && vec && delta, "bs_pg_solve: null pointer");
+    BS_REQUIRE(N >= 1 && N <= BS_PG_MAX_NODES && E >= 1 && E <= BS_PG_MAX_EDGES, "bs_pg_solve: N = %d (1 .. %d), E = %d (1 .. %d)", N, BS_PG_MAX_NODES, E,
+               BS_PG_MAX_EDGES);
+    BS_REQUIRE(S >= 1 && S <= BS_PG_MAX_SEPARATORS && S <= N, "bs_pg_solve: %d separators (1 .. %d, at most N)", S, BS_PG_MAX_SEPARATORS);
+    BS_REQUIRE(n_segments >= 0 && n_segments <= N && (n_segments == 0 || segments), "bs_pg_solve: %d segments", n_segments);
+    BS_REQUIRE(n_adjacent >= 0 && n_adjacent < BS_PG_MAX_SEPARATORS && (n_adjacent == 0 || adjacent), "bs_pg_solve: %d adjacent separator pairs", n_adjacent);
+    BS_REQUIRE(n_long >= 0 && n_long <= E && (n_long == 0 || long_edges), "bs_pg_solve: %d long edges of %d", n_long, E);
+    BS_REQUIRE(lambda > 0.0 && isfinite(lambda), "bs_pg_solve: lambda %g (positive)", lambda);
+    BS_REQUIRE(stages > 0 && (stages & ~BS_PG_STAGE_ALL) == 0, "bs_pg_solve: stages %d", stages);
+    if ((stages & BS_PG_STAGE_SWEEP) && n_segments) {
+        hipLaunchKernelGGL(pg_sweep_kernel, dim3((unsigned)cdiv(n_segments, 64)), dim3(64), 0, st, segments, n_segments, N, D, b, Cc, lambda, node_ws, slots);
+        BS_CHECK_LAUNCH();
+    }
+    if (stages & (BS_PG_STAGE_REDUCED | BS_PG_STAGE_DENSE_SOLVE)) {
+        pg_dense_args a;
+        a.D = D, a.b = b, a.Cc = Cc, a.Hss = Hss, a.slots = slots;
+        a.seg = segments, a.sep_node = sep_node, a.node_slot = node_slot, a.adjacent = adjacent, a.long_edges = long_edges;
+        a.N = N, a.E = E, a.S = S, a.nseg = n_segments, a.nadj = n_adjacent, a.nlong = n_long, a.stages = stages;
+        a.lam = lambda, a.M = M, a.vec = vec, a.delta = delta;
+        hipLaunchKernelGGL(pg_dense_kernel, dim3(1), dim3(PG_DENSE_THREADS), 0, st, a);
+        BS_CHECK_LAUNCH();
+    }
+    if (stages & BS_PG_STAGE_BACKSUB) {
+        if (n_segments) {
+            hipLaunchKernelGGL(pg_backsub_kernel, dim3((unsigned)cdiv(n_segments, 64)), dim3(64), 0, st, segments, n_segments, N, node_ws, delta);
+            BS_CHECK_LAUNCH();
+        }
+        if (sums) {
+            hipLaunchKernelGGL(pg_step_sums_kernel, dim3(1), dim3(64), 0, st, delta, b, 6 * N, lambda, sums);
+            BS_CHECK_LAUNCH();
+        }
+    }
+    return BS_OK;
+}
+
+extern "C" int bs_pg_update(const double* X, const double* delta, int32_t N, double* Xn, double* terms, double* xnorm2, void* stream) {
+    PG_ENTRY("bs_pg_update");
+    BS_REQUIRE(X && delta && Xn && terms && X != Xn, "bs_pg_update: null pointer, or X and Xn are the same array");
+    BS_REQUIRE(N >= 1 && N <= BS_PG_MAX_NODES, "bs_pg_update: N = %d (1 .. %d)", N, BS_PG_MAX_NODES);
+    hipLaunchKernelGGL(pg_update_kernel, dim3((unsigned)cdiv(N, PG_THREADS)), dim3(PG_THREADS), 0, st, X, delta, N, Xn, terms);
+    BS_CHECK_LAUNCH();
+    if (xnorm2) {
+        hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(64), 0, st, terms, N, xnorm2);
+        BS_CHECK_LAUNCH();
+    }
+    return BS_OK;
+}

@@ -126,6 +126,9 @@ class BodySlamPipeline:
         # (the reference never adds any: slam.py:30,80)
         self.posegraph_every = 0
         self.loop_closures = []
+        # where the pose graph is optimised: "host" (posegraph.py's numpy / sparse-LU path, as in the reference) or "device" (the same LM with its
+        # numerical pieces as HIP kernels).  Read wherever a PoseGraph is built below
+        self.posegraph_solver = "host"
         # the reference's names for the step it declares and never wrote (slam.py:30,41,42; :79-80 calls an undefined _loop_closure):
         # with perform_loop_closure, run_slam_loop makes every num_closure-th frame a keyframe and first looks for a closure of it
         # against the older keyframes (loop_closure.LoopCloser).  The edges found join the graph as uncertain edges and are listed in
@@ -209,7 +212,8 @@ class BodySlamPipeline:
         G = g_abs.cpu().numpy()
         T = t_all.view(-1, 4, 4).cpu().numpy().astype(np.float64)
         N = G.shape[0]
-        pg = PoseGraph()
+        pg = PoseGraph(solver=self.posegraph_solver)
+        pg.device = self.dev.index or 0
         pg.add_node(G[0])
         lc = sorted(self.loop_closures, key=lambda e: max(e[0], e[1]))
         k = 0
@@ -336,7 +340,8 @@ class BodySlamPipeline:
                     k += 1
                 state["tsdf"].build_3D_map_batch([RGBDImage(fr_dev[i], dm_map[i - b0]) for (_, i, _) in run], intr, [pose for (_, _, pose) in run])
 
-        pg = PoseGraph()
+        pg = PoseGraph(solver=self.posegraph_solver)
+        pg.device = self.dev.index or 0
         extr, rel_fused = [], []
         cnt_all = torch.empty(N, dtype=torch.int32, device=self.dev)
         points = [] if keep_points else None

@@ -701,6 +701,56 @@ int bs_loop_register(const double* xyz, int32_t n_frames, const int32_t* pairs, 
                      int32_t max_hamming, double tau, int32_t n_hyp, int32_t n_refit, int32_t min_matches, uint64_t seed, double* records,
                      int32_t* mask, void* stream);
 
+/* ---- pose graph: the numerical pieces of the line-process Levenberg-Marquardt (Choi, Zhou, Koltun, CVPR 2015) ---------------------------
+ * The algorithm is the one bodyslam_amd/posegraph.py and oracle/posegraph_ref.py state (parity with Open3D UNPINNED); the LM control flow
+ * stays on the host (PoseGraph(solver="device")), these four calls are what it evaluates.  Everything is fp64, device memory, row-major;
+ * poses are 4 x 4 rigid transforms whose inverse is taken in closed form ([R^T | -R^T t]; the host path calls a general inverse).  No LDS,
+ * no atomics, every sum in a fixed order: the same bits in every run.  The statement is tests/_posegraph_solve_ref.py.
+ *   bs_pg_linearise   one lane per edge e = (src, tgt, T, info [6, 6], uncertain):  z = lin6(T^-1 X_tgt^-1 X_src),  q = z^T info z;
+ *                     with BS_PG_LINE_PROCESS  lw = (mu / (mu + q))^2 for an uncertain edge and 1 otherwise is written, else lw is read;
+ *                     cterm = lw q (+ mu (sqrt(lw) - 1)^2, uncertain);  with BS_PG_SYSTEM  Js[:, i] = lin6(T^-1 X_tgt^-1 G_i X_src),
+ *                     Hss = Js^T (lw info) Js [E, 36] and g = Js^T (lw info) z [E, 6].  Without BS_PG_SYSTEM Hss and g are not touched
+ *                     (the trial step's "cost only" mode).  cost (may be null): the sum of cterm, one wave: lane l adds l, l + 64, ..., then
+ *                     the xor butterfly 32 .. 1.  An edge whose endpoints leave [0, N) reads nothing and writes zeros.
+ *   bs_pg_assemble    one lane per node, a gather over its incident edges: row_ptr int32 [N + 1], adj int32 [nnz, 3] = (edge, the other
+ *                     endpoint, -1 as the edge's source / +1 as its target) in ascending edge order, self-edges left out.
+ *                     D [N, 36] = sum Hss, b [N, 6] = sum (source: -g, target: +g), Cc [N, 36]: Cc[i] = H[i][i + 1] = -sum Hss over the
+ *                     edges between i and i + 1 (Cc[N - 1] = 0).  The reference node: D = I, b = 0, its couplings zero.
+ *                     maxes (may be null) [2] = max b, max diag H.
+ *   bs_pg_solve       (H + lambda I) delta = b by one level of substructuring over a plan made on the host (posegraph.solve_plan):
+ *                     sep_node int32 [S] (ascending), node_slot int32 [N] (the separator's slot, -1 otherwise), segments int32 [n, 2] =
+ *                     (first node, length) of every maximal run of non-separators, adjacent int32 [n_adjacent] = nodes i with i and i + 1
+ *                     both separators, long_edges int32 [n_long, 3] = (edge, slot of its source, slot of its target) of the edges with
+ *                     |src - tgt| >= 2 that do not touch the reference node.  stages: BS_PG_STAGE_SWEEP (one lane per segment: block
+ *                     Cholesky over the interior in index order, the fill column to the left separator carried along; writes node_ws
+ *                     [N, BS_PG_NODE_WORKSPACE] = L | L^-1 U | L^-1 F | L^-1 b~ and slots [n, BS_PG_SLOT_FIELDS] = the Schur contributions
+ *                     (a, a) | (c, a) | (c, c) | r_a | r_c to the left (a) and right (c) separator), BS_PG_STAGE_REDUCED (one workgroup: M
+ *                     [6 S, 6 S] and vec[0 : 6 S] = the separators' D + lambda I and b, the couplings of adjacent separators, the long edges
+ *                     in edge order, the slots in segment order), BS_PG_STAGE_DENSE_SOLVE (the same workgroup: left-looking Cholesky in
+ *                     place -- L(i, k) at M[k, i] --, two triangular solves, delta of the separators), BS_PG_STAGE_BACKSUB (one lane per
+ *                     segment: the interiors' delta; sums (may be null) [2] = |delta|^2, delta . (lambda delta + b), one wave as above).
+ *                     vec: 24 S doubles.  S <= BS_PG_MAX_SEPARATORS; a larger graph is the host path's.  information matrices are taken as
+ *                     symmetric.  A pivot that is not positive gives NaN in delta and the sums.
+ *   bs_pg_update      one lane per node: Xn = exp6(delta) X (exp6 = [Rz(d2) Ry(d1) Rx(d0) | d3:6], the bottom row copied), terms [N] =
+ *                     |lin6(X)|^2 of the INPUT pose, xnorm2 (may be null) = their sum, one wave as above.  X and Xn are different arrays. */
+#define BS_PG_MAX_SEPARATORS 128
+#define BS_PG_MAX_NODES (1 << 24)
+#define BS_PG_MAX_EDGES (1 << 24)
+#define BS_PG_NODE_WORKSPACE 114
+#define BS_PG_SLOT_FIELDS 120
+enum { BS_PG_LINE_PROCESS = 1, BS_PG_SYSTEM = 2 };
+enum { BS_PG_STAGE_SWEEP = 1, BS_PG_STAGE_REDUCED = 2, BS_PG_STAGE_DENSE_SOLVE = 4, BS_PG_STAGE_BACKSUB = 8, BS_PG_STAGE_ALL = 15 };
+int bs_pg_linearise(const double* X, int32_t N, const double* T, const double* info, const int32_t* src, const int32_t* tgt,
+                    const int32_t* uncertain, int32_t E, double mu, int32_t flags, double* lw, double* z, double* q, double* Hss, double* g,
+                    double* cterm, double* cost, void* stream);
+int bs_pg_assemble(const double* Hss, const double* g, int32_t E, int32_t N, const int32_t* row_ptr, const int32_t* adj, int32_t nnz,
+                   int32_t reference_node, double* D, double* b, double* Cc, double* maxes, void* stream);
+int bs_pg_solve(const double* D, const double* b, const double* Cc, const double* Hss, int32_t N, int32_t E, double lambda, const int32_t* segments,
+                int32_t n_segments, const int32_t* sep_node, int32_t S, const int32_t* node_slot, const int32_t* adjacent, int32_t n_adjacent,
+                const int32_t* long_edges, int32_t n_long, int32_t stages, double* node_ws, double* slots, double* M, double* vec, double* delta,
+                double* sums, void* stream);
+int bs_pg_update(const double* X, const double* delta, int32_t N, double* Xn, double* terms, double* xnorm2, void* stream);
+
 /* ---- engine files: the forward of a whole model for a host without Python ------------------------------------
  * The reference's hosts are DepthEstimator.infer_depth_map (BodySLAM_Refactored/src/depth_estimation/interface.py:39-45) and
  * MPEMInterface.infer_relative_pose_between (BodySLAM_not_refactored/MPEM/mpem_interface.py:61-99), both Python.  A plan -- the launch
