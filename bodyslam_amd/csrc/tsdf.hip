@@ -378,6 +378,99 @@ __global__ __launch_bounds__(256) void tsdf_integrate_batch_kernel(const TsdfFra
     }
 }
 
+// ---- frames taken out again: map correction after a pose-graph update ----------------------------------------------
+// The running means are invertible: a frame that went in with (pose, image) is taken out by observing the voxel with the SAME pose and
+// image -- tsdf_observe gives the same decision and the same tsdf bits -- and undoing the blend.  The undo is exact in the weight (a
+// small integer) and rounds in the values; a voxel whose weight returns to 0 is reset to all +0.0f, so rounding residue never
+// outlives the observations that made it and an emptied block is bit-identical to a fresh one.  Open3D has no such operation.
+// Returns false (and changes nothing) when the voxel holds no observation: the caller removed a frame it never integrated.
+__device__ __forceinline__ bool tsdf_unblend(float vox[5], float tsdf, const uint8_t* __restrict__ c) {
+    const float w0 = vox[1];
+    if (w0 < 1.0f) return false;
+    const float w1 = w0 - 1.0f;
+    if (w1 == 0.0f) {
+        vox[0] = vox[1] = vox[2] = vox[3] = vox[4] = 0.0f;
+        return true;
+    }
+    const float rw = 1.0f / w1;
+    vox[0] = fmaf(vox[0], w0, -tsdf) * rw;
+    if (c) {
+        vox[2] = fmaf(vox[2], w0, -(float)c[0]) * rw;
+        vox[3] = fmaf(vox[3], w0, -(float)c[1]) * rw;
+        vox[4] = fmaf(vox[4], w0, -(float)c[2]) * rw;
+    }
+    vox[1] = w1;
+    return true;
+}
+
+// tsdf_integrate_batch_kernel with a sign per record: bit f of remove_mask (a kernel argument: scalar registers) set = record f is
+// taken out, clear = it is added.  Records are applied in ascending order in registers, the voxel is loaded once and stored once, the
+// frame loop is uniform over the block.  A removal that finds weight < 1 is skipped and reported through *flag (counters[2] = 3).
+__global__ __launch_bounds__(256) void tsdf_update_batch_kernel(const TsdfFrame* __restrict__ frames, int H, int W, const int32_t* __restrict__ unit_index,
+                                                                 const int32_t* __restrict__ touched, const int32_t* __restrict__ n_touched_dev,
+                                                                 const unsigned long long* __restrict__ unit_mask, int blocks_per_unit,
+                                                                 const int64_t* __restrict__ slab_base, int slab_units, int res, double voxel_length,
+                                                                 double sdf_trunc, unsigned long long remove_mask, int32_t* __restrict__ flag) {
+    const long long total = (long long)(*n_touched_dev) * blocks_per_unit;
+    const int nvox = res * res * res;
+    const double unit_len = voxel_length * res, half = voxel_length * 0.5;
+    const bool with_color = frames[0].color != nullptr;
+    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
+        const int ti = (int)(w / blocks_per_unit), bx = (int)(w - (long long)ti * blocks_per_unit);
+        const int u = touched[ti];
+        const int v = bx * 256 + threadIdx.x;
+        if (v >= nvox) continue;
+        const unsigned long long m = unit_mask[u];
+        unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)m), hi = __builtin_amdgcn_readfirstlane((unsigned)(m >> 32));
+        const int x = v / (res * res), y = (v / res) % res, z = v % res;
+        const double px = half + voxel_length * x + unit_len * unit_index[3 * u + 0];
+        const double py = half + voxel_length * y + unit_len * unit_index[3 * u + 1];
+        const double pz = half + voxel_length * z + unit_len * unit_index[3 * u + 2];
+        float* vox = ts_block(slab_base, slab_units, (int64_t)nvox * 20, u) + (int64_t)v * 5;
+        float s[5];
+        bool have = false, wiped = false;
+        for (int half_ = 0; half_ < 2; ++half_) {
+            unsigned bits = half_ ? hi : lo;
+            while (bits) {
+                const int f = __builtin_ctz(bits) + 32 * half_;
+                bits &= bits - 1;
+                const bool remove = (remove_mask >> f) & 1ull;
+                const TsdfFrame& F = frames[f];
+                TsdfCam cam;
+                cam.fx = F.fx; cam.fy = F.fy; cam.cx = F.cx; cam.cy = F.cy; cam.ifx = F.ifx; cam.ify = F.ify;
+#pragma unroll
+                for (int i = 0; i < 12; ++i) cam.e[i] = F.view[i];
+                float tsdf;
+                int64_t pix;
+                if (!tsdf_observe(px, py, pz, cam, F.depth, H, W, sdf_trunc, tsdf, pix)) continue;
+                if (!have) {
+                    s[0] = vox[0]; s[1] = vox[1];
+                    s[2] = s[3] = s[4] = 0.0f;
+                    if (with_color) {
+                        s[2] = vox[2]; s[3] = vox[3]; s[4] = vox[4];
+                    }
+                    have = true;
+                }
+                const uint8_t* c = F.color ? F.color + pix * 3 : nullptr;
+                if (!remove) {
+                    tsdf_blend(s, tsdf, c);
+                } else if (!tsdf_unblend(s, tsdf, c)) {
+                    *flag = 3;        // a frame was removed that the voxel never held
+                } else if (s[1] == 0.0f) {
+                    wiped = true;     // the reset covers all five floats, colours included
+                }
+            }
+        }
+        if (have) {
+            vox[0] = s[0];
+            vox[1] = s[1];
+            if (with_color || wiped) {
+                vox[2] = s[2]; vox[3] = s[3]; vox[4] = s[4];
+            }
+        }
+    }
+}
+
 // ScalableTSDFVolume::GetTSDFAt: trilinear interpolation of the tsdf over the 8 voxel centres around p (a corner in a unit that does
 // not exist contributes 0; the first corner's unit missing gives 0 altogether)
 __device__ double ts_tsdf_at(const double p[3], const long long* __restrict__ keys, const int32_t* __restrict__ slots, unsigned mask,
@@ -969,6 +1062,37 @@ extern "C" int bs_tsdf_integrate_batch(const void* frames_dev, int32_t n_frames,
     const unsigned grid = (unsigned)(want < 16ll * cu_count() ? want : 16ll * cu_count());
     hipLaunchKernelGGL(tsdf_integrate_batch_kernel, dim3(grid), dim3(256), 0, st, frames, H, W, unit_index, touched, counters + 1,
                        reinterpret_cast<const unsigned long long*>(unit_mask), bpu, slab_base, slab_units, res, voxel_length, sdf_trunc);
+    BS_CHECK_LAUNCH();
+    return BS_OK;
+}
+
+// bs_tsdf_integrate_batch's launches with tsdf_update_batch_kernel as the third: the same assignment, frustum test and masks
+extern "C" int bs_tsdf_update_batch(const void* frames_dev, int32_t n_frames, int32_t H, int32_t W, const void* table_keys, int32_t* table_slots,
+                                    void* table_fmask, int32_t table_cap, int32_t* unit_index, int32_t max_units, int32_t* counters, int32_t* touched,
+                                    void* unit_mask, const int64_t* slab_base, int32_t slab_units, int32_t res, double voxel_length, double sdf_trunc,
+                                    uint64_t remove_mask, void* stream) {
+    if (!initialized()) { set_error("bs_tsdf_update_batch: call bs_init first"); return BS_ERR_NOT_INIT; }
+    BS_REQUIRE(frames_dev && table_keys && table_slots && table_fmask && unit_index && counters && touched && unit_mask && slab_base,
+               "bs_tsdf_update_batch: null argument");
+    BS_REQUIRE(n_frames > 0 && n_frames <= BS_TSDF_BATCH_MAX && H > 0 && W > 0 && res > 0 && res <= 64 && slab_units > 0 && voxel_length > 0.0 &&
+                   sdf_trunc > 0.0 && max_units > 0,
+               "bs_tsdf_update_batch: bad geometry");
+    BS_REQUIRE(table_cap >= 256 && (table_cap & (table_cap - 1)) == 0, "bs_tsdf_update_batch: table_cap=%d must be a power of two >= 256", table_cap);
+    BS_REQUIRE(n_frames == BS_TSDF_BATCH_MAX || (remove_mask >> n_frames) == 0ull, "bs_tsdf_update_batch: remove_mask names a record past n_frames=%d", n_frames);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const TsdfFrame* frames = static_cast<const TsdfFrame*>(frames_dev);
+    BS_CHECK_HIP(hipMemsetAsync(counters + 1, 0, sizeof(int32_t), st));
+    const int cull = diag_env("BS_TSDF_NO_CULL") == nullptr;
+    hipLaunchKernelGGL(tsdf_assign_batch_kernel, dim3(cdiv(table_cap, 256)), dim3(256), 0, st, frames, reinterpret_cast<const long long*>(table_keys),
+                       table_slots, reinterpret_cast<unsigned long long*>(table_fmask), (unsigned)table_cap, unit_index, max_units, counters, touched,
+                       reinterpret_cast<unsigned long long*>(unit_mask), voxel_length * res, W, H, cull);
+    BS_CHECK_LAUNCH();
+    const int nvox = res * res * res, bpu = cdiv(nvox, 256);
+    const long long want = (long long)bpu * max_units;
+    const unsigned grid = (unsigned)(want < 16ll * cu_count() ? want : 16ll * cu_count());
+    hipLaunchKernelGGL(tsdf_update_batch_kernel, dim3(grid), dim3(256), 0, st, frames, H, W, unit_index, touched, counters + 1,
+                       reinterpret_cast<const unsigned long long*>(unit_mask), bpu, slab_base, slab_units, res, voxel_length, sdf_trunc,
+                       (unsigned long long)remove_mask, counters + 2);
     BS_CHECK_LAUNCH();
     return BS_OK;
 }

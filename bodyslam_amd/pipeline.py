@@ -138,6 +138,13 @@ class BodySlamPipeline:
         self.global_key_frame_indices = []
         self.loop_closures_found = []
         self.loop_closure_options = {}
+        # what run_slam_loop does to the map when an optimisation moved poses: "rebuild" (the reference: a fresh volume, frames 0..i again),
+        # "incremental" (the moved frames are taken out with the pose they went in with and put back with the new one, TSDF.apply_batch;
+        # DESIGN section 3.15) or "auto" (incremental unless a fresh volume is no dearer).  map_correction_tol = (metres, radians): a frame
+        # whose pose changed by no more than both stays as it is.  last_map_corrections: (frame i, moved, added, decision) per such step
+        self.map_correction = "rebuild"
+        self.map_correction_tol = (0.0, 0.0)
+        self.last_map_corrections = []
         self.K, self.depth_scale, self.depth_trunc, self.flip = tuple(K), depth_scale, depth_trunc, flip_aug
         self.zoe = ZoeDepthEngine(zoe_weights, zoe_cfg, dtype=dtype, device=device, target_hw=target_hw, precision=precision)
         self.precision = precision
@@ -277,6 +284,9 @@ class BodySlamPipeline:
         (``RGBDOdometry.track``), the UKF / chain / pose graph are host arithmetic on a few numbers (as in the reference), the map
         steps are enqueued without a round trip (``TSDF.build_3D_map(sync=False)``; block capacity is reserved a batch ahead and
         checked at the batch end).  ``tsdf_factory()`` makes the fresh TSDF of a rebuild (default: a copy of ``tsdf``'s parameters).
+        With ``self.map_correction = "incremental"`` (or "auto") the map is not rebuilt after a pose-graph step that moved poses but
+        corrected in place: the moved frames are taken out and put back with their new poses (``TSDF.apply_batch``), the volume passed
+        in stays the loop's map; the rebuild at ``rebuild_every`` stays a rebuild.
         Returns the poses as they stand at the end (after pose-graph updates); ``on_frame(i, pose, pcd_or_None)`` is called per frame."""
         from .posegraph import PoseGraph, update_global_extrinsic
         from .tsdf import PinholeCameraIntrinsic, RGBDImage, TSDF
@@ -302,7 +312,11 @@ class BodySlamPipeline:
         if tsdf is not None and tsdf_factory is None:
             tsdf_factory = lambda: TSDF(tsdf.voxel_length, tsdf.sdf_trunc, tsdf.res, tsdf.stride, device=self.dev.index or 0,
                                         slab_bytes=tsdf.slab_units * tsdf.unit_floats * 4, max_units=tsdf.max_units)
-        state = {"tsdf": tsdf, "closer": None}
+        if self.map_correction not in ("rebuild", "incremental", "auto"):
+            raise ValueError(f"map_correction {self.map_correction!r} is none of 'rebuild', 'incremental', 'auto'")
+        # ledger[j]: the extrinsic frame j is in the map with, None while it is not (a frame of the optimise branch is never integrated)
+        state = {"tsdf": tsdf, "closer": None, "ledger": [None] * N}
+        self.last_map_corrections = []
         if self.perform_loop_closure:
             from .loop_closure import LoopCloser
             state["closer"] = LoopCloser(tuple(float(v) for v in self.K), device=self.dev.index or 0, **self.loop_closure_options)
@@ -323,6 +337,26 @@ class BodySlamPipeline:
                 t.build_3D_map_batch([RGBDImage(fr_dev[j], dm[j - j0]) for j in range(j0, j1)], intr, poses[j0:j1])
             t.sync()
             state["tsdf"] = t
+            state["ledger"] = [np.array(poses[j]) if j <= upto else None for j in range(N)]
+
+        def correct(upto, poses):
+            """the same map as rebuild(upto, poses) up to rounding, made in place: the frames whose pose moved are taken out with their
+            ledger pose and put back with the new one, the frames not yet in the map are added (map_correction.plan_map_correction)"""
+            from .map_correction import plan_map_correction
+            plan = plan_map_correction(state["ledger"], poses, upto, self.map_correction_tol, self.map_correction)
+            self.last_map_corrections.append((upto, list(plan.moved), list(plan.added), plan.decision))
+            if plan.decision == "rebuild":
+                rebuild(upto, poses)
+                return
+            for (r0, r1) in plan.groups:                                        # a group = one pass over the map
+                recs = plan.records[r0:r1]
+                js = sorted({j for (j, _, _) in recs})
+                at = {j: k for k, j in enumerate(js)}
+                dm = L.depth_u16_to_m(depth_all[torch.as_tensor(js, device=self.dev)].contiguous(), self.depth_scale, self.depth_trunc)
+                state["tsdf"].apply_batch([RGBDImage(fr_dev[j], dm[at[j]]) for (j, _, _) in recs], intr, [E for (_, E, _) in recs],
+                                          [rm for (_, _, rm) in recs])
+            for j in plan.moved + plan.added:
+                state["ledger"][j] = np.array(poses[j])
 
         def run_map_actions(actions, b0, dm_map):
             """the map steps a batch of frames asked for, in order.  A run of plain integrations is ONE pass over the map
@@ -330,8 +364,8 @@ class BodySlamPipeline:
             touched voxel loaded once and updated with its frames in order) -- bit for bit the frame-by-frame result."""
             k = 0
             while k < len(actions):
-                if actions[k][0] == "rebuild":
-                    rebuild(actions[k][1], actions[k][2])
+                if actions[k][0] in ("rebuild", "correct"):
+                    (rebuild if actions[k][0] == "rebuild" else correct)(actions[k][1], actions[k][2])
                     k += 1
                     continue
                 run = []
@@ -339,6 +373,8 @@ class BodySlamPipeline:
                     run.append(actions[k])
                     k += 1
                 state["tsdf"].build_3D_map_batch([RGBDImage(fr_dev[i], dm_map[i - b0]) for (_, i, _) in run], intr, [pose for (_, _, pose) in run])
+                for (_, i, pose) in run:
+                    state["ledger"][i] = np.array(pose)
 
         pg = PoseGraph(solver=self.posegraph_solver)
         pg.device = self.dev.index or 0
@@ -453,7 +489,7 @@ class BodySlamPipeline:
                         pg.optimize()
                         extr[:] = update_global_extrinsic(pg.pose_graph)        # (in place: the caller's list)
                         if state["tsdf"] is not None and not all(np.array_equal(a_, b_) for a_, b_ in zip(before, extr)):
-                            actions.append(("rebuild", i, [p_.copy() for p_ in extr]))
+                            actions.append(("rebuild" if self.map_correction == "rebuild" else "correct", i, [p_.copy() for p_ in extr]))
                     elif state["tsdf"] is not None:
                         actions.append(("int", i, extr[-1].copy()))
                     if state["tsdf"] is not None and rebuild_every > 0 and i % rebuild_every == 0:

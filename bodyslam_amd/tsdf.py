@@ -194,6 +194,9 @@ class TSDF:
         n_units, n_touched, overflow = (int(v) for v in self.counters.cpu())
         if overflow:
             self.counters[2] = 0
+            if overflow == 3:          # tsdf_update_batch_kernel: the removal was skipped there, no weight went below 0
+                raise L.BodySlamHipError("TSDF: a frame was removed that the voxel never held (deintegrate / apply_batch need the images and the "
+                                         "extrinsic the frame was integrated with)")
             raise L.BodySlamHipError("TSDF: " + ("unit table full" if overflow == 1 else
                                                  f"a frame needed more than the {self.alloc_units} blocks that existed (reserve() more ahead of a "
                                                  f"stream, or raise max_units={self.max_units})"))
@@ -279,8 +282,12 @@ class TSDF:
         reservation) per 64 frames instead of three launches per frame.  Device images (torch tensors) are used in place."""
         n = len(rgbds)
         assert len(extrinsics) == n
-        if n == 0:
-            return
+        for a in range(0, n, BATCH_MAX):
+            self._batch_pass(rgbds[a:a + BATCH_MAX], intrinsic, extrinsics[a:a + BATCH_MAX], None)
+
+    def _batch_pass(self, chunk, intrinsic: "PinholeCameraIntrinsic", extrinsics, remove) -> None:
+        """one pass over the map for at most BATCH_MAX records: discovery, the 12-byte round trip that makes the blocks, the update.
+        remove = None: every record is added (bs_tsdf_integrate_batch); else a bool per record, True = taken out (bs_tsdf_update_batch)"""
         lib, st = L.load_library(), L.stream_ptr()
         if not self.slabs:
             self.reserve(1)
@@ -289,46 +296,69 @@ class TSDF:
             self.unit_mask = torch.zeros(self.max_units, dtype=torch.int64, device=self.dev)
             self.frames_dev = torch.zeros(BATCH_MAX * 256, dtype=torch.uint8, device=self.dev)      # BS_TSDF_FRAME_BYTES per frame
         K = np.array([intrinsic.fx, intrinsic.fy, intrinsic.cx, intrinsic.cy], dtype=np.float64)
+        m = len(chunk)
+        depth = [self._image(r.depth, torch.float32) for r in chunk]
+        has_color = chunk[0].color is not None
+        assert all((r.color is not None) == has_color for r in chunk), "either every frame of a batch has a colour image or none"
+        color = [self._image(r.color, torch.uint8) for r in chunk] if has_color else None
+        H, W = depth[0].shape
+        assert all(d.shape == (H, W) for d in depth)
+        E = np.ascontiguousarray(np.stack([np.asarray(self._np(e), dtype=np.float64) for e in extrinsics]).reshape(m, 16))
+        P = np.ascontiguousarray(np.linalg.inv(E.reshape(m, 4, 4)).reshape(m, 16))
+        dptr = np.array([d.data_ptr() for d in depth], dtype=np.uint64)
+        cptr = np.array([c.data_ptr() for c in color], dtype=np.uint64) if has_color else None
+        L.check(lib.bs_tsdf_frames_upload(dptr.ctypes.data_as(C.c_void_p), cptr.ctypes.data_as(C.c_void_p) if has_color else None,
+                                          K.ctypes.data_as(C.c_void_p), E.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p), m,
+                                          L.p(self.frames_dev), st), "bs_tsdf_frames_upload")
+        L.check(lib.bs_tsdf_touch_batch(L.p(self.frames_dev), m, H, W, self.stride, self.unit_length, self.sdf_trunc, L.p(self.table_keys),
+                                        L.p(self.table_fmask), self.table_cap, L.p(self.counters), st), "bs_tsdf_touch_batch")
+        # the one round trip of the batch: how many blocks the discovered units need
+        # (+ the overflow flag the discovery may have raised: 1 = unit table full)
+        need = torch.stack([self.counters[0].to(torch.int64), ((self.table_keys != -1) & (self.table_slots < 0)).sum(),
+                            self.counters[2].to(torch.int64)]).cpu()
+        if int(need[2]) == 1 or int(need[0]) + int(need[1]) > self.max_units:
+            # nothing of this batch has been integrated yet: clear the flag and the batch's frame bits, then refuse
+            self.counters[2] = 0
+            self.table_fmask.zero_()
+            raise L.BodySlamHipError("TSDF: " + ("unit table full" if int(need[2]) == 1 else
+                                                 f"the batch needs {int(need[0]) + int(need[1])} volume units, more than max_units={self.max_units}")
+                                     + "; construct TSDF with a larger max_units")
+        self.reserve(int(need[0]) + int(need[1]))
+        args = (L.p(self.frames_dev), m, H, W, L.p(self.table_keys), L.p(self.table_slots), L.p(self.table_fmask), self.table_cap, L.p(self.unit_index),
+                self.alloc_units, L.p(self.counters), L.p(self.touched), L.p(self.unit_mask), L.p(self.slab_base), self.slab_units, self.res,
+                self.voxel_length, self.sdf_trunc)
+        if remove is None:
+            L.check(lib.bs_tsdf_integrate_batch(*args, st), "bs_tsdf_integrate_batch")
+            removed = 0
+        else:
+            mask = sum(1 << f for f in range(m) if remove[f])
+            L.check(lib.bs_tsdf_update_batch(*args, mask, st), "bs_tsdf_update_batch")
+            removed = sum(1 for f in range(m) if remove[f])
+        self.frames_integrated += m - 2 * removed
+        self._frames_since_sync += m
+        # (the assignment cannot run out of blocks after the reserve above; its flag is still collected by sync())
+        # every discovered unit has a block now (unless the map is full: sync() reports that), so the count is known without
+        # another round trip -- extract_pcd / extract_mesh right after a batch see the whole map
+        self.n_units = min(int(need[0]) + int(need[1]), self.alloc_units)
+
+    def apply_batch(self, rgbds: Sequence["RGBDImage"], intrinsic: "PinholeCameraIntrinsic", extrinsics, remove: Sequence[bool]) -> None:
+        """Records with a sign: ``remove[k]`` False integrates record k as ``build_3D_map_batch`` does, True takes it out of the map
+        again -- it must carry the images and the extrinsic it was integrated with.  Records are applied in the given order, in chunks
+        of at most BS_TSDF_BATCH_MAX consecutive records; each chunk is one discovery, one 12-byte round trip and one pass that loads
+        every touched voxel once (csrc/tsdf.hip, "frames taken out again"), with ``build_3D_map_batch``'s capacity checks before
+        anything of the chunk is applied.  Units are never freed: a unit whose voxels all returned to weight 0 keeps its (all-zero)
+        block, which extract_pcd / extract_mesh / raycast ignore.  Removing a frame the map never held is reported by ``sync()``."""
+        n = len(rgbds)
+        assert len(extrinsics) == n and len(remove) == n
+        remove = [bool(r) for r in remove]
         for a in range(0, n, BATCH_MAX):
-            chunk = rgbds[a:a + BATCH_MAX]
-            m = len(chunk)
-            depth = [self._image(r.depth, torch.float32) for r in chunk]
-            has_color = chunk[0].color is not None
-            assert all((r.color is not None) == has_color for r in chunk), "either every frame of a batch has a colour image or none"
-            color = [self._image(r.color, torch.uint8) for r in chunk] if has_color else None
-            H, W = depth[0].shape
-            assert all(d.shape == (H, W) for d in depth)
-            E = np.ascontiguousarray(np.stack([np.asarray(self._np(e), dtype=np.float64) for e in extrinsics[a:a + m]]).reshape(m, 16))
-            P = np.ascontiguousarray(np.linalg.inv(E.reshape(m, 4, 4)).reshape(m, 16))
-            dptr = np.array([d.data_ptr() for d in depth], dtype=np.uint64)
-            cptr = np.array([c.data_ptr() for c in color], dtype=np.uint64) if has_color else None
-            L.check(lib.bs_tsdf_frames_upload(dptr.ctypes.data_as(C.c_void_p), cptr.ctypes.data_as(C.c_void_p) if has_color else None,
-                                              K.ctypes.data_as(C.c_void_p), E.ctypes.data_as(C.c_void_p), P.ctypes.data_as(C.c_void_p), m,
-                                              L.p(self.frames_dev), st), "bs_tsdf_frames_upload")
-            L.check(lib.bs_tsdf_touch_batch(L.p(self.frames_dev), m, H, W, self.stride, self.unit_length, self.sdf_trunc, L.p(self.table_keys),
-                                            L.p(self.table_fmask), self.table_cap, L.p(self.counters), st), "bs_tsdf_touch_batch")
-            # the one round trip of the batch: how many blocks the discovered units need
-            # (+ the overflow flag the discovery may have raised: 1 = unit table full)
-            need = torch.stack([self.counters[0].to(torch.int64), ((self.table_keys != -1) & (self.table_slots < 0)).sum(),
-                                self.counters[2].to(torch.int64)]).cpu()
-            if int(need[2]) == 1 or int(need[0]) + int(need[1]) > self.max_units:
-                # nothing of this batch has been integrated yet: clear the flag and the batch's frame bits, then refuse
-                self.counters[2] = 0
-                self.table_fmask.zero_()
-                raise L.BodySlamHipError("TSDF: " + ("unit table full" if int(need[2]) == 1 else
-                                                     f"the batch needs {int(need[0]) + int(need[1])} volume units, more than max_units={self.max_units}")
-                                         + "; construct TSDF with a larger max_units")
-            self.reserve(int(need[0]) + int(need[1]))
-            L.check(lib.bs_tsdf_integrate_batch(L.p(self.frames_dev), m, H, W, L.p(self.table_keys), L.p(self.table_slots), L.p(self.table_fmask),
-                                                self.table_cap, L.p(self.unit_index), self.alloc_units, L.p(self.counters), L.p(self.touched),
-                                                L.p(self.unit_mask), L.p(self.slab_base), self.slab_units, self.res, self.voxel_length, self.sdf_trunc,
-                                                st), "bs_tsdf_integrate_batch")
-            self.frames_integrated += m
-            self._frames_since_sync += m
-            # (the assignment cannot run out of blocks after the reserve above; its flag is still collected by sync())
-            # every discovered unit has a block now (unless the map is full: sync() reports that), so the count is known without
-            # another round trip -- extract_pcd / extract_mesh right after a batch see the whole map
-            self.n_units = min(int(need[0]) + int(need[1]), self.alloc_units)
+            self._batch_pass(rgbds[a:a + BATCH_MAX], intrinsic, extrinsics[a:a + BATCH_MAX], remove[a:a + BATCH_MAX])
+
+    def deintegrate(self, rgbd: "RGBDImage", intrinsic: "PinholeCameraIntrinsic", extrinsic, sync: bool = True) -> None:
+        """take one frame out of the map: the inverse of ``build_3D_map(rgbd, intrinsic, extrinsic)`` with the same arguments"""
+        self.apply_batch([rgbd], intrinsic, [extrinsic], [True])
+        if sync:
+            self.sync()
 
     def _image(self, x, dtype) -> torch.Tensor:
         t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))

@@ -436,6 +436,17 @@ int bs_tsdf_integrate_batch(const void* frames_dev, int32_t n_frames, int32_t H,
                             void* table_fmask, int32_t table_cap, int32_t* unit_index, int32_t max_units, int32_t* counters, int32_t* touched,
                             void* unit_mask, const int64_t* slab_base, int32_t slab_units, int32_t res, double voxel_length, double sdf_trunc,
                             void* stream);
+/* Frames taken out again (map correction after a pose-graph update; Open3D has no such operation): bs_tsdf_integrate_batch
+ * with a sign per record.  Bit f of remove_mask set = record f is removed from the running means, clear = it is added; records are
+ * applied to a voxel in ascending order in registers, the voxel is loaded once and stored once.  A removed record must carry the
+ * extrinsic and images it was integrated with: the observation is then recomputed bit for bit and undone (w1 = w - 1; values
+ * (v w - x) / w1).  A voxel whose weight returns to 0 becomes five +0.0f, as in a fresh block; a removal that finds weight < 1 is
+ * skipped and sets counters[2] = 3 (sticky, like 1 and 2).  Units are never freed.  Preceded by bs_tsdf_frames_upload and
+ * bs_tsdf_touch_batch exactly as bs_tsdf_integrate_batch is. */
+int bs_tsdf_update_batch(const void* frames_dev, int32_t n_frames, int32_t H, int32_t W, const void* table_keys, int32_t* table_slots,
+                         void* table_fmask, int32_t table_cap, int32_t* unit_index, int32_t max_units, int32_t* counters, int32_t* touched,
+                         void* unit_mask, const int64_t* slab_base, int32_t slab_units, int32_t res, double voxel_length, double sdf_trunc,
+                         uint64_t remove_mask, void* stream);
 int bs_tsdf_extract(const int32_t* unit_index, int32_t units, const void* table_keys, const int32_t* table_slots, int32_t table_cap,
                     const int64_t* slab_base, int32_t slab_units, int32_t res, double voxel_length, int32_t* unit_count,
                     const int64_t* unit_offset, float* points, float* colors, float* normals, void* stream);
