@@ -160,6 +160,15 @@ _SIGS = {
     "bs_pg_solve": [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7,
     "bs_pg_update": [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4,
+    # cloud-to-cloud distances (csrc/pointcloud.hip); lo, hi, dims, thresholds and the affine are pointers to host arrays
+    "bs_pc_bounds": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_pc_grid_count": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_grid_scatter": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_pc_query_grid": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int32,
+                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_query_brute": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_transform": [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_stats": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
 }
 EXPORTS = sorted(list(_SIGS) + ["bs_last_error"])
 
@@ -836,3 +845,96 @@ def pg_update(X, delta, Xn, terms, xnorm2=None):
     _f64(X, delta, Xn, terms, xnorm2)
     assert X.numel() == N * 16 and Xn.numel() == N * 16 and delta.numel() == N * 6 and terms.numel() >= N
     check(load_library().bs_pg_update(p(X), p(delta), N, p(Xn), p(terms), p(xnorm2), stream_ptr()), "bs_pg_update")
+
+
+PC_MAX_CELLS, PC_MAX_THRESHOLDS, PC_STATS_FIELDS, PC_STATS_WORKSPACE_BYTES = 1 << 24, 8, 16, 163968
+
+
+def _pts(*ts):
+    for t in ts:
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 3, "fp32 contiguous [n, 3] device tensors"
+
+
+def _host(a, dtype, n):
+    """a host array of n `dtype` values as (the array, which must stay alive over the call; its address)"""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+    assert a.size == n, (a.size, n)
+    return a, a.ctypes.data
+
+
+def pc_bounds(points, out):
+    """points fp32 [n, 3], out int32 / uint32 storage [8], both on the device (include/bodyslam_hip.h)"""
+    _pts(points)
+    assert out.numel() == 8 and out.element_size() == 4 and out.is_cuda and out.is_contiguous()
+    check(load_library().bs_pc_bounds(p(points), points.shape[0], p(out), stream_ptr()), "bs_pc_bounds")
+
+
+def pc_grid_count(points, lo, hi, cell_size, dims, counts):
+    _pts(points)
+    _i32(counts)
+    (lo_, lo_p), (hi_, hi_p), (d_, d_p) = _host(lo, "float32", 3), _host(hi, "float32", 3), _host(dims, "int32", 3)
+    assert counts.numel() >= int(d_[0]) * int(d_[1]) * int(d_[2])
+    check(load_library().bs_pc_grid_count(p(points), points.shape[0], lo_p, hi_p, float(cell_size), d_p, p(counts), stream_ptr()), "bs_pc_grid_count")
+
+
+def pc_grid_scatter(points, lo, hi, cell_size, dims, cursor, records, n_records):
+    """cursor int32 [cells] (a copy of the exclusive scan; advanced by the call), records fp32 [>= n_records, 4]"""
+    _pts(points)
+    _i32(cursor)
+    assert records.dtype == torch.float32 and records.is_cuda and records.is_contiguous() and records.dim() == 2 and records.shape[1] == 4
+    (lo_, lo_p), (hi_, hi_p), (d_, d_p) = _host(lo, "float32", 3), _host(hi, "float32", 3), _host(dims, "int32", 3)
+    assert cursor.numel() >= int(d_[0]) * int(d_[1]) * int(d_[2]) and 0 <= n_records <= records.shape[0]
+    check(load_library().bs_pc_grid_scatter(p(points), points.shape[0], lo_p, hi_p, float(cell_size), d_p, p(cursor), int(n_records), p(records),
+                                            stream_ptr()), "bs_pc_grid_scatter")
+
+
+def pc_query_grid(records, n_records, cell_start, lo, hi, cell_size, dims, source, max_distance, shell_cap, dist, index, fallback_list, fallback_count):
+    """records fp32 [>= max(n_records, 1), 4] (a tensor of no elements has no address to hand over)"""
+    _pts(source)
+    _i32(cell_start, index, fallback_list, fallback_count)
+    m = source.shape[0]
+    (lo_, lo_p), (hi_, hi_p), (d_, d_p) = _host(lo, "float32", 3), _host(hi, "float32", 3), _host(dims, "int32", 3)
+    assert records.dtype == torch.float32 and records.is_cuda and records.is_contiguous() and records.dim() == 2 and records.shape[1] == 4
+    assert cell_start.numel() == int(d_[0]) * int(d_[1]) * int(d_[2]) + 1 and 0 <= n_records <= records.shape[0]
+    assert dist.dtype == torch.float32 and dist.is_cuda and dist.is_contiguous() and dist.numel() == m and index.numel() == m
+    assert fallback_list.numel() >= m and fallback_count.numel() >= 1
+    check(load_library().bs_pc_query_grid(p(records), p(cell_start), int(n_records), lo_p, hi_p, float(cell_size), d_p, p(source), m,
+                                          float(max_distance), int(shell_cap), p(dist), p(index), p(fallback_list), p(fallback_count), stream_ptr()),
+          "bs_pc_query_grid")
+
+
+def pc_query_brute(records, n_records, source, fallback_list, m, max_distance, keys, dist, index):
+    """fallback_list: int32 device tensor of m source indices, or None for all m = source.shape[0] sources; keys: int64 [>= m] scratch"""
+    _pts(source)
+    _i32(index)
+    assert records.dtype == torch.float32 and records.is_cuda and records.is_contiguous() and records.dim() == 2 and records.shape[1] == 4
+    assert dist.dtype == torch.float32 and dist.is_cuda and dist.is_contiguous() and dist.numel() == source.shape[0] and index.numel() == source.shape[0]
+    assert keys.dtype == torch.int64 and keys.is_cuda and keys.is_contiguous() and keys.numel() >= m and 0 <= n_records <= records.shape[0]
+    if fallback_list is None:
+        assert m == source.shape[0]
+    else:
+        _i32(fallback_list)
+        assert 1 <= m <= fallback_list.numel()
+    check(load_library().bs_pc_query_brute(p(records), int(n_records), p(source), p(fallback_list), int(m), float(max_distance), p(keys), p(dist),
+                                           p(index), stream_ptr()), "bs_pc_query_brute")
+
+
+def pc_transform(source, affine, out):
+    """source fp32 / fp64 [n, 3], affine: 12 host doubles (rows of [A | t]), out fp32 [n, 3]"""
+    _pts(out)
+    assert source.dtype in (torch.float32, torch.float64) and source.is_cuda and source.is_contiguous() and tuple(source.shape) == tuple(out.shape)
+    a_, a_p = _host(affine, "float64", 12)
+    check(load_library().bs_pc_transform(p(source), F32 if source.dtype == torch.float32 else F64, source.shape[0], a_p, p(out), stream_ptr()),
+          "bs_pc_transform")
+
+
+def pc_stats(dist, thresholds, workspace, out):
+    """dist fp32 [n] (device); thresholds: up to PC_MAX_THRESHOLDS host floats; workspace: uint8 device tensor of PC_STATS_WORKSPACE_BYTES;
+    out fp64 [PC_STATS_FIELDS] (device)"""
+    assert dist.dtype == torch.float32 and dist.is_cuda and dist.is_contiguous() and dist.dim() == 1
+    assert out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and out.numel() == PC_STATS_FIELDS
+    n_tau = len(thresholds)
+    t_, t_p = _host(thresholds, "float32", n_tau)
+    check(load_library().bs_pc_stats(p(dist), dist.numel(), t_p if n_tau else None, n_tau, p(workspace), workspace.numel() * workspace.element_size(),
+                                     p(out), stream_ptr()), "bs_pc_stats")

@@ -1,4 +1,5 @@
-"""Evaluation with the reference's two protocols, on the device: depth maps (MDEM) and trajectories (MPEM).
+"""Evaluation on the device: depth maps (the reference's MDEM protocol), trajectories (its MPEM protocol) and the map against ground-truth
+geometry (cloud-to-cloud distances).
 
 Depth.  The reference judges its depth module by BodySLAM_not_refactored/EVALUATION/MDEM_eval.py (compute_metrics_for, :130-259) over the
 MDEM_Metrics functions of EVALUATION/evaluation_metrics.py:17-102: per frame the GT is masked by dataset, the prediction is scaled by
@@ -10,6 +11,11 @@ Trajectories.  The reference judges its pose module by MPEM_Metrics.compute_pose
 align_origin, align(correct_scale=True), then ATE, RTE and RRE; while training it monitors its own compute_ARE_and_ATE /
 compute_RRE_and_RTE (MPEM/training_utils.py:473-585).  evaluate_trajectory computes either with one call of bs_trajectory_metrics over
 poses that can stay in device memory (SequenceResult.g_abs); similarity_transform is the Umeyama fit on its own (bs_similarity_fit).
+
+Reconstruction.  SCARED ships structured-light point clouds and EndoSLAM 3-D scans (the reference reads both, DatasetLoader.read_SCARED /
+read_EndoSlam); its mapping module measures clouds against each other with Open3D's compute_point_cloud_distance
+(3DM/mapping_module.py:45,48,62).  evaluate_reconstruction computes accuracy, completeness, chamfer distance and precision / recall /
+F-score from the two nearest-neighbour distance arrays (bodyslam_amd/pointcloud.py), which stay in device memory.
 
 There is no CPU fallback: without a GPU the calls raise BodySlamHipError.
 """
@@ -430,3 +436,143 @@ def similarity_transform(source, target) -> Tuple[np.ndarray, float, np.ndarray]
     degenerate point set; similarity_fit_record returns the rank next to the fit."""
     r = similarity_fit_record(source, target)
     return r[:9].reshape(3, 3).copy(), float(r[9]), r[10:13].copy()
+
+
+# ---- reconstruction ---------------------------------------------------------------------------------------------------------------------
+DISTANCE_STAT_NAMES = ("mean", "median", "rmse", "max")
+
+
+@dataclass
+class DistanceStats:
+    """mean, median, rmse and max of the matched (finite) nearest-neighbour distances of one direction, in the units of the clouds; NaN
+    when nothing was matched"""
+    mean: float
+    median: float
+    rmse: float
+    max: float
+
+
+@dataclass
+class ReconstructionMetrics:
+    """accuracy: pred -> gt; completeness: gt -> pred; chamfer: the mean of the two means.  Per threshold tau (thresholds, as fp32 values):
+    precision = the fraction of pred points with distance < tau, recall = that of gt points, fscore = 2 P R / (P + R), 0 when both are 0.
+    The fractions are over the points with finite coordinates; a point without a neighbour within max_distance (n_unmatched_*) is a
+    miss for every tau and enters neither mean, median, rmse nor max."""
+    accuracy: DistanceStats
+    completeness: DistanceStats
+    chamfer: float
+    thresholds: Tuple[float, ...]
+    precision: np.ndarray
+    recall: np.ndarray
+    fscore: np.ndarray
+    n_pred: int
+    n_gt: int
+    n_unmatched_pred: int
+    n_unmatched_gt: int
+
+    def as_dict(self) -> Dict[str, float]:
+        out: Dict[str, float] = {}
+        for side, st in (("accuracy", self.accuracy), ("completeness", self.completeness)):
+            for k in DISTANCE_STAT_NAMES:
+                out[f"{side}_{k}"] = float(getattr(st, k))
+        out["chamfer"] = float(self.chamfer)
+        for i, tau in enumerate(self.thresholds):
+            for k in ("precision", "recall", "fscore"):
+                out[f"{k}@{tau!r}"] = float(getattr(self, k)[i])
+        for k in ("n_pred", "n_gt", "n_unmatched_pred", "n_unmatched_gt"):
+            out[k] = int(getattr(self, k))
+        return out
+
+    def write_csv(self, path: str) -> str:
+        """A Metric,Value file, one row per entry of as_dict(), csv.DictWriter as TrajectoryMetrics.write_csv writes its file."""
+        with open(path, "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=["Metric", "Value"])
+            w.writeheader()
+            for k, v in self.as_dict().items():
+                w.writerow({"Metric": k, "Value": v})
+        return path
+
+
+def _check_thresholds(thresholds) -> Tuple[float, ...]:
+    try:
+        taus = tuple(float(np.float32(v)) for v in thresholds)
+    except (TypeError, ValueError):
+        raise ValueError(f"thresholds {thresholds!r}: expected a sequence of numbers") from None
+    if len(taus) > L.PC_MAX_THRESHOLDS or any(not (v > 0.0 and math.isfinite(v)) for v in taus):
+        raise ValueError(f"thresholds {thresholds!r}: expected at most {L.PC_MAX_THRESHOLDS} positive numbers")
+    return taus
+
+
+def distance_stats_record(dist: torch.Tensor, thresholds: Sequence[float] = ()) -> np.ndarray:
+    """The PC_STATS_FIELDS doubles of bs_pc_stats (include/bodyslam_hip.h) over a fp32 [n] device tensor of distances: n, finite, infinite
+    and NaN entries, sum, sum of squares, max, exact median, the count of d < tau per threshold.  The same bits in every run."""
+    taus = _check_thresholds(thresholds)
+    if not isinstance(dist, torch.Tensor) or dist.dtype != torch.float32 or dist.dim() != 1 or dist.numel() < 1:
+        raise ValueError("dist: expected a non-empty fp32 torch tensor [n]")
+    if not torch.cuda.is_available():
+        L.init(0)                              # raises BodySlamHipError: no CPU fallback
+    dev = dist.device if dist.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        L.init(dev.index)
+        ws = torch.empty(L.PC_STATS_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
+        out = torch.empty(L.PC_STATS_FIELDS, dtype=torch.float64, device=dev)
+        L.pc_stats(dist.to(dev).contiguous(), taus, ws, out)
+        return out.cpu().numpy()
+
+
+def _distance_stats(rec: np.ndarray) -> DistanceStats:
+    n = rec[1]
+    if n == 0:
+        return DistanceStats(math.nan, math.nan, math.nan, math.nan)
+    return DistanceStats(float(rec[4] / n), float(rec[7]), float(math.sqrt(rec[5] / n)), float(rec[6]))
+
+
+def evaluate_reconstruction(pred, gt, thresholds: Sequence[float] = (0.001, 0.002, 0.005), transform=None,
+                            max_distance: Optional[float] = None) -> ReconstructionMetrics:
+    """The reconstruction `pred` against the ground-truth geometry `gt`, by nearest-neighbour distances both ways.
+
+    pred, gt: numpy arrays or torch tensors [n, 3] (fp32, or fp64, which is rounded to fp32 once), host or device; a tsdf.PointCloud; a
+    tsdf.TriangleMesh (its vertices).  pred may also be a tsdf.TSDF or tsdf.MAP: its extract_pcd(host=False) is evaluated where it lies.
+    transform: a 4 x 4, or (R, s, t) as similarity_transform returns it, applied to pred on the device as s R p + t in fp64 and rounded
+    once to fp32 -- how a monocular map is put into the ground truth's frame, by the similarity of its trajectory (evaluate_trajectory,
+    similarity_transform).  No alignment is searched for here (no ICP).  thresholds: at most 8, compared as fp32 values.
+    max_distance: a point without a neighbour within it is unmatched (ReconstructionMetrics).  Two runs on the same arrays return the
+    same bits.  A TSDF or MAP hands over its points in the order its extraction's atomics gave, which differs from call to call: counts,
+    max, median, precision and recall are then still exact, the means and rmse agree to the rounding of an fp64 sum (n 2^-53 relative)."""
+    from . import pointcloud as PC
+    from .tsdf import MAP, TSDF
+    taus = _check_thresholds(thresholds)
+    PC._check_max_distance(max_distance)
+    A = None if transform is None else PC.affine_rows(transform)
+    if not isinstance(pred, (TSDF, MAP)):
+        p = PC.as_points(pred, "pred")
+    g = PC.as_points(gt, "gt")
+    if not torch.cuda.is_available():
+        L.init(0)                              # raises BodySlamHipError: no CPU fallback
+    if isinstance(pred, (TSDF, MAP)):
+        pts = pred.extract_pcd(host=False).points
+        if pts.shape[0] == 0:
+            raise ValueError("pred: the map has no surface points")
+        p = PC.as_points(pts, "pred")
+    cuda = [t.device for t in (p, g) if t.is_cuda]
+    dev = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        L.init(dev.index)
+        p, g = p.to(dev).contiguous(), g.to(dev).to(torch.float32).contiguous()
+        if A is not None:
+            moved = torch.empty(p.shape[0], 3, dtype=torch.float32, device=dev)
+            L.pc_transform(p, A, moved)
+            p = moved
+        p = p.to(torch.float32)
+        d_pg, _ = PC.NearestNeighbours(g).query(p, max_distance=max_distance)
+        d_gp, _ = PC.NearestNeighbours(p).query(g, max_distance=max_distance)
+        ra, rc = distance_stats_record(d_pg, taus), distance_stats_record(d_gp, taus)
+    acc, comp = _distance_stats(ra), _distance_stats(rc)
+    k = len(taus)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        prec = ra[8:8 + k] / (ra[1] + ra[2])
+        rec = rc[8:8 + k] / (rc[1] + rc[2])
+        f = np.where(prec + rec > 0.0, 2.0 * prec * rec / (prec + rec), 0.0)
+    f = np.where(np.isnan(prec) | np.isnan(rec), math.nan, f)
+    return ReconstructionMetrics(accuracy=acc, completeness=comp, chamfer=(acc.mean + comp.mean) / 2.0, thresholds=taus, precision=prec, recall=rec,
+                                 fscore=f, n_pred=int(ra[0]), n_gt=int(rc[0]), n_unmatched_pred=int(ra[2]), n_unmatched_gt=int(rc[2]))

@@ -1,0 +1,232 @@
+"""Cloud-to-cloud distances on the device: the exact nearest neighbour of every point of one cloud in another.
+
+The primitive is Open3D's ``PointCloud.compute_point_cloud_distance``, which the reference calls at
+BodySLAM_not_refactored/3DM/mapping_module.py:45,48,62.  Open3D is not vendored: the meaning is restated from its documentation and
+parity with Open3D is unpinned.  The arithmetic is fixed (include/bodyslam_hip.h, tests/_pointcloud_ref.py): in fp32 without contraction
+d2 = (dx dx + dy dy) + dz dz, the neighbour is the lexicographic minimum of (d2, index in the target as given), the distance sqrtf(d2).
+So the answer does not depend on the spatial index at all -- not on the cell size, not on the order points land in a cell -- and
+``method="grid"`` and ``method="brute"`` return the same bits.
+
+``NearestNeighbours`` builds a uniform grid over the finite target points once (csrc/pointcloud.hip: bounds, counts per cell, a scan,
+a scatter into 16-byte records); ``query`` walks the shells of cells around every source point and hands the few points that are far
+from everything to the brute-force kernel.  There is no CPU fallback: without a GPU the calls raise BodySlamHipError.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+SHELL_CAP = 8               # a source still searching after this shell goes to the brute-force kernel (a starting point, not tuned)
+METHODS = ("grid", "brute")
+
+
+def as_points(x, what: str) -> torch.Tensor:
+    """-> fp32 or fp64 torch tensor [n, 3] on whatever device x is on.  x: a numpy array or torch tensor [n, 3], fp32 or fp64; a
+    tsdf.PointCloud (its points); a tsdf.TriangleMesh (its vertices).  ValueError on anything else."""
+    from .tsdf import PointCloud, TriangleMesh
+    if isinstance(x, PointCloud):
+        x = x.points
+    elif isinstance(x, TriangleMesh):
+        x = x.vertices
+    if isinstance(x, np.ndarray):
+        if x.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{what}: dtype {x.dtype}, expected float32 or float64")
+        t = torch.from_numpy(np.ascontiguousarray(x))
+    elif isinstance(x, torch.Tensor):
+        if x.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{what}: dtype {x.dtype}, expected torch.float32 or torch.float64")
+        t = x.detach()
+    else:
+        raise ValueError(f"{what}: expected a numpy array, a torch tensor, a PointCloud or a TriangleMesh, got {type(x).__name__}")
+    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError(f"{what}: shape {tuple(t.shape)}, expected a non-empty [n, 3]")
+    if t.shape[0] >= 2 ** 31:
+        raise ValueError(f"{what}: {t.shape[0]} points: the indices are int32")
+    return t
+
+
+def _check_cell_size(cell_size) -> Optional[float]:
+    if cell_size is None:
+        return None
+    if isinstance(cell_size, bool) or not isinstance(cell_size, (int, float, np.integer, np.floating)):
+        raise ValueError(f"cell_size {cell_size!r}: expected None or a positive number")
+    h = float(np.float32(cell_size))
+    if not (h > 0.0 and math.isfinite(h)):
+        raise ValueError(f"cell_size {cell_size!r}: expected None or a positive number (finite and non-zero in fp32)")
+    return h
+
+
+def _check_max_distance(max_distance) -> float:
+    if max_distance is None:
+        return math.inf
+    if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float, np.integer, np.floating)):
+        raise ValueError(f"max_distance {max_distance!r}: expected None or a number >= 0")
+    v = float(np.float32(max_distance))
+    if not v >= 0.0:
+        raise ValueError(f"max_distance {max_distance!r}: expected None or a number >= 0")
+    return v
+
+
+def grid_dims(lo: np.ndarray, hi: np.ndarray, h: float) -> np.ndarray:
+    """cells per axis of the grid over [lo, hi] (fp32 [3] each) with edge h, in the kernels' fp32 arithmetic: floor((hi - lo) / h) + 1"""
+    f32 = np.float32
+    with np.errstate(over="ignore"):
+        q = np.floor((hi.astype(f32) - lo.astype(f32)) / f32(h))
+    return np.minimum(q, f32(2.0 ** 30)).astype(np.int64) + 1
+
+
+def n_cells(dims) -> int:
+    return int(dims[0]) * int(dims[1]) * int(dims[2])
+
+
+def default_cell_size(lo: np.ndarray, hi: np.ndarray, n: int) -> float:
+    """The default edge: over the k axes of positive extent, h = (the product of those extents / n)^(1 / k) -- about as many cells as
+    points -- rounded to fp32, then grown by factors of 1.25 until the grid holds at most 2^24 cells.  No positive extent (one
+    point, or all points equal): 1.0, a single cell."""
+    ext = (hi.astype(np.float32) - lo.astype(np.float32)).astype(np.float64)
+    pos = ext[(ext > 0.0) & np.isfinite(ext)]
+    if pos.size == 0 or n < 1:
+        return 1.0
+    h = float(np.float32(np.exp((np.sum(np.log(pos)) - np.log(n)) / pos.size)))
+    h = max(h, float(np.finfo(np.float32).tiny))
+    while n_cells(grid_dims(lo, hi, h)) > L.PC_MAX_CELLS:
+        h = float(np.float32(h * 1.25))
+    return h
+
+
+def _decode_bounds(raw: np.ndarray) -> Tuple[np.ndarray, np.ndarray, int]:
+    """bs_pc_bounds' 8 words -> (lo fp32 [3], hi fp32 [3], finite points)"""
+    o = raw.astype(np.uint32).copy()
+    o[3:6] = ~o[3:6]
+    b = np.where((o[:6] & np.uint32(0x80000000)) != 0, o[:6] & np.uint32(0x7fffffff), ~o[:6]).astype(np.uint32)
+    v = b.view(np.float32)
+    return v[:3].copy(), v[3:6].copy(), int(o[6])
+
+
+class NearestNeighbours:
+    """The index over `target`, built once; ``query`` may be called any number of times.
+
+    target: numpy array or torch tensor [n, 3], fp32 or fp64 (fp64 is rounded to fp32 once, before anything else: the neighbours are
+    those of the rounded points), host or device; a tsdf.PointCloud; a tsdf.TriangleMesh (its vertices).  Non-finite target points are
+    left out; indices always refer to `target` as given.  cell_size: the grid's edge, None = default_cell_size; a ValueError if the grid
+    would exceed 2^24 cells.  The cell size changes the time, never the result."""
+
+    def __init__(self, target, cell_size: Optional[float] = None, device: int = 0):
+        t = as_points(target, "target")
+        h = _check_cell_size(cell_size)
+        if not torch.cuda.is_available():
+            L.init(0)                              # raises BodySlamHipError: no CPU fallback
+        self.dev = t.device if t.is_cuda else torch.device("cuda", int(device))
+        with torch.cuda.device(self.dev):
+            L.init(self.dev.index)
+            self.target = t.to(self.dev).to(torch.float32).contiguous()
+            raw = torch.empty(8, dtype=torch.int32, device=self.dev)
+            L.pc_bounds(self.target, raw)
+            lo, hi, n_finite = _decode_bounds(raw.cpu().numpy().view(np.uint32))
+            if n_finite == 0:
+                lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
+            self.lo, self.hi, self.n_finite = lo, hi, n_finite
+            self.cell_size = default_cell_size(lo, hi, n_finite) if h is None else h
+            dims = grid_dims(lo, hi, self.cell_size)
+            if n_cells(dims) > L.PC_MAX_CELLS:
+                raise ValueError(f"cell_size {self.cell_size}: a grid of {dims[0]} x {dims[1]} x {dims[2]} cells, at most 2^24")
+            self.dims = dims.astype(np.int32)
+            cells = n_cells(dims)
+            counts = torch.zeros(cells, dtype=torch.int32, device=self.dev)
+            self.records = torch.empty(max(n_finite, 1), 4, dtype=torch.float32, device=self.dev)       # rows 0 .. n_finite - 1
+            self.cell_start = torch.zeros(cells + 1, dtype=torch.int32, device=self.dev)
+            if n_finite:
+                L.pc_grid_count(self.target, lo, hi, self.cell_size, self.dims, counts)
+                self.cell_start[1:] = torch.cumsum(counts, 0).to(torch.int32)                  # the scan is plumbing: integer, exact
+                cursor = self.cell_start[:-1].clone()
+                L.pc_grid_scatter(self.target, lo, hi, self.cell_size, self.dims, cursor, self.records, n_finite)
+
+    def __len__(self) -> int:
+        return int(self.target.shape[0])
+
+    def query(self, source, max_distance: Optional[float] = None, method: str = "grid") -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (distance fp32 [n], index int32 [n]), device tensors: for every source point its nearest target point.
+
+        source: as `target` (fp64 is rounded to fp32 once).  A source point with a non-finite coordinate gets (NaN, -1); without a finite
+        target point every finite source gets (+inf, -1).  max_distance: a source whose distance is > max_distance (compared in fp32)
+        gets (+inf, -1).  method: "grid" (the index; sources far from every target are finished by brute force) or "brute" (brute force
+        for all: the path for small targets and the cross-check) -- the same bits either way."""
+        if method not in METHODS:
+            raise ValueError(f"unknown method {method!r}: one of {METHODS}")
+        md = _check_max_distance(max_distance)
+        s = as_points(source, "source")
+        with torch.cuda.device(self.dev):
+            s = s.to(self.dev).to(torch.float32).contiguous()
+            m = int(s.shape[0])
+            dist = torch.empty(m, dtype=torch.float32, device=self.dev)
+            index = torch.empty(m, dtype=torch.int32, device=self.dev)
+            if method == "grid":
+                fb_list = torch.empty(m, dtype=torch.int32, device=self.dev)
+                fb_count = torch.empty(1, dtype=torch.int32, device=self.dev)
+                L.pc_query_grid(self.records, self.n_finite, self.cell_start, self.lo, self.hi, self.cell_size, self.dims, s, md, SHELL_CAP, dist, index, fb_list,
+                                fb_count)
+                n_fb = int(fb_count.cpu())
+                if n_fb:
+                    keys = torch.empty(n_fb, dtype=torch.int64, device=self.dev)
+                    L.pc_query_brute(self.records, self.n_finite, s, fb_list, n_fb, md, keys, dist, index)
+                self.last_fallback = n_fb
+            else:
+                keys = torch.empty(m, dtype=torch.int64, device=self.dev)
+                L.pc_query_brute(self.records, self.n_finite, s, None, m, md, keys, dist, index)
+        return dist, index
+
+
+def point_cloud_distance(source, target, cell_size: Optional[float] = None, device: int = 0, max_distance: Optional[float] = None,
+                         method: str = "grid") -> Tuple[torch.Tensor, torch.Tensor]:
+    """NearestNeighbours(target, cell_size, device).query(source, max_distance, method) in one call."""
+    if method not in METHODS:
+        raise ValueError(f"unknown method {method!r}: one of {METHODS}")
+    _check_max_distance(max_distance)
+    as_points(source, "source")
+    return NearestNeighbours(target, cell_size=cell_size, device=device).query(source, max_distance=max_distance, method=method)
+
+
+def transform_points(points, transform) -> torch.Tensor:
+    """s R p + t on the device in fp64, rounded once to fp32 -> fp32 [n, 3] device tensor.  transform: a 4 x 4 (its top three rows are
+    applied) or (R [3, 3], s, t [3]) as evaluation.similarity_transform returns it."""
+    A = affine_rows(transform)
+    p = as_points(points, "points")
+    if not torch.cuda.is_available():
+        L.init(0)                              # raises BodySlamHipError: no CPU fallback
+    dev = p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        L.init(dev.index)
+        p = p.to(dev).contiguous()
+        out = torch.empty(p.shape[0], 3, dtype=torch.float32, device=dev)
+        L.pc_transform(p, A, out)
+    return out
+
+
+def affine_rows(transform) -> np.ndarray:
+    """-> float64 [3, 4] = [s R | t]; ValueError on anything that is neither a 4 x 4 nor (R, s, t)"""
+    if isinstance(transform, (tuple, list)) and len(transform) == 3:
+        R, s, t = transform
+        R, t = np.asarray(_np(R), dtype=np.float64), np.asarray(_np(t), dtype=np.float64).reshape(-1)
+        if R.shape != (3, 3) or t.shape != (3,):
+            raise ValueError(f"transform (R, s, t): R {R.shape}, t {t.shape}; expected [3, 3] and [3]")
+        try:
+            s = float(s)
+        except (TypeError, ValueError):
+            raise ValueError(f"transform (R, s, t): s {s!r} is not a number") from None
+        return np.concatenate([s * R, t[:, None]], 1)
+    try:
+        T = np.asarray(_np(transform), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("transform: expected a 4 x 4 or (R, s, t)") from None
+    if T.shape != (4, 4):
+        raise ValueError(f"transform: shape {T.shape}, expected a 4 x 4 or (R, s, t)")
+    return T[:3].copy()
+
+
+def _np(m):
+    return m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else m

@@ -67,6 +67,14 @@ class PointCloud:
     points: np.ndarray                      # [M, 3] float32
     colors: np.ndarray                      # [M, 3] float32 in [0, 1]
     normals: Optional[np.ndarray] = None    # [M, 3] float32, unit length (zero where the tsdf gradient vanishes)
+    # (extract_pcd(host=False) fills the three fields with device tensors of the same shapes and rows)
+
+    def compute_point_cloud_distance(self, target) -> np.ndarray:
+        """o3d.geometry.PointCloud.compute_point_cloud_distance(target): for each point of this cloud the distance to the closest point
+        of `target` (a PointCloud, or anything pointcloud.NearestNeighbours takes), float64 numpy [M].  Computed on the device in fp32
+        (bodyslam_amd/pointcloud.py states the arithmetic); restated from Open3D's documented meaning, parity with Open3D unpinned."""
+        from .pointcloud import point_cloud_distance
+        return point_cloud_distance(self, target)[0].cpu().numpy().astype(np.float64)
 
 
 @dataclass
@@ -375,9 +383,14 @@ class TSDF:
         other.build_3D_map(rgbd, intrinsic, extrinsic)
         return other
 
-    def extract_pcd(self) -> PointCloud:
+    def extract_pcd(self, host: bool = True) -> PointCloud:
+        """host=False: the PointCloud's fields are device tensors holding the same rows, so a map of millions of points is evaluated where
+        it lies (evaluation.evaluate_reconstruction).  In either form the rows of one volume unit come out in the order the extraction's
+        atomics gave, which differs from call to call."""
         U = self.n_units
         if U == 0:
+            if not host:
+                return PointCloud(*(torch.zeros(0, 3, device=self.dev) for _ in range(3)))
             return PointCloud(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32))
         count = torch.zeros(U, dtype=torch.int32, device=self.dev)
         lib = L.load_library()
@@ -391,6 +404,8 @@ class TSDF:
         nrm = torch.empty(max(total, 1), 3, device=self.dev)
         off = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)).to(self.dev)
         L.check(lib.bs_tsdf_extract(*args, L.p(off), L.p(pts), L.p(cols), L.p(nrm), L.stream_ptr()), "bs_tsdf_extract")
+        if not host:
+            return PointCloud(pts[:total], cols[:total], nrm[:total])
         return PointCloud(pts[:total].cpu().numpy(), cols[:total].cpu().numpy(), nrm[:total].cpu().numpy())
 
     def save_pcd(self, saving_path: str) -> None:
@@ -565,8 +580,8 @@ class MAP:
         self.integrate(curr_rgbd, i, pose)
         return pose
 
-    def extract_pcd(self) -> PointCloud:
-        return self.model.extract_pcd()
+    def extract_pcd(self, host: bool = True) -> PointCloud:
+        return self.model.extract_pcd(host=host)
 
     def extract_mesh(self) -> TriangleMesh:
         return self.model.extract_mesh()

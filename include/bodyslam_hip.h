@@ -27,7 +27,7 @@ typedef enum {
     BS_ERR_NOT_INIT = -3
 } bs_status;
 
-enum { BS_F32 = 0, BS_F16 = 1, BS_BF16 = 2, BS_F64 = 3 /* bs_similarity_fit only */ };
+enum { BS_F32 = 0, BS_F16 = 1, BS_BF16 = 2, BS_F64 = 3 /* bs_similarity_fit and bs_pc_transform only */ };
 /* BS_ACT_SOFTPLUS: torch.nn.Softplus(beta = 1, threshold = 20) through libm (log1pf(expf(x))), what the oracle computes.
  * BS_ACT_SOFTPLUS_FAST: the same function on v_exp / v_log (relative error <= 4e-6): the attractor MLPs only, whose epilogue was bound by
  * libm's arithmetic and whose inputs are 16-bit hidden units anyway; the seed regressors (bin start values) and the reference
@@ -622,6 +622,61 @@ int bs_similarity_fit(const void* source, const void* target, int64_t n, int32_t
                       void* stream);
 int bs_trajectory_metrics(const double* gt, const double* pred, const int32_t* offsets, int32_t S, int64_t total_poses, int32_t protocol,
                           int32_t delta, int32_t flags, double* out, void* stream);
+
+/* ---- reconstruction evaluation: cloud-to-cloud distances ----------------------------------------------------------------------------------
+ * bs_pc_query_grid / bs_pc_query_brute replace Open3D's PointCloud.compute_point_cloud_distance, the exact nearest-neighbour distance from
+ * every point of one cloud to another cloud, which the reference calls at BodySLAM_not_refactored/3DM/mapping_module.py:45,48,62.  Restated
+ * from Open3D's documented meaning; parity with Open3D is UNPINNED.  The statement is tests/_pointcloud_ref.py.
+ * Arithmetic, fp32, no contraction: dx = s.x - t.x, dy, dz alike, d2 = (dx dx + dy dy) + dz dz; the neighbour of s is the lexicographic
+ * minimum of (d2, original target index) over the finite target points; distance = sqrtf(d2), correctly rounded; index int32.  The result
+ * depends on neither the order of the candidates, nor the order of the points inside a cell, nor the cell size.  A source point with a
+ * non-finite coordinate gets (NaN, -1); no finite target point gives (+inf, -1).  max_distance (+inf: none; fp32): a source whose
+ * distance is > max_distance gets (+inf, -1).
+ *   bs_pc_bounds        replaces PointCloud.get_min_bound / get_max_bound over the finite points [n, 3] fp32 (device).  out: 8 uint32
+ *                       (device): 0-2 o(min x, y, z), 3-5 ~o(max x, y, z), 6 the number of finite points, 7 zero; o(v) maps fp32 bit
+ *                       patterns to uint32 in order: b | 0x80000000 for b >= 0, ~b otherwise.  No finite point: 0-5 are 0xffffffff
+ *   the grid            lo, hi: host float [3], the bounds; cell_size h > 0; dims: host int32 [3] = cells per axis, their product at most
+ *                       BS_PC_MAX_CELLS.  Cell coordinate along an axis: (int) min(max(floorf((x - lo) / h), 0), n - 1) in fp32; cell
+ *                       index (cz ny + cy) nx + cx
+ *   bs_pc_grid_count    (the build step of Open3D's KDTreeFlann, as a uniform grid) counts int32 [cells] (device, zeroed by the caller) +=
+ *                       the finite points per cell.  The caller scans: cell_start int32 [cells + 1] (exclusive, cell_start[cells] =
+ *                       n_records), and hands a copy of it as `cursor` to
+ *   bs_pc_grid_scatter  records [n_records] of 16 bytes (x, y, z, the bit pattern of the original index), in cell order; the order inside a
+ *                       cell is whatever the atomics gave
+ *   bs_pc_query_grid    (KDTreeFlann.search_knn_vector_3d with k = 1, per source point) one thread per source [m, 3] fp32 (device) over
+ *                       the Chebyshev shells of cells around its (clamped) cell until the best d2 is below the square of a conservative
+ *                       bound on everything unvisited (csrc/pointcloud.hip derives it), every cell has been seen, or the shell covers
+ *                       max_distance.  A source still searching after shell `shell_cap` is appended to fallback_list int32 [m] (device),
+ *                       fallback_count int32 [1] (device, zeroed by the call) counts them; their dist / index are NOT written:
+ *   bs_pc_query_brute   finishes them -- list int32 [m] (device) of source indices, or NULL for the sources 0 .. m - 1 -- by brute force
+ *                       over the records (LDS tiles of 1024 records, 16-byte LDS reads).  keys: m * 8 bytes of device scratch
+ *   bs_pc_transform     (PointCloud.transform / scale) out fp32 [n, 3] = the rows of [A | t] (affine: 12 host doubles, row-major 3 x 4)
+ *                       applied to source [n, 3] (BS_F32 or BS_F64) in fp64, ((a0 p0 + a1 p1) + a2 p2) + t, rounded once to fp32
+ *   bs_pc_stats         (np.mean / np.median / ... over the distance array the reference gets back) over dist fp32 [n] (device), out
+ *                       BS_PC_STATS_FIELDS doubles (device): 0 n, 1 finite entries, 2 infinite entries (unmatched), 3 NaN entries, and over
+ *                       the finite ones 4 the sum, 5 the sum of squares (fp64), 6 the max, 7 the exact median (for an even count
+ *                       ((double) a + (double) b) / 2; radix selection on the bit patterns), 8-15 the count of d < thresholds[k] compared
+ *                       in fp32 (host float [n_thresholds <= BS_PC_MAX_THRESHOLDS]); 6 and 7 are NaN without a finite entry.  The sums are
+ *                       added in an order fixed by n alone: the same bits in every run.  workspace: BS_PC_STATS_WORKSPACE_BYTES of
+ *                       device memory, 128-byte aligned.  Six launches and one memset
+ * 1 <= n, m < 2^31.  No floating-point atomics anywhere. */
+#define BS_PC_MAX_CELLS (1 << 24)
+#define BS_PC_MAX_THRESHOLDS 8
+#define BS_PC_STATS_FIELDS 16
+#define BS_PC_STATS_WORKSPACE_BYTES 163968
+int bs_pc_bounds(const float* points, int64_t n, uint32_t* out, void* stream);
+int bs_pc_grid_count(const float* points, int64_t n, const float* lo, const float* hi, float cell_size, const int32_t* dims, int32_t* counts,
+                     void* stream);
+int bs_pc_grid_scatter(const float* points, int64_t n, const float* lo, const float* hi, float cell_size, const int32_t* dims, int32_t* cursor,
+                       int64_t n_records, void* records, void* stream);
+int bs_pc_query_grid(const void* records, const int32_t* cell_start, int64_t n_records, const float* lo, const float* hi, float cell_size,
+                     const int32_t* dims, const float* source, int64_t m, float max_distance, int32_t shell_cap, float* dist, int32_t* index,
+                     int32_t* fallback_list, int32_t* fallback_count, void* stream);
+int bs_pc_query_brute(const void* records, int64_t n_records, const float* source, const int32_t* list, int64_t m, float max_distance, void* keys,
+                      float* dist, int32_t* index, void* stream);
+int bs_pc_transform(const void* source, int32_t dtype, int64_t n, const double* affine, float* out, void* stream);
+int bs_pc_stats(const float* dist, int64_t n, const float* thresholds, int32_t n_thresholds, void* workspace, int64_t workspace_bytes, double* out,
+                void* stream);
 
 /* ---- sparse-feature scale path: ORB match displacement (N3, rgbd_odo = False) ---------------------------------------------------------
  * The role of scaling_system.compute_scaling_factor (BodySLAM_not_refactored/3DM/scaling_system.py:107-137), which
