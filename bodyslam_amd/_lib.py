@@ -169,6 +169,10 @@ _SIGS = {
     "bs_pc_query_brute": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pc_transform": [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pc_stats": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    # rigid ICP registration (csrc/icp.hip); lo, hi and dims are pointers to host arrays
+    "bs_icp_step": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                    C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_icp_finish": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p],
 }
 EXPORTS = sorted(list(_SIGS) + ["bs_last_error"])
 
@@ -938,3 +942,38 @@ def pc_stats(dist, thresholds, workspace, out):
     t_, t_p = _host(thresholds, "float32", n_tau)
     check(load_library().bs_pc_stats(p(dist), dist.numel(), t_p if n_tau else None, n_tau, p(workspace), workspace.numel() * workspace.element_size(),
                                      p(out), stream_ptr()), "bs_pc_stats")
+
+
+ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1
+ICP_ITERATE, ICP_EVALUATE = 0, 1
+ICP_RUNNING, ICP_CONVERGED, ICP_MAX_ITERATION, ICP_DEGENERATE = 0, 1, 2, 3
+ICP_PARTIAL_FIELDS, ICP_STATE_FIELDS, ICP_LOG_FIELDS, ICP_MAX_ITERATIONS, ICP_BLOCK = 32, 64, 4, 65536, 256
+
+
+def icp_step(records, n_records, cell_start, lo, hi, cell_size, dims, target, normals, source, max_distance, estimation, mode, state, partial):
+    """records / cell_start / lo / hi / cell_size / dims: the index as for pc_query_grid; target fp32 [n, 3] (the points the index was built
+    from), normals fp32 [n, 3] or None, source fp32 / fp64 [m, 3], state fp64 [ICP_STATE_FIELDS + ICP_LOG_FIELDS * max_iteration], partial
+    fp64 [ceil(m / ICP_BLOCK), ICP_PARTIAL_FIELDS]: all on the device (include/bodyslam_hip.h)"""
+    _pts(target)
+    _i32(cell_start)
+    _f64(state, partial)
+    m = source.shape[0]
+    assert source.dtype in (torch.float32, torch.float64) and source.is_cuda and source.is_contiguous() and source.dim() == 2 and source.shape[1] == 3
+    if normals is not None:
+        _pts(normals)
+        assert tuple(normals.shape) == tuple(target.shape)
+    (lo_, lo_p), (hi_, hi_p), (d_, d_p) = _host(lo, "float32", 3), _host(hi, "float32", 3), _host(dims, "int32", 3)
+    assert records.dtype == torch.float32 and records.is_cuda and records.is_contiguous() and records.dim() == 2 and records.shape[1] == 4
+    assert cell_start.numel() == int(d_[0]) * int(d_[1]) * int(d_[2]) + 1 and 0 <= n_records <= min(records.shape[0], target.shape[0])
+    assert state.numel() >= ICP_STATE_FIELDS + ICP_LOG_FIELDS and partial.numel() >= -(-m // ICP_BLOCK) * ICP_PARTIAL_FIELDS
+    check(load_library().bs_icp_step(p(records), p(cell_start), int(n_records), lo_p, hi_p, float(cell_size), d_p, p(target), p(normals),
+                                     target.shape[0], p(source), F32 if source.dtype == torch.float32 else F64, m, float(max_distance),
+                                     int(estimation), int(mode), p(state), p(partial), stream_ptr()), "bs_icp_step")
+
+
+def icp_finish(partial, m, lo, hi, estimation, mode, max_iteration, relative_fitness, relative_rmse, state):
+    _f64(state, partial)
+    (lo_, lo_p), (hi_, hi_p) = _host(lo, "float32", 3), _host(hi, "float32", 3)
+    assert partial.numel() >= -(-m // ICP_BLOCK) * ICP_PARTIAL_FIELDS and state.numel() >= ICP_STATE_FIELDS + ICP_LOG_FIELDS * int(max_iteration)
+    check(load_library().bs_icp_finish(p(partial), int(m), lo_p, hi_p, int(estimation), int(mode), int(max_iteration), float(relative_fitness),
+                                       float(relative_rmse), p(state), stream_ptr()), "bs_icp_finish")

@@ -1,0 +1,87 @@
+// The uniform grid of the cloud-to-cloud distances and the walk over it, shared by the query (pointcloud.hip, bs_pc_query_grid) and the
+// ICP step (icp.hip, bs_icp_step): one copy of the cell function, the candidate test, the 16-byte record load and the conservative bound,
+// so the two kernels cannot drift apart.  The arithmetic and the derivation of the bound are at the top of pointcloud.hip.
+#pragma once
+#include <math.h>
+
+#include "common.h"
+
+namespace bs {
+
+constexpr int PC_NONE = 0x7fffffff;                 // "no neighbour yet": above every index
+
+__device__ __forceinline__ bool pc_finite(float v) { return fabsf(v) < INFINITY; }          // false for NaN
+
+struct PcGrid {
+    float lo[3], hi[3], h;
+    int32_t n[3];
+};
+
+__device__ __forceinline__ int pc_cell(float x, float lo, float h, int n) {
+    float t = floorf(__fdiv_rn(x - lo, h));
+    t = fminf(fmaxf(t, 0.0f), (float)(n - 1));
+    return (int)t;
+}
+
+__device__ __forceinline__ void pc_candidate(const f32x4 t, float sx, float sy, float sz, float& best, int32_t& bi) {
+    const float dx = sx - t[0], dy = sy - t[1], dz = sz - t[2];
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    const int32_t id = __float_as_int(t[3]);
+    if (d2 < best || (d2 == best && id < bi)) { best = d2; bi = id; }
+}
+
+// The Chebyshev shells r = 0, 1, 2, ... of cells around the (clamped) cell of the finite source (sx, sy, sz): best = the minimum d2,
+// bi = its original index (PC_NONE: no candidate seen).  true: the search is complete -- the bound holds, every cell has been seen, or
+// the shell covers max_distance.  false: the source was still searching after shell `shell_cap` (the caller finishes it some other way).
+__device__ __forceinline__ bool pc_walk_shells(const f32x4* __restrict__ records, const int32_t* __restrict__ cell_start, const PcGrid& g,
+                                               float sx, float sy, float sz, float max_distance, int32_t shell_cap, float& best, int32_t& bi) {
+    const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
+    const int cx = pc_cell(sx, g.lo[0], g.h, nx), cy = pc_cell(sy, g.lo[1], g.h, ny), cz = pc_cell(sz, g.lo[2], g.h, nz);
+    const float slack = fmaxf(fmaxf((g.hi[0] - g.lo[0]) + fabsf(sx - g.lo[0]), (g.hi[1] - g.lo[1]) + fabsf(sy - g.lo[1])),
+                              (g.hi[2] - g.lo[2]) + fabsf(sz - g.lo[2])) * 4.76837158203125e-07f;       // 2^-21
+    const int r_all = max(max(max(cx, nx - 1 - cx), max(cy, ny - 1 - cy)), max(cz, nz - 1 - cz));      // after this shell: every cell seen
+    best = INFINITY;
+    bi = PC_NONE;
+    for (int r = 0;; ++r) {
+        const int z0 = max(cz - r, 0), z1 = min(cz + r, nz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, ny - 1);
+        const int x0 = max(cx - r, 0), x1 = min(cx + r, nx - 1);
+        for (int z = z0; z <= z1; ++z)
+            for (int y = y0; y <= y1; ++y) {
+                const int row = (z * ny + y) * nx;
+                if (abs(z - cz) == r || abs(y - cy) == r) {             // a face row of the shell: its cells are one run of records
+                    for (int32_t k = cell_start[row + x0], e = cell_start[row + x1 + 1]; k < e; ++k) pc_candidate(records[k], sx, sy, sz, best, bi);
+                } else {                                                // an inner row: the two end cells
+                    if (cx - r >= 0)
+                        for (int32_t k = cell_start[row + cx - r], e = cell_start[row + cx - r + 1]; k < e; ++k)
+                            pc_candidate(records[k], sx, sy, sz, best, bi);
+                    if (cx + r <= nx - 1)
+                        for (int32_t k = cell_start[row + cx + r], e = cell_start[row + cx + r + 1]; k < e; ++k)
+                            pc_candidate(records[k], sx, sy, sz, best, bi);
+                }
+            }
+        if (r >= r_all) return true;
+        const float lb = ((float)r * g.h - slack) * 0.99999f;
+        if (lb > 0.0f && best < lb * lb) return true;
+        if (lb * 0.9999f > max_distance) return true;
+        if (r >= shell_cap) return false;
+    }
+}
+
+inline bool pc_grid_ok(const PcGrid& g) {
+    if (!(g.h > 0.0f) || !isfinite(g.h)) return false;
+    int64_t cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (g.n[a] < 1 || !isfinite(g.lo[a]) || !isfinite(g.hi[a]) || !(g.hi[a] >= g.lo[a])) return false;
+        cells *= g.n[a];
+        if (cells > BS_PC_MAX_CELLS) return false;
+    }
+    return true;
+}
+inline PcGrid pc_grid(const float* lo, const float* hi, float h, const int32_t* dims) {
+    PcGrid g;
+    for (int a = 0; a < 3; ++a) { g.lo[a] = lo[a]; g.hi[a] = hi[a]; g.n[a] = dims[a]; }
+    g.h = h;
+    return g;
+}
+
+}  // namespace bs

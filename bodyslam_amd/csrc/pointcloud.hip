@@ -45,12 +45,12 @@
 #include <algorithm>
 
 #include "common.h"
+#include "pc_grid.h"
 
 namespace bs {
 namespace {
 
 constexpr int PC_THREADS = 256;
-constexpr int PC_NONE = 0x7fffffff;                 // "no neighbour yet": above every index
 
 // order-preserving map of fp32 bit patterns onto uint32 (and back)
 __device__ __forceinline__ uint32_t pc_ord(float v) {
@@ -58,18 +58,6 @@ __device__ __forceinline__ uint32_t pc_ord(float v) {
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ __forceinline__ float pc_unord(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
-__device__ __forceinline__ bool pc_finite(float v) { return fabsf(v) < INFINITY; }          // false for NaN
-
-struct PcGrid {
-    float lo[3], hi[3], h;
-    int32_t n[3];
-};
-
-__device__ __forceinline__ int pc_cell(float x, float lo, float h, int n) {
-    float t = floorf(__fdiv_rn(x - lo, h));
-    t = fminf(fmaxf(t, 0.0f), (float)(n - 1));
-    return (int)t;
-}
 
 // ---- build ---------------------------------------------------------------------------------------------------------------------------------
 // out[0..2] = min of ord(x, y, z), out[3..5] = min of ~ord = ~max (so one 0xff fill initialises both), out[6] = finite points
@@ -123,13 +111,7 @@ __global__ void __launch_bounds__(PC_THREADS) pc_grid_kernel(const float* __rest
 }
 
 // ---- query ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void pc_candidate(const f32x4 t, float sx, float sy, float sz, float& best, int32_t& bi) {
-    const float dx = sx - t[0], dy = sy - t[1], dz = sz - t[2];
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    const int32_t id = __float_as_int(t[3]);
-    if (d2 < best || (d2 == best && id < bi)) { best = d2; bi = id; }
-}
-
+// (the cell function, the candidate test and the walk over the shells: pc_grid.h, shared with icp.hip)
 __global__ void __launch_bounds__(PC_THREADS) pc_query_grid_kernel(const f32x4* __restrict__ records, const int32_t* __restrict__ cell_start,
                                                                    PcGrid g, const float* __restrict__ src, int64_t m, float max_distance,
                                                                    int32_t shell_cap, float* __restrict__ dist, int32_t* __restrict__ idx,
@@ -142,38 +124,11 @@ __global__ void __launch_bounds__(PC_THREADS) pc_query_grid_kernel(const f32x4* 
         idx[i] = -1;
         return;
     }
-    const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
-    const int cx = pc_cell(sx, g.lo[0], g.h, nx), cy = pc_cell(sy, g.lo[1], g.h, ny), cz = pc_cell(sz, g.lo[2], g.h, nz);
-    const float slack = fmaxf(fmaxf((g.hi[0] - g.lo[0]) + fabsf(sx - g.lo[0]), (g.hi[1] - g.lo[1]) + fabsf(sy - g.lo[1])),
-                              (g.hi[2] - g.lo[2]) + fabsf(sz - g.lo[2])) * 4.76837158203125e-07f;       // 2^-21
-    const int r_all = max(max(max(cx, nx - 1 - cx), max(cy, ny - 1 - cy)), max(cz, nz - 1 - cz));      // after this shell: every cell seen
-    float best = INFINITY;
-    int32_t bi = PC_NONE;
-    for (int r = 0;; ++r) {
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, nz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, ny - 1);
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, nx - 1);
-        for (int z = z0; z <= z1; ++z)
-            for (int y = y0; y <= y1; ++y) {
-                const int row = (z * ny + y) * nx;
-                if (abs(z - cz) == r || abs(y - cy) == r) {             // a face row of the shell: its cells are one run of records
-                    for (int32_t k = cell_start[row + x0], e = cell_start[row + x1 + 1]; k < e; ++k) pc_candidate(records[k], sx, sy, sz, best, bi);
-                } else {                                                // an inner row: the two end cells
-                    if (cx - r >= 0)
-                        for (int32_t k = cell_start[row + cx - r], e = cell_start[row + cx - r + 1]; k < e; ++k)
-                            pc_candidate(records[k], sx, sy, sz, best, bi);
-                    if (cx + r <= nx - 1)
-                        for (int32_t k = cell_start[row + cx + r], e = cell_start[row + cx + r + 1]; k < e; ++k)
-                            pc_candidate(records[k], sx, sy, sz, best, bi);
-                }
-            }
-        if (r >= r_all) break;
-        const float lb = ((float)r * g.h - slack) * 0.99999f;
-        if (lb > 0.0f && best < lb * lb) break;
-        if (lb * 0.9999f > max_distance) break;
-        if (r >= shell_cap) {                                           // the brute-force kernel finishes this one
-            fb_list[atomicAdd(fb_count, 1)] = (int32_t)i;
-            return;
-        }
+    float best;
+    int32_t bi;
+    if (!pc_walk_shells(records, cell_start, g, sx, sy, sz, max_distance, shell_cap, best, bi)) {     // the brute-force kernel finishes this one
+        fb_list[atomicAdd(fb_count, 1)] = (int32_t)i;
+        return;
     }
     float d = sqrtf(best);
     if (bi == PC_NONE || d > max_distance) { d = INFINITY; bi = -1; }
@@ -456,23 +411,6 @@ __global__ void __launch_bounds__(PC_THREADS) ps_select_kernel(const uint32_t* _
             for (int k = 8 + BS_PC_MAX_THRESHOLDS; k < BS_PC_STATS_FIELDS; ++k) out[k] = 0.0;
         }
     }
-}
-
-bool pc_grid_ok(const PcGrid& g) {
-    if (!(g.h > 0.0f) || !isfinite(g.h)) return false;
-    int64_t cells = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (g.n[a] < 1 || !isfinite(g.lo[a]) || !isfinite(g.hi[a]) || !(g.hi[a] >= g.lo[a])) return false;
-        cells *= g.n[a];
-        if (cells > BS_PC_MAX_CELLS) return false;
-    }
-    return true;
-}
-PcGrid pc_grid(const float* lo, const float* hi, float h, const int32_t* dims) {
-    PcGrid g;
-    for (int a = 0; a < 3; ++a) { g.lo[a] = lo[a]; g.hi[a] = hi[a]; g.n[a] = dims[a]; }
-    g.h = h;
-    return g;
 }
 
 }  // namespace

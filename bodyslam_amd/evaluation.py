@@ -15,7 +15,8 @@ poses that can stay in device memory (SequenceResult.g_abs); similarity_transfor
 Reconstruction.  SCARED ships structured-light point clouds and EndoSLAM 3-D scans (the reference reads both, DatasetLoader.read_SCARED /
 read_EndoSlam); its mapping module measures clouds against each other with Open3D's compute_point_cloud_distance
 (3DM/mapping_module.py:45,48,62).  evaluate_reconstruction computes accuracy, completeness, chamfer distance and precision / recall /
-F-score from the two nearest-neighbour distance arrays (bodyslam_amd/pointcloud.py), which stay in device memory.
+F-score from the two nearest-neighbour distance arrays (bodyslam_amd/pointcloud.py), which stay in device memory;
+evaluate_reconstruction_aligned refines the frame by rigid ICP first (bodyslam_amd/registration.py).
 
 There is no CPU fallback: without a GPU the calls raise BodySlamHipError.
 """
@@ -25,12 +26,15 @@ import csv
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import TYPE_CHECKING, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib as L
+
+if TYPE_CHECKING:
+    from .registration import RegistrationResult
 
 # GT masks of MDEM_eval.py:179-192, as open intervals lo < gt < hi on the GT alone: Hamlyn `gt > 1.0 and gt < 300` (:183), SCARED
 # `gt > 0` (:190); EndoSlam has no branch, so nothing is masked -- zeros in its GT are part of the median (and of no metric)
@@ -457,7 +461,8 @@ class ReconstructionMetrics:
     """accuracy: pred -> gt; completeness: gt -> pred; chamfer: the mean of the two means.  Per threshold tau (thresholds, as fp32 values):
     precision = the fraction of pred points with distance < tau, recall = that of gt points, fscore = 2 P R / (P + R), 0 when both are 0.
     The fractions are over the points with finite coordinates; a point without a neighbour within max_distance (n_unmatched_*) is a
-    miss for every tau and enters neither mean, median, rmse nor max."""
+    miss for every tau and enters neither mean, median, rmse nor max.  alignment: with align="icp" the registration.RegistrationResult whose
+    transformation (pred -> gt, after `transform`) was applied to pred before the distances; None otherwise."""
     accuracy: DistanceStats
     completeness: DistanceStats
     chamfer: float
@@ -469,6 +474,7 @@ class ReconstructionMetrics:
     n_gt: int
     n_unmatched_pred: int
     n_unmatched_gt: int
+    alignment: Optional["RegistrationResult"] = None       # align="icp": the registration applied to pred (not in as_dict() or the CSV)
 
     def as_dict(self) -> Dict[str, float]:
         out: Dict[str, float] = {}
@@ -527,6 +533,61 @@ def _distance_stats(rec: np.ndarray) -> DistanceStats:
     return DistanceStats(float(rec[4] / n), float(rec[7]), float(math.sqrt(rec[5] / n)), float(rec[6]))
 
 
+_ICP_KEYS = ("max_correspondence_distance", "init", "estimation", "target_normals", "max_iteration", "relative_fitness", "relative_rmse", "cell_size",
+             "device")
+
+
+def _check_align(align, icp) -> Optional[dict]:
+    if align is None:
+        if icp is not None:
+            raise ValueError('icp given without align="icp"')
+        return None
+    if align != "icp":
+        raise ValueError(f'unknown align {align!r}: None or "icp"')
+    if not isinstance(icp, dict) or "max_correspondence_distance" not in icp:
+        raise ValueError('align="icp" needs icp, a dict of registration_icp keywords with max_correspondence_distance')
+    unknown = sorted(set(icp) - set(_ICP_KEYS))
+    if unknown:
+        raise ValueError(f"icp: unknown keys {unknown}; registration_icp takes {_ICP_KEYS}")
+    from . import registration as REG
+    kw = dict(icp)
+    REG._check_radius(kw["max_correspondence_distance"])
+    kw["init"] = REG._check_init(kw.get("init"))
+    kw.setdefault("estimation", "auto")
+    if kw["estimation"] not in REG.ESTIMATIONS:
+        raise ValueError(f"unknown estimation {kw['estimation']!r}: one of {REG.ESTIMATIONS}")
+    REG._check_criteria(kw.get("max_iteration", 30), kw.get("relative_fitness", 1e-6), kw.get("relative_rmse", 1e-6))
+    return kw
+
+
+def _align_icp(p, g, p_normals, g_normals, A, kw, dev):
+    """registers the fp32 device clouds p (pred, `transform` applied) -> g (gt); -> (p moved, the RegistrationResult of pred -> gt)"""
+    import dataclasses
+
+    from . import registration as REG
+    kw = dict(kw)
+    radius, est, init = kw.pop("max_correspondence_distance"), kw.pop("estimation"), kw.pop("init")
+    normals = kw.pop("target_normals", None)
+    if normals is None:
+        normals = g_normals
+    if est == "auto" and normals is None and p_normals is not None:
+        # the map has normals and the scan has none: gt -> pred by point-to-plane, inverted.  Normals follow `transform` by the inverse
+        # transpose of its linear part (R / s for a similarity); their length does not matter to the normal equations' solution
+        n = REG._as_normals(p_normals, int(p.shape[0])).to(dev).contiguous()
+        if A is not None:
+            N = np.concatenate([np.linalg.inv(A[:, :3]).T, np.zeros((3, 1))], 1)
+            turned = torch.empty(n.shape[0], 3, dtype=torch.float32, device=dev)
+            L.pc_transform(n, N, turned)
+            n = turned
+        back = REG.registration_icp(g, p, radius, init=np.linalg.inv(init), estimation="point_to_plane", target_normals=n, **kw)
+        res = dataclasses.replace(back, transformation=np.linalg.inv(back.transformation))
+    else:
+        res = REG.registration_icp(p, g, radius, init=init, estimation=est, target_normals=normals, **kw)
+    moved = torch.empty(p.shape[0], 3, dtype=torch.float32, device=dev)
+    L.pc_transform(p, res.transformation[:3], moved)
+    return moved, res
+
+
 def evaluate_reconstruction(pred, gt, thresholds: Sequence[float] = (0.001, 0.002, 0.005), transform=None,
                             max_distance: Optional[float] = None) -> ReconstructionMetrics:
     """The reconstruction `pred` against the ground-truth geometry `gt`, by nearest-neighbour distances both ways.
@@ -535,27 +596,57 @@ def evaluate_reconstruction(pred, gt, thresholds: Sequence[float] = (0.001, 0.00
     tsdf.TriangleMesh (its vertices).  pred may also be a tsdf.TSDF or tsdf.MAP: its extract_pcd(host=False) is evaluated where it lies.
     transform: a 4 x 4, or (R, s, t) as similarity_transform returns it, applied to pred on the device as s R p + t in fp64 and rounded
     once to fp32 -- how a monocular map is put into the ground truth's frame, by the similarity of its trajectory (evaluate_trajectory,
-    similarity_transform).  No alignment is searched for here (no ICP).  thresholds: at most 8, compared as fp32 values.
+    similarity_transform).  No alignment is searched for here: evaluate_reconstruction_aligned refines `transform` by ICP first.
+    thresholds: at most 8, compared as fp32 values.
     max_distance: a point without a neighbour within it is unmatched (ReconstructionMetrics).  Two runs on the same arrays return the
     same bits.  A TSDF or MAP hands over its points in the order its extraction's atomics gave, which differs from call to call: counts,
     max, median, precision and recall are then still exact, the means and rmse agree to the rounding of an fp64 sum (n 2^-53 relative)."""
+    return _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, None, None)
+
+
+def evaluate_reconstruction_aligned(pred, gt, thresholds: Sequence[float] = (0.001, 0.002, 0.005), transform=None,
+                                    max_distance: Optional[float] = None, align: Optional[str] = "icp",
+                                    icp: Optional[dict] = None) -> ReconstructionMetrics:
+    """evaluate_reconstruction after an alignment search.  align="icp": after `transform`, pred is registered onto gt by
+    registration.registration_icp with the keywords of the dict `icp` (max_correspondence_distance is required; rigid, no scale: the
+    scale is `transform`'s), and the result is applied on the device before the two distance queries; it is returned as
+    ReconstructionMetrics.alignment.  Normals for point-to-plane come from icp["target_normals"] or a PointCloud gt; when gt has none and
+    pred has them (a TSDF, MAP or PointCloud), estimation "auto" registers gt -> pred by point-to-plane and inverts the result (fitness and
+    rmse are then those of that direction).  align=None: evaluate_reconstruction itself.  (A function of its own: evaluate_reconstruction's
+    parameter list is pinned by tests/test_pointcloud_cpu.py.)"""
+    return _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, align, icp)
+
+
+def _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, align, icp) -> ReconstructionMetrics:
     from . import pointcloud as PC
     from .tsdf import MAP, TSDF
     taus = _check_thresholds(thresholds)
     PC._check_max_distance(max_distance)
     A = None if transform is None else PC.affine_rows(transform)
+    kw = _check_align(align, icp)
+    p_normals = g_normals = None
+    if kw is not None:
+        from .tsdf import PointCloud
+        p_normals = pred.normals if isinstance(pred, PointCloud) else None
+        g_normals = gt.normals if isinstance(gt, PointCloud) else None
+        if kw["estimation"] == "point_to_plane" and kw.get("target_normals") is None and g_normals is None:
+            raise ValueError('icp: estimation "point_to_plane" needs target_normals (or a PointCloud gt with normals)')
     if not isinstance(pred, (TSDF, MAP)):
         p = PC.as_points(pred, "pred")
     g = PC.as_points(gt, "gt")
     if not torch.cuda.is_available():
         L.init(0)                              # raises BodySlamHipError: no CPU fallback
     if isinstance(pred, (TSDF, MAP)):
-        pts = pred.extract_pcd(host=False).points
+        cloud = pred.extract_pcd(host=False)
+        pts = cloud.points
         if pts.shape[0] == 0:
             raise ValueError("pred: the map has no surface points")
         p = PC.as_points(pts, "pred")
+        if kw is not None:
+            p_normals = cloud.normals
     cuda = [t.device for t in (p, g) if t.is_cuda]
     dev = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
+    alignment = None
     with torch.cuda.device(dev):
         L.init(dev.index)
         p, g = p.to(dev).contiguous(), g.to(dev).to(torch.float32).contiguous()
@@ -564,6 +655,8 @@ def evaluate_reconstruction(pred, gt, thresholds: Sequence[float] = (0.001, 0.00
             L.pc_transform(p, A, moved)
             p = moved
         p = p.to(torch.float32)
+        if kw is not None:
+            p, alignment = _align_icp(p, g, p_normals, g_normals, A, kw, dev)
         d_pg, _ = PC.NearestNeighbours(g).query(p, max_distance=max_distance)
         d_gp, _ = PC.NearestNeighbours(p).query(g, max_distance=max_distance)
         ra, rc = distance_stats_record(d_pg, taus), distance_stats_record(d_gp, taus)
@@ -575,4 +668,5 @@ def evaluate_reconstruction(pred, gt, thresholds: Sequence[float] = (0.001, 0.00
         f = np.where(prec + rec > 0.0, 2.0 * prec * rec / (prec + rec), 0.0)
     f = np.where(np.isnan(prec) | np.isnan(rec), math.nan, f)
     return ReconstructionMetrics(accuracy=acc, completeness=comp, chamfer=(acc.mean + comp.mean) / 2.0, thresholds=taus, precision=prec, recall=rec,
-                                 fscore=f, n_pred=int(ra[0]), n_gt=int(rc[0]), n_unmatched_pred=int(ra[2]), n_unmatched_gt=int(rc[2]))
+                                 fscore=f, n_pred=int(ra[0]), n_gt=int(rc[0]), n_unmatched_pred=int(ra[2]), n_unmatched_gt=int(rc[2]),
+                                 alignment=alignment)

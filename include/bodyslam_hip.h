@@ -678,6 +678,53 @@ int bs_pc_transform(const void* source, int32_t dtype, int64_t n, const double* 
 int bs_pc_stats(const float* dist, int64_t n, const float* thresholds, int32_t n_thresholds, void* workspace, int64_t workspace_bytes, double* out,
                 void* stream);
 
+/* ---- rigid ICP registration ------------------------------------------------------------------------------------------------------------
+ * bs_icp_step + bs_icp_finish replace Open3D's pipelines.registration.registration_icp with TransformationEstimationPointToPlane or
+ * TransformationEstimationPointToPoint (no scale) and ICPConvergenceCriteria, and, in BS_ICP_EVALUATE mode, evaluate_registration: what
+ * everyone runs before comparing a reconstruction with a scan.  The reference does not call them; they are restated from Open3D's
+ * published interface, parity with Open3D is UNPINNED.  The statement is tests/_icp_ref.py.  One iteration at T (source -> target):
+ *   point           p = fl32(((a0 s0 + a1 s1) + a2 s2) + t) per row of T, in fp64, rounded once: bs_pc_transform's arithmetic
+ *   correspondence  the exact nearest target point of p under the contract above (ties to the lower index), valid when the fp32 distance
+ *                   d <= max_distance; a non-finite row has none.  count = the valid pairs, fitness = count / m,
+ *                   inlier_rmse = sqrt(sum d^2 / count) with d widened to fp64 (0 without a pair)
+ *   coordinates     every sum is over coordinates relative to c = ((double) lo + (double) hi) / 2, the midpoint of the grid's box
+ *   point-to-plane  target normals n fp32 [n_target, 3] (device), indexed as the target was given; a pair whose normal is non-finite or
+ *                   zero counts for fitness and rmse and is left out of the sums.  r = (p - q) . n, J = [(p - c) x n, n], A = sum J J^T
+ *                   (unweighted, 21 upper entries), b = sum J r; delta = -A^-1 b by Cholesky; T <- C exp(delta) C^-1 T with C the
+ *                   translation by c and exp the SE(3) exponential of the left twist (omega, nu) as in bs_odo_p2p_step.  Fewer than 6
+ *                   usable pairs or a non-positive pivot: BS_ICP_DEGENERATE, T unchanged.  No robust kernel
+ *   point-to-point  sum (p - c), sum (q - c), sum (p - c)(q - c)^T; the Kabsch rotation from the 3 x 3 SVD of the centred covariance with
+ *                   the sign fix on the smallest singular direction, t = mean q - R mean p, T <- [R | t] T.  Fewer than 3 pairs or a second
+ *                   singular value that is not positive: BS_ICP_DEGENERATE.  No scale
+ *   stopping        iteration k logs (fitness_k, rmse_k, count_k, usable_k) at the current T; for k >= 1, |fitness_k - fitness_(k-1)| <
+ *                   relative_fitness and |rmse_k - rmse_(k-1)| < relative_rmse set BS_ICP_CONVERGED before any update; otherwise T is
+ *                   updated, and after max_iteration updates the status is BS_ICP_MAX_ITERATION
+ *   state           BS_ICP_STATE_FIELDS + BS_ICP_LOG_FIELDS * max_iteration doubles (device, 16-byte aligned), written by the caller before
+ *                   the first call: 0 the status (0 = running), 1 the iterations logged so far (0), 2-13 the rows of [R | t] of T, the rest 0.
+ *                   bs_icp_finish keeps 14-15 (the previous fitness and rmse), writes 16-19 in BS_ICP_EVALUATE mode (fitness, rmse,
+ *                   count, usable count of the T in the state, which it leaves alone), 32-63 the last call's summed row, and from
+ *                   BS_ICP_STATE_FIELDS on the log rows.  Once the status is set both entries return at their first instruction in
+ *                   BS_ICP_ITERATE mode: iterations can be enqueued in chunks and the state read once per chunk
+ *   bs_icp_step     one thread per source row (BS_F32 or BS_F64 [m, 3], device) over the index of bs_pc_grid_scatter and the target it was
+ *                   built from: the shells of bs_pc_query_grid (the same device function) with no shell cap and no brute-force fallback
+ *                   -- the radius is mandatory -- so the correspondence does not depend on the cell size.  partial: one row of
+ *                   BS_ICP_PARTIAL_FIELDS doubles per block of 256 rows (device, ceil(m / 256) rows): 0 count, 1 usable count, 2 sum d^2,
+ *                   then the 27 (plane: A, b) or 15 (point) sums; fp64, the xor butterfly in the wave, the waves in order
+ *   bs_icp_finish   one block: adds the rows in an order fixed by m, logs, tests the stopping rule, solves and updates T, sets the status
+ * No floating-point atomics: the same bits in every run, for every cell size. */
+enum { BS_ICP_POINT_TO_POINT = 0, BS_ICP_POINT_TO_PLANE = 1 };
+enum { BS_ICP_ITERATE = 0, BS_ICP_EVALUATE = 1 };
+enum { BS_ICP_RUNNING = 0, BS_ICP_CONVERGED = 1, BS_ICP_MAX_ITERATION = 2, BS_ICP_DEGENERATE = 3 };
+#define BS_ICP_PARTIAL_FIELDS 32
+#define BS_ICP_STATE_FIELDS 64
+#define BS_ICP_LOG_FIELDS 4
+#define BS_ICP_MAX_ITERATIONS 65536
+int bs_icp_step(const void* records, const int32_t* cell_start, int64_t n_records, const float* lo, const float* hi, float cell_size,
+                const int32_t* dims, const float* target, const float* normals, int64_t n_target, const void* source, int32_t dtype, int64_t m,
+                float max_distance, int32_t estimation, int32_t mode, const double* state, double* partial, void* stream);
+int bs_icp_finish(const double* partial, int64_t m, const float* lo, const float* hi, int32_t estimation, int32_t mode, int32_t max_iteration,
+                  double relative_fitness, double relative_rmse, double* state, void* stream);
+
 /* ---- sparse-feature scale path: ORB match displacement (N3, rgbd_odo = False) ---------------------------------------------------------
  * The role of scaling_system.compute_scaling_factor (BodySLAM_not_refactored/3DM/scaling_system.py:107-137), which
  * VO.estimate_relative_pose_between calls with rgbd_odo = False (3DM/visual_odometry.py:70-79): cv2.ORB_create() on both frames,
