@@ -5,7 +5,7 @@
 //   RGBD depth constants   BodySLAM_not_refactored/3DM/slam_utils.py:173,212-220,232
 //   compute_curr_estimate_global_pose / ensure_so3_v2   3DM/slam_utils.py:93-122
 #include "common.h"
-#include "svd3.h"
+#include "rigid3.h"
 
 namespace bs {
 
@@ -156,19 +156,9 @@ __device__ void svd3_project_so3(double (&M)[3][3]) {
     double s[3], U[3][3], V[3][3];
     svd3_jacobi(M, U, s, V);
     // the reflection correction acts on the SMALLEST singular direction (LAPACK orders them descending)
-    // (ties -> the last index, which is where a descending LAPACK ordering leaves the flipped direction)
-    int kmin = 0;
-    if (s[1] <= s[kmin]) kmin = 1;
-    if (s[2] <= s[kmin]) kmin = 2;
-    const double dd = det3(U) * det3(V);  // det(V^T) == det(V)
     double D[3] = {1.0, 1.0, 1.0};
-    D[kmin] = dd;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double acc = 0;
-            for (int k = 0; k < 3; ++k) acc += U[i][k] * D[k] * V[j][k];
-            M[i][j] = acc;
-        }
+    D[svd3_smallest(s)] = det3(U) * det3(V);  // det(V^T) == det(V)
+    svd3_usvt(U, D, V, &M[0][0]);
 }
 
 // The strict recurrence, one lane (kept for inputs whose 4x4 matrices are not affine: a bottom row other than [0 0 0 1]).
@@ -206,21 +196,8 @@ __device__ void pose_chain_sequential(const float* t_rel, int N, const double* g
 // (one lane per pose, fp64 one-sided Jacobi); phase 2 is a wave-shuffle prefix product (Kogge-Stone over 64 lanes, wave
 // totals combined through LDS, 256-pose chunks carried by the block).  Pose 1 is formed from g0 exactly as the reference does
 // (g0 need not be a rotation: ensure_so3_v2 goes through here); reassociation moves results by ~1e-15 (tolerance 1e-9).
-struct Se3 {
-    double r[9], t[3];
-};
-__device__ __forceinline__ Se3 se3_compose(const Se3& a, const Se3& b) {
-    Se3 c;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c.r[i * 3 + j] = a.r[i * 3] * b.r[j] + a.r[i * 3 + 1] * b.r[3 + j] + a.r[i * 3 + 2] * b.r[6 + j];
-        c.t[i] = a.r[i * 3] * b.t[0] + a.r[i * 3 + 1] * b.t[1] + a.r[i * 3 + 2] * b.t[2] + a.t[i];
-    }
-    return c;
-}
-__device__ __forceinline__ Se3 se3_shfl_up(const Se3& a, int d) {
-    Se3 o;
+__device__ __forceinline__ Rigid3 se3_shfl_up(const Rigid3& a, int d) {
+    Rigid3 o;
 #pragma unroll
     for (int i = 0; i < 9; ++i) o.r[i] = __shfl_up(a.r[i], d, 64);
 #pragma unroll
@@ -261,8 +238,8 @@ __global__ __launch_bounds__(64) void pose_project_kernel(const float* t_rel, in
 // phase 2: in-place prefix product over the projected elements (one block; 256 poses per round)
 constexpr int CHAIN_THREADS = 256;
 __global__ __launch_bounds__(CHAIN_THREADS) void pose_scan_kernel(const float* t_rel, int N, double* g_abs) {
-    __shared__ Se3 wave_tot[CHAIN_THREADS / 64];
-    __shared__ Se3 carry;
+    __shared__ Rigid3 wave_tot[CHAIN_THREADS / 64];
+    __shared__ Rigid3 carry;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // any non-affine input: the strict recurrence on one lane (g_abs[0:16] holds g0)
     int bad = 0;
@@ -273,45 +250,27 @@ __global__ __launch_bounds__(CHAIN_THREADS) void pose_scan_kernel(const float* t
     }
     for (int base = 0; base < N; base += CHAIN_THREADS) {
         const int n = base + tid;
-        Se3 e;
-        if (n < N) {
-            const double* s = g_abs + (int64_t)(n + 1) * 16;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) e.r[i * 3 + j] = s[i * 4 + j];
-                e.t[i] = s[i * 4 + 3];
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) e.r[i] = (i % 4 == 0) ? 1.0 : 0.0;
-            e.t[0] = e.t[1] = e.t[2] = 0.0;
-        }
+        Rigid3 e = n < N ? rigid3_load(g_abs + (int64_t)(n + 1) * 16) : rigid3_identity();
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
-            const Se3 o = se3_shfl_up(e, d);
-            if (lane >= d) e = se3_compose(o, e);
+            const Rigid3 o = se3_shfl_up(e, d);
+            if (lane >= d) e = rigid3_compose(o, e);
         }
         if (lane == 63) wave_tot[wave] = e;
         __syncthreads();
-        Se3 pre;
+        Rigid3 pre;
         bool has_pre = false;
         if (base > 0) { pre = carry; has_pre = true; }
         for (int w = 0; w < wave; ++w) {
-            pre = has_pre ? se3_compose(pre, wave_tot[w]) : wave_tot[w];
+            pre = has_pre ? rigid3_compose(pre, wave_tot[w]) : wave_tot[w];
             has_pre = true;
         }
-        if (has_pre) e = se3_compose(pre, e);
+        if (has_pre) e = rigid3_compose(pre, e);
         __syncthreads();                       // everyone has read carry / wave_tot
         if (tid == CHAIN_THREADS - 1) carry = e;
         if (n < N) {
             double* o = g_abs + (int64_t)(n + 1) * 16;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) o[i * 4 + j] = e.r[i * 3 + j];
-                o[i * 4 + 3] = e.t[i];
-            }
+            rigid3_store(e, o);
             o[12] = 0.0; o[13] = 0.0; o[14] = 0.0; o[15] = 1.0;
         }
         __syncthreads();

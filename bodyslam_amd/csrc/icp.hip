@@ -19,14 +19,16 @@
 //                  block; the grid depends on m alone.  No floating-point atomics; LDS carries the four wave sums only and is read 16 bytes
 //                  per lane (DESIGN section 7's rule for kernels that may run beside a second stream).
 //   bs_icp_finish  one block: the rows added in an order fixed by their number (a wave per term, lanes strided over the rows, the
-//                  butterfly); fitness = count / m, rmse = sqrt(sum d^2 / count); the log row; the stopping rule; the solve -- Cholesky of
-//                  the 6 x 6 normal matrix and T <- C exp(delta) C^-1 T, or the Kabsch rotation through svd3.h and T <- [R | t] T -- and
-//                  the status word.  One thread does the serial part: a 6 x 6 system.
+//                  butterfly: reduce.h); fitness = count / m, rmse = sqrt(sum d^2 / count); the log row; the stopping rule; the solve --
+//                  Cholesky of the 6 x 6 normal matrix (block6.h) and T <- C exp(delta) C^-1 T, or Kabsch (rigid3.h) and T <- [R | t] T --
+//                  and the status word.  One thread does the serial part: a 6 x 6 system.
 #include <math.h>
 
+#include "block6.h"
 #include "common.h"
 #include "pc_grid.h"
-#include "svd3.h"
+#include "reduce.h"
+#include "rigid3.h"
 
 namespace bs {
 namespace {
@@ -52,10 +54,9 @@ __global__ void __launch_bounds__(ICP_THREADS) icp_step_kernel(const f32x4* __re
     const int64_t i = (int64_t)blockIdx.x * ICP_THREADS + threadIdx.x;
     if (i < m) {
         const double s0 = (double)src[3 * i], s1 = (double)src[3 * i + 1], s2 = (double)src[3 * i + 2];
-        const double* __restrict__ T = state + IS_T;
-        const float px = (float)(((T[0] * s0 + T[1] * s1) + T[2] * s2) + T[3]);
-        const float py = (float)(((T[4] * s0 + T[5] * s1) + T[6] * s2) + T[7]);
-        const float pz = (float)(((T[8] * s0 + T[9] * s1) + T[10] * s2) + T[11]);
+        float p[3];
+        affine_point_f32(state + IS_T, s0, s1, s2, p);
+        const float px = p[0], py = p[1], pz = p[2];
         if (pc_finite(px) && pc_finite(py) && pc_finite(pz)) {
             float best;
             int32_t bi;
@@ -99,9 +100,7 @@ __global__ void __launch_bounds__(ICP_THREADS) icp_step_kernel(const f32x4* __re
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < NT; ++k) {
-        double s = v[k];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+        const double s = wave_sum(v[k]);
         if (lane == 0) reinterpret_cast<double*>(red)[k * ICP_WAVES + wave] = s;
     }
     __syncthreads();
@@ -115,90 +114,36 @@ __global__ void __launch_bounds__(ICP_THREADS) icp_step_kernel(const f32x4* __re
     }
 }
 
-// the SE(3) exponential of the left twist (omega = d[0:3], nu = d[3:6]), odometry.hip's arithmetic
-__device__ void icp_se3_exp(const double (&d)[6], double (&R)[3][3], double (&t)[3]) {
-    const double wx = d[0], wy = d[1], wz = d[2];
-    const double th = sqrt(wx * wx + wy * wy + wz * wz);
-    const double Wx[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
-    double W2[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) W2[i][j] = Wx[i][0] * Wx[0][j] + Wx[i][1] * Wx[1][j] + Wx[i][2] * Wx[2][j];
-    double a, b, c;
-    if (th < 1e-12) {
-        a = 1.0; b = 0.5; c = 0.0;
-    } else {
-        a = sin(th) / th;
-        b = (1.0 - cos(th)) / (th * th);
-        c = (th - sin(th)) / (th * th * th);
-    }
-    for (int i = 0; i < 3; ++i) {
-        double V[3];
-        for (int j = 0; j < 3; ++j) {
-            const double I = i == j ? 1.0 : 0.0;
-            R[i][j] = I + a * Wx[i][j] + (th < 1e-12 ? 0.0 : b * W2[i][j]);
-            V[j] = I + b * Wx[i][j] + c * W2[i][j];
-        }
-        t[i] = V[0] * d[3] + V[1] * d[4] + V[2] * d[5];
-    }
-}
-
-// delta = -A^-1 b by Cholesky (s: the 21 upper entries of A, then b).  false: a pivot is not positive
-__device__ bool icp_solve_plane(const double* __restrict__ s, double (&R)[3][3], double (&t)[3]) {
-    double Lc[6][6], y[6], d[6];
+// delta = -A^-1 b by Cholesky (s: the 21 upper entries of A, then b), g = exp(delta).  false: a pivot is not positive and finite
+__device__ bool icp_solve_plane(const double* __restrict__ s, Rigid3& g) {
+    double A[36], L[36], nb[6], d[6];
     int k = 0;
     for (int a = 0; a < 6; ++a)
-        for (int b = a; b < 6; ++b) Lc[b][a] = s[k++];                 // the lower triangle
-    for (int j = 0; j < 6; ++j) {
-        double p = Lc[j][j];
-        for (int q = 0; q < j; ++q) p -= Lc[j][q] * Lc[j][q];
-        if (!(p > 0.0) || !(p < INFINITY)) return false;
-        const double l = sqrt(p);
-        Lc[j][j] = l;
-        for (int i = j + 1; i < 6; ++i) {
-            double x = Lc[i][j];
-            for (int q = 0; q < j; ++q) x -= Lc[i][q] * Lc[j][q];
-            Lc[i][j] = x / l;
-        }
-    }
-    for (int i = 0; i < 6; ++i) {
-        double x = -s[21 + i];
-        for (int q = 0; q < i; ++q) x -= Lc[i][q] * y[q];
-        y[i] = x / Lc[i][i];
-    }
-    for (int i = 5; i >= 0; --i) {
-        double x = y[i];
-        for (int q = i + 1; q < 6; ++q) x -= Lc[q][i] * d[q];
-        d[i] = x / Lc[i][i];
-    }
+        for (int b = a; b < 6; ++b) A[b * 6 + a] = s[k++];             // the lower triangle, which is what chol6 reads
+    chol6(A, L);
+    // chol6 does not stop at a bad pivot, and this test rejects what a test of each pivot p would: up to the first bad one the arithmetic is
+    // the same, and p <= 0, NaN or Inf gives sqrt(p) = a zero, NaN or Inf, which fails here
+    for (int j = 0; j < 6; ++j)
+        if (!(L[j * 6 + j] > 0.0) || !(L[j * 6 + j] < INFINITY)) return false;
+    for (int i = 0; i < 6; ++i) nb[i] = -s[21 + i];
+    lsolve6(L, nb, 1, d);
+    ltsolve6(L, d);
     for (int i = 0; i < 6; ++i)
         if (!(fabs(d[i]) < INFINITY)) return false;
-    icp_se3_exp(d, R, t);
+    se3_exp(d, g);
     return true;
 }
 
-// Kabsch on the centred sums, as loop_closure.hip's: S = sum (q - c)(p - c)^T - sum (q - c) mean(p - c)^T = U diag(d) V^T, R = U V^T with the
-// columns of the smallest singular value replaced by the cross product of the other two (the det sign fix); t = mean q - R mean p, in
-// the coordinates relative to c.  false: the second singular value is not positive (collinear or coincident pairs)
-__device__ bool icp_solve_point(const double* __restrict__ s, double n, double (&R)[3][3], double (&t)[3]) {
-    double S[3][3], U[3][3], V[3][3], d[3];
-    const double mp[3] = {s[0] / n, s[1] / n, s[2] / n}, mq[3] = {s[3] / n, s[4] / n, s[5] / n};
+// Kabsch on the sums relative to c (s: sum p, sum q, sum p q^T; rigid3.h takes sum q p^T).  false: the second singular value is not
+// positive (collinear or coincident pairs)
+__device__ bool icp_solve_point(const double* __restrict__ s, double n, Rigid3& g) {
+    double t[15];
+    for (int i = 0; i < 6; ++i) t[i] = s[i];
     for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) S[i][j] = s[6 + 3 * j + i] - s[3 + i] * mp[j];
-    svd3_jacobi(S, U, d, V);
-    int kmin = 0;
-    if (d[1] <= d[kmin]) kmin = 1;
-    if (d[2] <= d[kmin]) kmin = 2;
-    const int a = (kmin + 1) % 3, b = (kmin + 2) % 3;
-    if (!(fmin(d[a], d[b]) > 0.0) || !(fmax(d[a], d[b]) < INFINITY)) return false;
-    U[0][kmin] = U[1][a] * U[2][b] - U[2][a] * U[1][b];
-    U[1][kmin] = U[2][a] * U[0][b] - U[0][a] * U[2][b];
-    U[2][kmin] = U[0][a] * U[1][b] - U[1][a] * U[0][b];
-    V[0][kmin] = V[1][a] * V[2][b] - V[2][a] * V[1][b];
-    V[1][kmin] = V[2][a] * V[0][b] - V[0][a] * V[2][b];
-    V[2][kmin] = V[0][a] * V[1][b] - V[1][a] * V[0][b];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) R[i][j] = (U[i][0] * V[j][0] + U[i][1] * V[j][1]) + U[i][2] * V[j][2];
-    for (int i = 0; i < 3; ++i) t[i] = mq[i] - ((R[i][0] * mp[0] + R[i][1] * mp[1]) + R[i][2] * mp[2]);
+        for (int j = 0; j < 3; ++j) t[6 + 3 * i + j] = s[6 + 3 * j + i];
+    const KabschFit f = kabsch_from_sums(t, n);
+    if (!(fmin(f.da, f.db) > 0.0) || !(fmax(f.da, f.db) < INFINITY)) return false;
+    g = f.g;
     return true;
 }
 
@@ -210,11 +155,7 @@ __global__ void __launch_bounds__(ICP_THREADS) icp_finish_kernel(const double* _
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nt = plane ? ICP_TERMS_PLANE : ICP_TERMS_POINT;
     for (int k = wave; k < ICP_ROW; k += ICP_WAVES) {
-        double s = 0.0;
-        if (k < nt)
-            for (int b = lane; b < nblocks; b += 64) s += partial[(int64_t)b * ICP_ROW + k];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+        const double s = column_sum(partial, k < nt ? nblocks : 0, ICP_ROW, k, lane);          // (a term the estimation has not: +0)
         if (lane == 0) reinterpret_cast<double*>(tot)[k] = s;
     }
     __syncthreads();
@@ -244,18 +185,13 @@ __global__ void __launch_bounds__(ICP_THREADS) icp_finish_kernel(const double* _
     }
     state[IS_PREV] = fitness;
     state[IS_PREV + 1] = rmse;
-    double R[3][3], t[3];
-    const bool ok = plane ? (usable >= 6.0 && icp_solve_plane(s + 3, R, t)) : (count >= 3.0 && icp_solve_point(s + 3, count, R, t));
+    Rigid3 g;
+    const bool ok = plane ? (usable >= 6.0 && icp_solve_plane(s + 3, g)) : (count >= 3.0 && icp_solve_point(s + 3, count, g));
     if (!ok) { state[IS_STATUS] = (double)BS_ICP_DEGENERATE; return; }
-    // (R, t) acts on coordinates relative to c: x -> R (x - c) + t + c
+    // g acts on coordinates relative to c: x -> R (x - c) + t + c
     const double c[3] = {c0, c1, c2};
-    double* T = state + IS_T;
-    double N[12];
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 4; ++j) N[4 * i + j] = (R[i][0] * T[j] + R[i][1] * T[4 + j]) + R[i][2] * T[8 + j];
-        N[4 * i + 3] += (t[i] + c[i]) - ((R[i][0] * c[0] + R[i][1] * c[1]) + R[i][2] * c[2]);
-    }
-    for (int i = 0; i < 12; ++i) T[i] = N[i];
+    for (int i = 0; i < 3; ++i) g.t[i] = (g.t[i] + c[i]) - ((g.r[i * 3] * c[0] + g.r[i * 3 + 1] * c[1]) + g.r[i * 3 + 2] * c[2]);
+    left_apply(g, state + IS_T);
     if (it + 1 >= max_iteration) state[IS_STATUS] = (double)BS_ICP_MAX_ITERATION;
 }
 

@@ -17,8 +17,8 @@
 //     2 hypotheses        one thread per hypothesis h (strided): three distinct indices from a counter-based integer hash of
 //                         (seed, pair, h, draw) -- loop_draw below, no RNG state --, Kabsch, score = #(|R p + t - q| < tau)
 //     3 winner            the highest score, the lowest h among equals; a best score below 3 rejects the pair
-//     4 refit             n_refit rounds of Kabsch over the current inliers + recount.  Centroids and covariance are block sums in a fixed
-//                         order (thread-strided partial sums, butterfly in the wave, waves in order): no atomics, same bits in every run
+//     4 refit             n_refit rounds of Kabsch (rigid3.h) over the current inliers + recount.  Centroids and covariance are block sums
+//                         in a fixed order (thread-strided partial sums, then reduce.h's block_sum): no atomics, same bits in every run
 //     5 record            T, counts, RMSE, the information matrix; the inlier mask by match row
 // LDS: the correspondences as four arrays of 16-byte pairs -- source (x, y), (z, match row), target (x, y), (z, 0) -- 4 x 500 x 16 B =
 // 32 000 B, + 2 000 B of inlier flags + 2 x 1 024 B for the winner + 4 x 21 x 8 B of reduction scratch: 36.7 KB.  Every gather of the
@@ -29,7 +29,8 @@
 
 #include "common.h"
 #include "orb_match.h"
-#include "svd3.h"
+#include "reduce.h"
+#include "rigid3.h"
 
 namespace bs {
 namespace {
@@ -96,68 +97,39 @@ __device__ __forceinline__ void loop_sample(uint64_t seed, uint32_t pair, uint32
     idx[0] = i0; idx[1] = i1; idx[2] = i2;
 }
 
-struct Rigid {
-    double R[3][3], t[3];
-};
-
-// Kabsch from the sums: sp = sum p, sq = sum q, spq[i][j] = sum q_i p_j over n points.  S = spq - sq sp^T / n is the (summed)
-// cross-covariance; with S = U diag(d) V^T, R = U diag(1, 1, det) V^T on the smallest singular direction.  The columns of U and V that belong
-// to the smallest singular value are replaced by the cross product of the other two: for full rank that is the det sign fix, for the
-// rank 2 of a three-point sample (where the Jacobi leaves that column of U undetermined) it completes the bases.  false: the second
-// singular value is below LC_RANK_EPS (collinear or coincident points).
-__device__ bool kabsch(const double (&sp)[3], const double (&sq)[3], const double (&spq)[3][3], double n, Rigid& g) {
-    double S[3][3], U[3][3], V[3][3], d[3];
-    const double mp[3] = {sp[0] / n, sp[1] / n, sp[2] / n}, mq[3] = {sq[0] / n, sq[1] / n, sq[2] / n};
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) S[i][j] = spq[i][j] - sq[i] * mp[j];
-    svd3_jacobi(S, U, d, V);
-    int kmin = 0;
-    if (d[1] <= d[kmin]) kmin = 1;
-    if (d[2] <= d[kmin]) kmin = 2;
-    const int a = (kmin + 1) % 3, b = (kmin + 2) % 3;           // (a, b, kmin) is a cyclic order
-    if (!(fmin(d[a], d[b]) >= LC_RANK_EPS)) return false;
-    U[0][kmin] = U[1][a] * U[2][b] - U[2][a] * U[1][b];
-    U[1][kmin] = U[2][a] * U[0][b] - U[0][a] * U[2][b];
-    U[2][kmin] = U[0][a] * U[1][b] - U[1][a] * U[0][b];
-    V[0][kmin] = V[1][a] * V[2][b] - V[2][a] * V[1][b];
-    V[1][kmin] = V[2][a] * V[0][b] - V[0][a] * V[2][b];
-    V[2][kmin] = V[0][a] * V[1][b] - V[1][a] * V[0][b];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) g.R[i][j] = (U[i][0] * V[j][0] + U[i][1] * V[j][1]) + U[i][2] * V[j][2];
-    for (int i = 0; i < 3; ++i) g.t[i] = mq[i] - ((g.R[i][0] * mp[0] + g.R[i][1] * mp[1]) + g.R[i][2] * mp[2]);
-    return true;
-}
-
 // |R p + t - q|^2
-__device__ __forceinline__ double residual2(const Rigid& g, double px, double py, double pz, double qx, double qy, double qz) {
-    const double ex = (((g.R[0][0] * px + g.R[0][1] * py) + g.R[0][2] * pz) + g.t[0]) - qx;
-    const double ey = (((g.R[1][0] * px + g.R[1][1] * py) + g.R[1][2] * pz) + g.t[1]) - qy;
-    const double ez = (((g.R[2][0] * px + g.R[2][1] * py) + g.R[2][2] * pz) + g.t[2]) - qz;
+__device__ __forceinline__ double residual2(const Rigid3& g, double px, double py, double pz, double qx, double qy, double qz) {
+    const double ex = (((g.r[0] * px + g.r[1] * py) + g.r[2] * pz) + g.t[0]) - qx;
+    const double ey = (((g.r[3] * px + g.r[4] * py) + g.r[5] * pz) + g.t[1]) - qy;
+    const double ez = (((g.r[6] * px + g.r[7] * py) + g.r[8] * pz) + g.t[2]) - qz;
     return (ex * ex + ey * ey) + ez * ez;
 }
 
-// sums of K values over the block in a fixed order (trajectory_eval.hip's block_sum): every thread returns with the same totals
-template <int K>
-__device__ __forceinline__ void lc_block_sum(double (&v)[K], double* lds) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+// Kabsch (rigid3.h) over the three-point sample of hypothesis h, from the correspondences in LDS.  false: the second singular value of the
+// sample's cross-covariance is below LC_RANK_EPS (collinear or coincident points); g is then left alone.
+__device__ __forceinline__ bool lc_sample_fit(uint64_t seed, uint32_t pair, uint32_t h, int C, const f64x2* s_xy, const f64x2* s_zm, const f64x2* d_xy,
+                                              const f64x2* d_zw, Rigid3& g) {
+    int id[3];
+    loop_sample(seed, pair, h, C, id);
+    double s[15];
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
+    for (int k = 0; k < 15; ++k) s[k] = 0.0;
 #pragma unroll
-        for (int k = 0; k < K; ++k) v[k] += __shfl_xor(v[k], d, 64);
+    for (int k = 0; k < 3; ++k) {
+        const f64x2 a0 = s_xy[id[k]], a1 = s_zm[id[k]], b0 = d_xy[id[k]], b1 = d_zw[id[k]];
+        const double pp[3] = {a0[0], a0[1], a1[0]}, qq[3] = {b0[0], b0[1], b1[0]};
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            s[i] += pp[i];
+            s[3 + i] += qq[i];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) s[6 + 3 * i + j] += qq[i] * pp[j];
+        }
     }
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) lds[w * K + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double a = lds[k];
-#pragma unroll
-        for (int i = 1; i < LC_WAVES; ++i) a += lds[i * K + k];
-        v[k] = a;
-    }
+    const KabschFit f = kabsch_from_sums(s, 3.0);
+    if (!(fmin(f.da, f.db) >= LC_RANK_EPS)) return false;
+    g = f.g;
+    return true;
 }
 
 // rec [P, BS_LOOP_FIELDS] fp64: 0-15 T (row-major 4 x 4, X_train = T X_query), 16 inliers, 17 C, 18 the winning h (-1: rejected), 19 RMSE over
@@ -172,7 +144,7 @@ __global__ void __launch_bounds__(LC_THREADS) register_kernel(const double* __re
     __shared__ int red_s[LC_THREADS], red_h[LC_THREADS];
     __shared__ double red[LC_WAVES * 21];
     __shared__ int scan[LC_WAVES];
-    __shared__ Rigid fit;
+    __shared__ Rigid3 fit;
     __shared__ int fit_ok;
     const int t = threadIdx.x, p = blockIdx.x;
     double* o = rec + (int64_t)p * BS_LOOP_FIELDS;
@@ -223,24 +195,9 @@ __global__ void __launch_bounds__(LC_THREADS) register_kernel(const double* __re
         // 2: the hypotheses; a thread keeps its best (the lowest h among equal scores: h ascends)
         int my_s = 0, my_h = -1;
         for (int h = t; h < n_hyp; h += LC_THREADS) {
-            int id[3];
-            loop_sample(seed, (uint32_t)p, (uint32_t)h, C, id);
-            double sp[3] = {0, 0, 0}, sq[3] = {0, 0, 0}, spq[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const f64x2 a0 = s_xy[id[k]], a1 = s_zm[id[k]], b0 = d_xy[id[k]], b1 = d_zw[id[k]];
-                const double pp[3] = {a0[0], a0[1], a1[0]}, qq[3] = {b0[0], b0[1], b1[0]};
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    sp[i] += pp[i];
-                    sq[i] += qq[i];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) spq[i][j] += qq[i] * pp[j];
-                }
-            }
-            Rigid g;
+            Rigid3 g;
             int score = 0;
-            if (kabsch(sp, sq, spq, 3.0, g)) {
+            if (lc_sample_fit(seed, (uint32_t)p, (uint32_t)h, C, s_xy, s_zm, d_xy, d_zw, g)) {
                 for (int j = 0; j < C; ++j) {
                     const f64x2 a0 = s_xy[j], a1 = s_zm[j], b0 = d_xy[j], b1 = d_zw[j];
                     score += residual2(g, a0[0], a0[1], a1[0], b0[0], b0[1], b1[0]) < tau2;
@@ -258,24 +215,10 @@ __global__ void __launch_bounds__(LC_THREADS) register_kernel(const double* __re
                 if (red_s[i] > bs_ || (red_s[i] == bs_ && bs_ > 0 && red_h[i] < bh)) { bs_ = red_s[i]; bh = red_h[i]; }
             }
             fit_ok = 0;
-            if (bs_ >= 3) {
-                int id[3];
-                loop_sample(seed, (uint32_t)p, (uint32_t)bh, C, id);
-                double sp[3] = {0, 0, 0}, sq[3] = {0, 0, 0}, spq[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-                for (int k = 0; k < 3; ++k) {
-                    const f64x2 a0 = s_xy[id[k]], a1 = s_zm[id[k]], b0 = d_xy[id[k]], b1 = d_zw[id[k]];
-                    const double pp[3] = {a0[0], a0[1], a1[0]}, qq[3] = {b0[0], b0[1], b1[0]};
-                    for (int i = 0; i < 3; ++i) {
-                        sp[i] += pp[i];
-                        sq[i] += qq[i];
-                        for (int j = 0; j < 3; ++j) spq[i][j] += qq[i] * pp[j];
-                    }
-                }
-                Rigid g;
-                if (kabsch(sp, sq, spq, 3.0, g)) {
-                    fit = g;
-                    fit_ok = 1;
-                }
+            Rigid3 g;
+            if (bs_ >= 3 && lc_sample_fit(seed, (uint32_t)p, (uint32_t)bh, C, s_xy, s_zm, d_xy, d_zw, g)) {
+                fit = g;
+                fit_ok = 1;
             }
             red_h[0] = bh;
         }
@@ -286,7 +229,7 @@ __global__ void __launch_bounds__(LC_THREADS) register_kernel(const double* __re
 
     // 4: the inliers of the winner, then n_refit rounds of (Kabsch over the inliers, recount)
     for (int round = 0; status && round <= n_refit; ++round) {
-        const Rigid g = fit;
+        const Rigid3 g = fit;
         double cnt[1] = {0.0};
         for (int j = t; j < C; j += LC_THREADS) {
             const f64x2 a0 = s_xy[j], a1 = s_zm[j], b0 = d_xy[j], b1 = d_zw[j];
@@ -294,7 +237,7 @@ __global__ void __launch_bounds__(LC_THREADS) register_kernel(const double* __re
             flag[j] = in;
             cnt[0] += (double)in;
         }
-        lc_block_sum<1>(cnt, red);
+        block_sum<1, LC_WAVES>(cnt, red);
         n_in = (int)cnt[0];
         if (n_in < 3) { status = 0; break; }
         if (round == n_refit) break;
@@ -314,13 +257,11 @@ __global__ void __launch_bounds__(LC_THREADS) register_kernel(const double* __re
                 }
             }
         }
-        lc_block_sum<15>(s, red);
+        block_sum<15, LC_WAVES>(s, red);
         if (t == 0) {
-            const double sp[3] = {s[0], s[1], s[2]}, sq[3] = {s[3], s[4], s[5]};
-            const double spq[3][3] = {{s[6], s[7], s[8]}, {s[9], s[10], s[11]}, {s[12], s[13], s[14]}};
-            Rigid g2;
-            fit_ok = kabsch(sp, sq, spq, (double)n_in, g2) ? 1 : 0;
-            if (fit_ok) fit = g2;
+            const KabschFit f = kabsch_from_sums(s, (double)n_in);
+            fit_ok = !(fmin(f.da, f.db) >= LC_RANK_EPS) ? 0 : 1;
+            if (fit_ok) fit = f.g;
         }
         __syncthreads();
         if (!fit_ok) status = 0;
@@ -328,7 +269,7 @@ __global__ void __launch_bounds__(LC_THREADS) register_kernel(const double* __re
 
     // 5: RMSE and the information matrix over the inliers (the upper triangle, row by row); the mask by match row
     if (status) {
-        const Rigid g = fit;
+        const Rigid3 g = fit;
         double s[22];
 #pragma unroll
         for (int k = 0; k < 22; ++k) s[k] = 0.0;
@@ -357,9 +298,9 @@ __global__ void __launch_bounds__(LC_THREADS) register_kernel(const double* __re
         double s21[21];
 #pragma unroll
         for (int k = 0; k < 21; ++k) s21[k] = s[k];
-        lc_block_sum<21>(s21, red);
+        block_sum<21, LC_WAVES>(s21, red);
         double r1[1] = {s[21]};
-        lc_block_sum<1>(r1, red);
+        block_sum<1, LC_WAVES>(r1, red);
         rmse = sqrt(r1[0] / (double)n_in);
 #pragma unroll
         for (int k = 0; k < 21; ++k) info[k] = s21[k];
@@ -369,7 +310,7 @@ __global__ void __launch_bounds__(LC_THREADS) register_kernel(const double* __re
 
     if (t == 0) {
         for (int i = 0; i < 4; ++i)
-            for (int j = 0; j < 4; ++j) o[i * 4 + j] = status ? (i < 3 ? (j < 3 ? fit.R[i][j] : fit.t[i]) : (j == 3 ? 1.0 : 0.0)) : (i == j ? 1.0 : 0.0);
+            for (int j = 0; j < 4; ++j) o[i * 4 + j] = status ? (i < 3 ? (j < 3 ? fit.r[i * 3 + j] : fit.t[i]) : (j == 3 ? 1.0 : 0.0)) : (i == j ? 1.0 : 0.0);
         o[16] = status ? (double)n_in : 0.0;
         o[17] = (double)C;
         o[18] = status ? (double)best_h : -1.0;

@@ -10,6 +10,8 @@
 // (21 of the symmetric 6x6, 6 of the right-hand side, the cost, the inlier count) per block into a [blocks, 29] buffer plus a
 // second, single-block kernel that adds the partials in a fixed order -- the result does not depend on scheduling.
 #include "common.h"
+#include "reduce.h"
+#include "rigid3.h"
 
 namespace bs {
 
@@ -198,9 +200,7 @@ __global__ __launch_bounds__(256) void odo_accumulate_kernel(const float* __rest
 // one wave per term group would not be faster for a few thousand blocks
 __global__ __launch_bounds__(64) void odo_finish_kernel(const double* __restrict__ partial, int nblocks, double* __restrict__ out) {
     const int k = blockIdx.x;                 // one block (one wave) per term
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 64) s += partial[(int64_t)b * ODO_TERMS + k];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    const double s = column_sum(partial, nblocks, ODO_TERMS, k, threadIdx.x);
     if (threadIdx.x == 0) out[k] = s;
 }
 
@@ -242,35 +242,9 @@ __device__ void odo_solve(const double* __restrict__ s29, double* __restrict__ T
         for (int j = r + 1; j < 6; ++j) v -= M[r][j] * d[j];
         d[r] = v / M[r][r];
     }
-    const double wx = d[0], wy = d[1], wz = d[2];
-    const double th = sqrt(wx * wx + wy * wy + wz * wz);
-    const double Wx[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
-    double W2[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) W2[i][j] = Wx[i][0] * Wx[0][j] + Wx[i][1] * Wx[1][j] + Wx[i][2] * Wx[2][j];
-    double a, b, c;
-    if (th < 1e-12) {
-        a = 1.0; b = 0.5; c = 0.0;                 // R = I + Wx, V = I + Wx / 2 (the oracle's small-angle branch)
-    } else {
-        a = sin(th) / th;
-        b = (1.0 - cos(th)) / (th * th);
-        c = (th - sin(th)) / (th * th * th);
-    }
-    double R[3][3], V[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            const double I = i == j ? 1.0 : 0.0;
-            R[i][j] = I + a * Wx[i][j] + (th < 1e-12 ? 0.0 : b * W2[i][j]);
-            V[i][j] = I + b * Wx[i][j] + c * W2[i][j];
-        }
-    const double t[3] = {V[0][0] * d[3] + V[0][1] * d[4] + V[0][2] * d[5], V[1][0] * d[3] + V[1][1] * d[4] + V[1][2] * d[5],
-                         V[2][0] * d[3] + V[2][1] * d[4] + V[2][2] * d[5]};
-    double N[12];
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 4; ++j) N[4 * i + j] = R[i][0] * T[j] + R[i][1] * T[4 + j] + R[i][2] * T[8 + j];
-        N[4 * i + 3] += t[i];
-    }
-    for (int i = 0; i < 12; ++i) T[i] = N[i];
+    Rigid3 g;
+    se3_exp(d, g);
+    left_apply(g, T);
 }
 
 __global__ void odo_solve_kernel(const double* __restrict__ s29, double* __restrict__ T) {
@@ -287,9 +261,7 @@ __global__ __launch_bounds__(1024) void odo_finish_solve_kernel(const double* __
     out += (int64_t)blockIdx.x * ODO_TERMS;
     T += (int64_t)blockIdx.x * 12;
     for (int k = wave; k < ODO_TERMS; k += 16) {
-        double s = 0.0;
-        for (int b = lane; b < nblocks; b += 64) s += partial[(int64_t)b * ODO_TERMS + k];
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        const double s = column_sum(partial, nblocks, ODO_TERMS, k, lane);
         if (lane == 0) {
             s29[k] = s;
             out[k] = s;

@@ -46,6 +46,7 @@
 
 #include "common.h"
 #include "pc_grid.h"
+#include "rigid3.h"
 
 namespace bs {
 namespace {
@@ -194,8 +195,10 @@ __global__ void __launch_bounds__(PC_THREADS) pc_transform_kernel(const T* __res
     const int64_t i = (int64_t)blockIdx.x * PC_THREADS + threadIdx.x;
     if (i >= n) return;
     const double p0 = (double)src[3 * i], p1 = (double)src[3 * i + 1], p2 = (double)src[3 * i + 2];
+    float o[3];
+    affine_point_f32(M.a, p0, p1, p2, o);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) out[3 * i + r] = (float)(((M.a[4 * r] * p0 + M.a[4 * r + 1] * p1) + M.a[4 * r + 2] * p2) + M.a[4 * r + 3]);
+    for (int r = 0; r < 3; ++r) out[3 * i + r] = o[r];
 }
 
 // ---- statistics ----------------------------------------------------------------------------------------------------------------------------

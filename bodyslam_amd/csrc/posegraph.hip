@@ -11,7 +11,9 @@
 // checked against tests/_posegraph_solve_ref.py before it ran on a GPU).
 #include <math.h>
 
+#include "block6.h"
 #include "common.h"
+#include "reduce.h"
 
 namespace bs {
 namespace {
@@ -164,31 +166,7 @@ PG_HD inline void assemble_node(int n, int N, int E, const double* Hss, const do
     for (int i = 0; i < 6; ++i) b[(size_t)n * 6 + i] = v[i];
 }
 
-// ---- 6 x 6 blocks ------------------------------------------------------------------------------------------------------------------------
-PG_HD inline void chol6(const double* A, double* L) {               // A = L L^T, L lower; a non-positive pivot gives NaN, which the host sees
-    for (int i = 0; i < 36; ++i) L[i] = 0.0;
-    for (int j = 0; j < 6; ++j) {
-        double s = A[j * 6 + j];
-        for (int k = 0; k < j; ++k) s -= L[j * 6 + k] * L[j * 6 + k];
-        const double d = sqrt(s);
-        L[j * 6 + j] = d;
-        for (int i = j + 1; i < 6; ++i) {
-            double a = A[i * 6 + j];
-            for (int k = 0; k < j; ++k) a -= L[i * 6 + k] * L[j * 6 + k];
-            L[i * 6 + j] = a / d;
-        }
-    }
-}
-
-PG_HD inline void lsolve6(const double* L, const double* B, int cols, double* Y) {     // Y = L^-1 B, B and Y [6, cols]
-    for (int c = 0; c < cols; ++c)
-        for (int i = 0; i < 6; ++i) {
-            double a = B[i * cols + c];
-            for (int k = 0; k < i; ++k) a -= L[i * 6 + k] * Y[k * cols + c];
-            Y[i * cols + c] = a / L[i * 6 + i];
-        }
-}
-
+// ---- 6 x 6 blocks (chol6, lsolve6, ltsolve6: block6.h) ------------------------------------------------------------------------------------------------------------------------
 PG_HD inline void atb6(const double* A, const double* B, int cols, double* C) {        // C = A^T B, A [6, 6], B and C [6, cols]
     for (int i = 0; i < 6; ++i)
         for (int c = 0; c < cols; ++c) {
@@ -260,11 +238,7 @@ PG_HD inline void backsub_segment(int sidx, const int32_t* seg, int N, const dou
             for (int j = 0; j < 6; ++j) a -= w[72 + i * 6 + j] * xa[j];
             x[i] = a;
         }
-        for (int i = 5; i >= 0; --i) {               // L^T x = rhs
-            double a = x[i];
-            for (int j = i + 1; j < 6; ++j) a -= w[j * 6 + i] * x[j];
-            x[i] = a / w[i * 6 + i];
-        }
+        ltsolve6(w, x);                              // L^T x = rhs
         for (int i = 0; i < 6; ++i) delta[(size_t)k * 6 + i] = x[i], xn[i] = x[i];
     }
 }
@@ -431,16 +405,7 @@ __global__ __launch_bounds__(PG_THREADS) void pg_update_kernel(const double* X, 
     if (n < N) update_node(n, X, delta, Xn, term);
 }
 
-// One-wave reductions: lane l adds its elements l, l + 64, ... in order, then the xor butterfly 32, 16, ..., 1: a fixed order.
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    return v;
-}
-
+// One-wave reductions: lane l adds its elements l, l + 64, ... in order, then the xor butterfly (reduce.h): a fixed order.
 __global__ __launch_bounds__(64) void pg_sum_kernel(const double* v, int n, double* out) {
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += 64) s += v[i];

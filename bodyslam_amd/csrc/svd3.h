@@ -1,5 +1,5 @@
-// The 3x3 SVD both the pose chain (geom3d.hip, svd3_project_so3) and the similarity fit (trajectory_eval.hip) use: a one-sided Jacobi in
-// fp64.  One copy, so the two callers cannot drift apart; the arithmetic is the pose chain's of old, operation for operation.
+// The 3x3 SVD of every fp64 geometry kernel: a one-sided Jacobi.  One copy, so the callers cannot drift apart; the arithmetic is the pose
+// chain's of old, operation for operation.  rigid3.h builds the rotations and rigid fits on it.
 #pragma once
 #include <math.h>
 

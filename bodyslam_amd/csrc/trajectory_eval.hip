@@ -17,7 +17,8 @@
 #include <math.h>
 
 #include "common.h"
-#include "svd3.h"
+#include "reduce.h"
+#include "rigid3.h"
 
 namespace bs {
 namespace {
@@ -28,31 +29,7 @@ constexpr int SIM_GRID = 1024;    // blocks of a pass (four per CU); each walks 
 constexpr double TE_EPS = 2.220446049250313e-16;    // np.finfo(np.float64).eps
 constexpr double TE_DEG = 57.29577951308232;        // 180 / pi
 
-// sums of K values over the block: on return every thread holds the same totals, added in the same order (the butterfly inside a wave,
-// then the waves in order).  lds: TE_WAVES * K doubles; the leading barrier lets a caller reuse it from one call to the next.
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double* lds) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) v[k] += __shfl_xor(v[k], d, 64);
-    }
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) lds[w * K + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double a = lds[k];
-#pragma unroll
-        for (int i = 1; i < TE_WAVES; ++i) a += lds[i * K + k];
-        v[k] = a;
-    }
-}
-// the same for minima (v[0 .. K-1]) and maxima (v[K .. 2K-1]); NaN never enters (callers feed finite errors or the neutral +-inf)
+// reduce.h's block_sum for minima (v[0 .. K-1]) and maxima (v[K .. 2K-1]); NaN never enters (callers feed finite errors or the neutral +-inf)
 template <int K>
 __device__ __forceinline__ void block_minmax(double (&v)[2 * K], double* lds) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -92,28 +69,18 @@ struct SimFit {
 __device__ void sim_solve(const double (&mx)[3], const double (&my)[3], double sigma_x, const double (&Sxy)[3][3], bool with_scale, SimFit& f) {
     double U[3][3], V[3][3], d[3];
     svd3_jacobi(Sxy, U, d, V);
-    int kmin = 0;
-    if (d[1] <= d[kmin]) kmin = 1;
-    if (d[2] <= d[kmin]) kmin = 2;
+    const int kmin = svd3_smallest(d);
     f.rank = (d[0] > TE_EPS) + (d[1] > TE_EPS) + (d[2] > TE_EPS);
     bool flip;
     if (f.rank == 3) {
         flip = det3(Sxy) < 0.0;
     } else {
-        const int a = (kmin + 1) % 3, b = (kmin + 2) % 3;       // (a, b, kmin) is a cyclic order: u_kmin = u_a x u_b gives det(U) = +1
-        U[0][kmin] = U[1][a] * U[2][b] - U[2][a] * U[1][b];
-        U[1][kmin] = U[2][a] * U[0][b] - U[0][a] * U[2][b];
-        U[2][kmin] = U[0][a] * U[1][b] - U[1][a] * U[0][b];
+        svd3_complete_column(U, kmin);                          // u_kmin = u_a x u_b gives det(U) = +1
         flip = det3(U) * det3(V) < 0.0;
     }
     double S[3] = {1.0, 1.0, 1.0};
     if (flip) S[kmin] = -1.0;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double acc = 0;
-            for (int k = 0; k < 3; ++k) acc += U[i][k] * S[k] * V[j][k];
-            f.R[i * 3 + j] = acc;
-        }
+    svd3_usvt(U, S, V, f.R);
     const double tr = (d[0] * S[0] + d[1] * S[1]) + d[2] * S[2];          // tr(D S)
     f.s = with_scale ? tr / sigma_x : 1.0;
     f.sigma_x = sigma_x;
@@ -195,7 +162,7 @@ __global__ void __launch_bounds__(TE_THREADS) sim_pass_kernel(const T* __restric
         const double y[3] = {(double)dst[3 * tail], (double)dst[3 * tail + 1], (double)dst[3 * tail + 2]};
         sim_point<PASS>(x, y, m, acc);
     }
-    block_sum<K>(acc, lds);
+    block_sum<K, TE_WAVES>(acc, lds);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < K; ++k) partial[(int64_t)blockIdx.x * K + k] = acc[k];
@@ -266,39 +233,9 @@ int sim_launch(const T* src, const T* dst, int64_t n, char* ws, double* out, hip
 }
 
 // ---- bs_trajectory_metrics --------------------------------------------------------------------------------------------------------------
-struct Aff {          // the top three rows of a 4x4 pose: x -> r x + t (the bottom row is taken as [0 0 0 1])
-    double r[9], t[3];
-};
-__device__ __forceinline__ Aff aff_load(const double* __restrict__ p) {
-    Aff a;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) a.r[i * 3 + j] = p[i * 4 + j];
-        a.t[i] = p[i * 4 + 3];
-    }
-    return a;
-}
-__device__ __forceinline__ Aff aff_identity() {
-    Aff a;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) a.r[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    a.t[0] = a.t[1] = a.t[2] = 0.0;
-    return a;
-}
-__device__ __forceinline__ Aff aff_mul(const Aff& a, const Aff& b) {
-    Aff c;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c.r[i * 3 + j] = (a.r[i * 3] * b.r[j] + a.r[i * 3 + 1] * b.r[3 + j]) + a.r[i * 3 + 2] * b.r[6 + j];
-        c.t[i] = ((a.r[i * 3] * b.t[0] + a.r[i * 3 + 1] * b.t[1]) + a.r[i * 3 + 2] * b.t[2]) + a.t[i];
-    }
-    return c;
-}
 // evo's lie.se3_inverse: [R^T | -R^T t] (the rotation block is taken as a rotation)
-__device__ __forceinline__ Aff aff_inv_se3(const Aff& a) {
-    Aff c;
+__device__ __forceinline__ Rigid3 aff_inv_se3(const Rigid3& a) {
+    Rigid3 c;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -309,9 +246,9 @@ __device__ __forceinline__ Aff aff_inv_se3(const Aff& a) {
     return c;
 }
 // np.linalg.inv of an affine 4x4: [A^-1 | -A^-1 t], A^-1 by the adjugate (the training protocol inverts whatever block it is given)
-__device__ __forceinline__ Aff aff_inv_general(const Aff& a) {
+__device__ __forceinline__ Rigid3 aff_inv_general(const Rigid3& a) {
     const double* m = a.r;
-    Aff c;
+    Rigid3 c;
     c.r[0] = m[4] * m[8] - m[5] * m[7];
     c.r[1] = m[2] * m[7] - m[1] * m[8];
     c.r[2] = m[1] * m[5] - m[2] * m[4];
@@ -339,13 +276,13 @@ __device__ __forceinline__ double trace_abT(const double* a, const double* b) { 
 __device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
 
 struct TrajAlign {        // pose i of the prediction as evaluated: (R, t) o scale_s(O o P_i)
-    Aff O, A;
+    Rigid3 O, A;                // (the top three rows of a 4 x 4 pose; the bottom row is taken as [0 0 0 1])
     double s;
 };
-__device__ __forceinline__ Aff traj_aligned(const TrajAlign& al, const double* __restrict__ pred, int64_t i) {
-    Aff x = aff_mul(al.O, aff_load(pred + i * 16));
+__device__ __forceinline__ Rigid3 traj_aligned(const TrajAlign& al, const double* __restrict__ pred, int64_t i) {
+    Rigid3 x = rigid3_compose(al.O, rigid3_load(pred + i * 16));
     x.t[0] *= al.s; x.t[1] *= al.s; x.t[2] *= al.s;
-    return aff_mul(al.A, x);
+    return rigid3_compose(al.A, x);
 }
 
 // the four errors of index i: err[0] ATE, err[1] ARE (both when i < n), err[2] RTE, err[3] RRE (both when i < pairs)
@@ -353,28 +290,28 @@ __device__ __forceinline__ void traj_errors(int protocol, const TrajAlign& al, c
                                             int64_t i, int64_t n, int64_t pairs, int64_t step, int64_t delta, double (&err)[4]) {
     if (protocol == BS_TRAJ_EVO) {
         if (i < n) {
-            const Aff q = aff_load(gt + i * 16), p = traj_aligned(al, pred, i);
+            const Rigid3 q = rigid3_load(gt + i * 16), p = traj_aligned(al, pred, i);
             err[0] = norm3(q.t[0] - p.t[0], q.t[1] - p.t[1], q.t[2] - p.t[2]);
             err[1] = angle_of_trace(trace_abT(q.r, p.r)) * TE_DEG;                  // tr(Q^T P) = sum q_ij p_ij
         }
         if (i < pairs) {
             const int64_t a = i * step, b = a + delta;
-            const Aff qrel = aff_mul(aff_inv_se3(aff_load(gt + a * 16)), aff_load(gt + b * 16));
-            const Aff prel = aff_mul(aff_inv_se3(traj_aligned(al, pred, a)), traj_aligned(al, pred, b));
-            const Aff e = aff_mul(aff_inv_se3(qrel), prel);
+            const Rigid3 qrel = rigid3_compose(aff_inv_se3(rigid3_load(gt + a * 16)), rigid3_load(gt + b * 16));
+            const Rigid3 prel = rigid3_compose(aff_inv_se3(traj_aligned(al, pred, a)), traj_aligned(al, pred, b));
+            const Rigid3 e = rigid3_compose(aff_inv_se3(qrel), prel);
             err[2] = norm3(e.t[0], e.t[1], e.t[2]);
             err[3] = angle_of_trace((e.r[0] + e.r[4]) + e.r[8]) * TE_DEG;
         }
     } else {
         if (i < n) {
-            const Aff q = aff_load(gt + i * 16), p = aff_load(pred + i * 16);
+            const Rigid3 q = rigid3_load(gt + i * 16), p = rigid3_load(pred + i * 16);
             err[0] = norm3(q.t[0] - al.s * p.t[0], q.t[1] - al.s * p.t[1], q.t[2] - al.s * p.t[2]);
             err[1] = angle_of_trace(trace_abT(q.r, p.r));
         }
         if (i < pairs) {
             const int64_t a = i * step, b = a + delta;
-            const Aff qrel = aff_mul(aff_inv_general(aff_load(gt + a * 16)), aff_load(gt + b * 16));
-            const Aff prel = aff_mul(aff_inv_general(aff_load(pred + a * 16)), aff_load(pred + b * 16));
+            const Rigid3 qrel = rigid3_compose(aff_inv_general(rigid3_load(gt + a * 16)), rigid3_load(gt + b * 16));
+            const Rigid3 prel = rigid3_compose(aff_inv_general(rigid3_load(pred + a * 16)), rigid3_load(pred + b * 16));
             err[2] = norm3(qrel.t[0] - prel.t[0], qrel.t[1] - prel.t[1], qrel.t[2] - prel.t[2]);
             err[3] = angle_of_trace(trace_abT(qrel.r, prel.r));
         }
@@ -408,13 +345,13 @@ __global__ void __launch_bounds__(TE_THREADS) traj_metrics_kernel(const double* 
     const double* pred = pred_all + o0 * 16;
 
     TrajAlign al;
-    al.O = aff_identity();
-    al.A = aff_identity();
+    al.O = rigid3_identity();
+    al.A = rigid3_identity();
     al.s = 1.0;
     int status = BS_TRAJ_OK;
     double sigma_x = 0.0, rank = 3.0;
     if (evo) {
-        if (flags & BS_TRAJ_ALIGN_ORIGIN) al.O = aff_mul(aff_load(gt), aff_inv_se3(aff_load(pred)));
+        if (flags & BS_TRAJ_ALIGN_ORIGIN) al.O = rigid3_compose(rigid3_load(gt), aff_inv_se3(rigid3_load(pred)));
         if (flags & (BS_TRAJ_ALIGN | BS_TRAJ_CORRECT_SCALE)) {
             // the positions of the origin-aligned prediction (x) against the ground truth's (y): means, then moments about them
             double m[6] = {0, 0, 0, 0, 0, 0};
@@ -427,7 +364,7 @@ __global__ void __launch_bounds__(TE_THREADS) traj_metrics_kernel(const double* 
                     m[3 + k] += q[4 * k + 3];
                 }
             }
-            block_sum<6>(m, lds);
+            block_sum<6, TE_WAVES>(m, lds);
 #pragma unroll
             for (int k = 0; k < 6; ++k) m[k] /= (double)n;
             double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -442,7 +379,7 @@ __global__ void __launch_bounds__(TE_THREADS) traj_metrics_kernel(const double* 
                 }
                 sim_point<1>(x, y, m, acc);
             }
-            block_sum<10>(acc, lds);
+            block_sum<10, TE_WAVES>(acc, lds);
             if (t == 0) {
                 const double mx[3] = {m[0], m[1], m[2]}, my[3] = {m[3], m[4], m[5]};
                 double Sxy[3][3];
@@ -473,7 +410,7 @@ __global__ void __launch_bounds__(TE_THREADS) traj_metrics_kernel(const double* 
             const double nr = norm3(p[3], p[7], p[11]);          // np.linalg.norm(...) ** 2
             a[1] += nr * nr;
         }
-        block_sum<2>(a, lds);
+        block_sum<2, TE_WAVES>(a, lds);
         al.s = a[0] / a[1];
         sigma_x = a[1];
         if (!(a[1] > 0.0)) status = BS_TRAJ_DEGENERATE;
@@ -500,7 +437,7 @@ __global__ void __launch_bounds__(TE_THREADS) traj_metrics_kernel(const double* 
             }
         }
     }
-    block_sum<8>(sum, lds);
+    block_sum<8, TE_WAVES>(sum, lds);
     block_minmax<4>(mm, lds);
     const double cnt[4] = {(double)n, (double)n, (double)pairs, (double)pairs};
     double mean[4], dev[4] = {0, 0, 0, 0};
@@ -514,7 +451,7 @@ __global__ void __launch_bounds__(TE_THREADS) traj_metrics_kernel(const double* 
             if (k < 2 || i < pairs) dev[k] += (e[k] - mean[k]) * (e[k] - mean[k]);
         }
     }
-    block_sum<4>(dev, lds);
+    block_sum<4, TE_WAVES>(dev, lds);
     if (t == 0) {
         o[0] = (double)n;
         o[1] = (double)pairs;
