@@ -169,6 +169,11 @@ _SIGS = {
     "bs_pc_query_brute": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pc_transform": [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pc_stats": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    # k nearest neighbours, normals, the mean neighbour distance (csrc/knn.hip); the orientation vector is a pointer to 3 host doubles
+    "bs_pc_query_knn": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float,
+                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_normals": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_knn_mean_distance": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p],
     # rigid ICP registration (csrc/icp.hip); lo, hi and dims are pointers to host arrays
     "bs_icp_step": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                     C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -942,6 +947,49 @@ def pc_stats(dist, thresholds, workspace, out):
     t_, t_p = _host(thresholds, "float32", n_tau)
     check(load_library().bs_pc_stats(p(dist), dist.numel(), t_p if n_tau else None, n_tau, p(workspace), workspace.numel() * workspace.element_size(),
                                      p(out), stream_ptr()), "bs_pc_stats")
+
+
+PC_KNN_MAX = 32
+PC_ORIENT_AXIS, PC_ORIENT_DIRECTION, PC_ORIENT_CAMERA = 0, 1, 2
+
+
+def pc_query_knn(records, n_records, cell_start, lo, hi, cell_size, dims, source, k, radius, index, d2, count):
+    """the index as for pc_query_grid; source fp32 [m, 3]; radius: a positive float, math.inf = none; index int32 [m, k], d2 fp32 [m, k],
+    count int32 [m]: all on the device (include/bodyslam_hip.h)"""
+    _pts(source)
+    _i32(cell_start, index, count)
+    m, k = source.shape[0], int(k)
+    (lo_, lo_p), (hi_, hi_p), (d_, d_p) = _host(lo, "float32", 3), _host(hi, "float32", 3), _host(dims, "int32", 3)
+    assert records.dtype == torch.float32 and records.is_cuda and records.is_contiguous() and records.dim() == 2 and records.shape[1] == 4
+    assert cell_start.numel() == int(d_[0]) * int(d_[1]) * int(d_[2]) + 1 and 0 <= n_records <= records.shape[0]
+    assert d2.dtype == torch.float32 and d2.is_cuda and d2.is_contiguous() and d2.numel() == m * k and index.numel() == m * k and count.numel() == m
+    check(load_library().bs_pc_query_knn(p(records), p(cell_start), int(n_records), lo_p, hi_p, float(cell_size), d_p, p(source), m, k, float(radius),
+                                         p(index), p(d2), p(count), stream_ptr()), "bs_pc_query_knn")
+
+
+def pc_normals(points, index, count, k, orientation, vector, normals, eigenvalues=None):
+    """points fp32 [n, 3], index int32 [n, k] and count int32 [n] (the cloud's query on itself), normals fp32 [n, 3], eigenvalues fp64 [n, 3]
+    or None: all on the device; vector: 3 host doubles, or None with PC_ORIENT_AXIS"""
+    _pts(points, normals)
+    _i32(index, count)
+    n, k = points.shape[0], int(k)
+    assert tuple(normals.shape) == tuple(points.shape) and index.numel() == n * k and count.numel() == n
+    if eigenvalues is not None:
+        _f64(eigenvalues)
+        assert eigenvalues.numel() == 3 * n
+    v_, v_p = (None, None) if vector is None else _host(vector, "float64", 3)
+    check(load_library().bs_pc_normals(p(points), n, p(index), p(count), k, int(orientation), v_p, p(normals), p(eigenvalues), stream_ptr()),
+          "bs_pc_normals")
+
+
+def pc_knn_mean_distance(d2, count, k, avg):
+    """d2 fp32 [m, k], count int32 [m], avg fp32 [m]: all on the device"""
+    _i32(count)
+    m, k = count.numel(), int(k)
+    for t in (d2, avg):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()
+    assert d2.numel() == m * k and avg.numel() == m
+    check(load_library().bs_pc_knn_mean_distance(p(d2), p(count), m, k, p(avg), stream_ptr()), "bs_pc_knn_mean_distance")
 
 
 ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1

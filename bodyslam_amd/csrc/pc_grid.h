@@ -1,6 +1,6 @@
-// The uniform grid of the cloud-to-cloud distances and the walk over it, shared by the query (pointcloud.hip, bs_pc_query_grid) and the
-// ICP step (icp.hip, bs_icp_step): one copy of the cell function, the candidate test, the 16-byte record load and the conservative bound,
-// so the two kernels cannot drift apart.  The arithmetic and the derivation of the bound are at the top of pointcloud.hip.
+// The uniform grid of the cloud-to-cloud distances and the walk over it, shared by the query (pointcloud.hip, bs_pc_query_grid), the
+// ICP step (icp.hip, bs_icp_step) and the k-nearest-neighbour query (knn.hip, bs_pc_query_knn): one copy of the cell function, the
+// candidate test, the 16-byte record load and the conservative bound, so the kernels cannot drift apart.  The arithmetic and the derivation of the bound are at the top of pointcloud.hip.
 #pragma once
 #include <math.h>
 
@@ -30,41 +30,64 @@ __device__ __forceinline__ void pc_candidate(const f32x4 t, float sx, float sy, 
     if (d2 < best || (d2 == best && id < bi)) { best = d2; bi = id; }
 }
 
-// The Chebyshev shells r = 0, 1, 2, ... of cells around the (clamped) cell of the finite source (sx, sy, sz): best = the minimum d2,
-// bi = its original index (PC_NONE: no candidate seen).  true: the search is complete -- the bound holds, every cell has been seen, or
-// the shell covers max_distance.  false: the source was still searching after shell `shell_cap` (the caller finishes it some other way).
-__device__ __forceinline__ bool pc_walk_shells(const f32x4* __restrict__ records, const int32_t* __restrict__ cell_start, const PcGrid& g,
-                                               float sx, float sy, float sz, float max_distance, int32_t shell_cap, float& best, int32_t& bi) {
+// The k = 1 sink of the walk below: the minimum of (d2, original index).
+struct PcMinSink {
+    float sx, sy, sz, best;
+    int32_t bi;
+    __device__ __forceinline__ void add(const f32x4 t) { pc_candidate(t, sx, sy, sz, best, bi); }
+    __device__ __forceinline__ bool bounded(float lb2) const { return best < lb2; }      // nothing unvisited can change the result
+};
+
+// The Chebyshev shells r = 0, 1, 2, ... of cells around the (clamped) cell of the finite source (sx, sy, sz), ONE copy for every kernel
+// that searches the grid: each record goes to sink.add(record); after a shell the search is complete when sink.bounded(lb * lb) -- what
+// the sink keeps is strictly below the bound on everything unvisited --, when every cell has been seen, or when the shell covers
+// max_distance: true.  false: the source was still searching after shell `shell_cap` (the caller finishes it some other way).
+template <typename Sink>
+__device__ __forceinline__ bool pc_walk(const f32x4* __restrict__ records, const int32_t* __restrict__ cell_start, const PcGrid& g, float sx,
+                                        float sy, float sz, float max_distance, int32_t shell_cap, Sink& sink) {
     const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
     const int cx = pc_cell(sx, g.lo[0], g.h, nx), cy = pc_cell(sy, g.lo[1], g.h, ny), cz = pc_cell(sz, g.lo[2], g.h, nz);
     const float slack = fmaxf(fmaxf((g.hi[0] - g.lo[0]) + fabsf(sx - g.lo[0]), (g.hi[1] - g.lo[1]) + fabsf(sy - g.lo[1])),
                               (g.hi[2] - g.lo[2]) + fabsf(sz - g.lo[2])) * 4.76837158203125e-07f;       // 2^-21
     const int r_all = max(max(max(cx, nx - 1 - cx), max(cy, ny - 1 - cy)), max(cz, nz - 1 - cz));      // after this shell: every cell seen
-    best = INFINITY;
-    bi = PC_NONE;
     for (int r = 0;; ++r) {
         const int z0 = max(cz - r, 0), z1 = min(cz + r, nz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, ny - 1);
         const int x0 = max(cx - r, 0), x1 = min(cx + r, nx - 1);
         for (int z = z0; z <= z1; ++z)
             for (int y = y0; y <= y1; ++y) {
                 const int row = (z * ny + y) * nx;
+                // the row's records as up to two runs, and ONE place where a record meets the sink: a sink that keeps a list in registers
+                // (knn.hip) is inlined once, not three times
+                int32_t b0 = 0, e0 = 0, b1 = 0, e1 = 0;
                 if (abs(z - cz) == r || abs(y - cy) == r) {             // a face row of the shell: its cells are one run of records
-                    for (int32_t k = cell_start[row + x0], e = cell_start[row + x1 + 1]; k < e; ++k) pc_candidate(records[k], sx, sy, sz, best, bi);
+                    b0 = cell_start[row + x0];
+                    e0 = cell_start[row + x1 + 1];
                 } else {                                                // an inner row: the two end cells
-                    if (cx - r >= 0)
-                        for (int32_t k = cell_start[row + cx - r], e = cell_start[row + cx - r + 1]; k < e; ++k)
-                            pc_candidate(records[k], sx, sy, sz, best, bi);
-                    if (cx + r <= nx - 1)
-                        for (int32_t k = cell_start[row + cx + r], e = cell_start[row + cx + r + 1]; k < e; ++k)
-                            pc_candidate(records[k], sx, sy, sz, best, bi);
+                    if (cx - r >= 0) { b0 = cell_start[row + cx - r]; e0 = cell_start[row + cx - r + 1]; }
+                    if (cx + r <= nx - 1) { b1 = cell_start[row + cx + r]; e1 = cell_start[row + cx + r + 1]; }
+                }
+#pragma clang loop unroll(disable)
+                for (int part = 0; part < 2; ++part) {
+                    const int32_t e = part ? e1 : e0;
+                    for (int32_t k = part ? b1 : b0; k < e; ++k) sink.add(records[k]);
                 }
             }
         if (r >= r_all) return true;
         const float lb = ((float)r * g.h - slack) * 0.99999f;
-        if (lb > 0.0f && best < lb * lb) return true;
+        if (lb > 0.0f && sink.bounded(lb * lb)) return true;
         if (lb * 0.9999f > max_distance) return true;
         if (r >= shell_cap) return false;
     }
+}
+
+// The k = 1 search: best = the minimum d2, bi = its original index (PC_NONE: no candidate seen).
+__device__ __forceinline__ bool pc_walk_shells(const f32x4* __restrict__ records, const int32_t* __restrict__ cell_start, const PcGrid& g,
+                                               float sx, float sy, float sz, float max_distance, int32_t shell_cap, float& best, int32_t& bi) {
+    PcMinSink sink{sx, sy, sz, INFINITY, PC_NONE};
+    const bool done = pc_walk(records, cell_start, g, sx, sy, sz, max_distance, shell_cap, sink);
+    best = sink.best;
+    bi = sink.bi;
+    return done;
 }
 
 inline bool pc_grid_ok(const PcGrid& g) {

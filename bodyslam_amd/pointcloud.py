@@ -10,6 +10,11 @@ So the answer does not depend on the spatial index at all -- not on the cell siz
 ``NearestNeighbours`` builds a uniform grid over the finite target points once (csrc/pointcloud.hip: bounds, counts per cell, a scan,
 a scatter into 16-byte records); ``query`` walks the shells of cells around every source point and hands the few points that are far
 from everything to the brute-force kernel.  There is no CPU fallback: without a GPU the calls raise BodySlamHipError.
+
+``query_knn`` extends the same walk from the minimum to the k smallest under the same total order (csrc/knn.hip; Open3D's
+search_knn_vector_3d / search_hybrid_vector_3d), and two things stand on it: ``estimate_normals`` (PointCloud.estimate_normals) and
+``remove_statistical_outlier`` (PointCloud.remove_statistical_outlier).  Restated, parity with Open3D unpinned; the statement is
+tests/_knn_ref.py.  Not built: pure radius search with an unbounded list, voxel down-sampling, orientation propagation, k > 32.
 """
 from __future__ import annotations
 
@@ -70,6 +75,41 @@ def _check_max_distance(max_distance) -> float:
     if not v >= 0.0:
         raise ValueError(f"max_distance {max_distance!r}: expected None or a number >= 0")
     return v
+
+
+def _check_k(k, what: str = "k") -> int:
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= L.PC_KNN_MAX:
+        raise ValueError(f"{what} {k!r}: expected an integer in 1 .. {L.PC_KNN_MAX}")
+    return int(k)
+
+
+def _check_radius(radius) -> float:
+    """None -> inf (no radius); otherwise a positive number, finite and non-zero in fp32"""
+    if radius is None:
+        return math.inf
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise ValueError(f"radius {radius!r}: expected None or a positive number")
+    with np.errstate(over="ignore"):
+        v = float(np.float32(radius))
+    if not (v > 0.0 and math.isfinite(v)):
+        raise ValueError(f"radius {radius!r}: expected None or a positive number (finite and non-zero in fp32)")
+    return v
+
+
+def _check_orientation(direction, camera_location) -> Tuple[int, Optional[np.ndarray]]:
+    if direction is not None and camera_location is not None:
+        raise ValueError("direction and camera_location are mutually exclusive")
+    for name, v, mode in (("direction", direction, L.PC_ORIENT_DIRECTION), ("camera_location", camera_location, L.PC_ORIENT_CAMERA)):
+        if v is None:
+            continue
+        try:
+            a = np.asarray(_np(v), dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: expected three finite numbers") from None
+        if a.shape != (3,) or not np.isfinite(a).all():
+            raise ValueError(f"{name}: expected three finite numbers")
+        return mode, a
+    return L.PC_ORIENT_AXIS, None
 
 
 def grid_dims(lo: np.ndarray, hi: np.ndarray, h: float) -> np.ndarray:
@@ -179,6 +219,98 @@ class NearestNeighbours:
                 keys = torch.empty(m, dtype=torch.int64, device=self.dev)
                 L.pc_query_brute(self.records, self.n_finite, s, None, m, md, keys, dist, index)
         return dist, index
+
+
+    def query_knn(self, source, k: int, radius: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """-> (index int32 [m, k], d2 fp32 [m, k], count int32 [m]), device tensors: for every source point its k nearest target points --
+        Open3D's KDTreeFlann.search_knn_vector_3d, and with `radius` search_hybrid_vector_3d (restated, parity unpinned).
+
+        The neighbours are the k lexicographically smallest (d2, index in the target as given) among the finite target points, ascending,
+        d2 in ``query``'s fp32 arithmetic; with a radius a candidate counts only when sqrtf(d2) <= radius in fp32 (a target at exactly
+        the radius is in).  Rows are padded with index -1 and d2 +inf; a source point with a non-finite coordinate gets count 0, index
+        -1 and d2 NaN.  A source that is a point of the target finds itself first (d2 = 0).  1 <= k <= 32; for k = 1 the result is
+        ``query``'s.  The walk has no shell cap and no brute-force fallback: a source far from every target, or a k above the number of
+        targets in reach, costs time and never changes the result.  Pure radius search with an unbounded list is not built."""
+        k = _check_k(k)
+        r = _check_radius(radius)
+        s = as_points(source, "source")
+        with torch.cuda.device(self.dev):
+            s = s.to(self.dev).to(torch.float32).contiguous()
+            m = int(s.shape[0])
+            index = torch.empty(m, k, dtype=torch.int32, device=self.dev)
+            d2 = torch.empty(m, k, dtype=torch.float32, device=self.dev)
+            count = torch.empty(m, dtype=torch.int32, device=self.dev)
+            L.pc_query_knn(self.records, self.n_finite, self.cell_start, self.lo, self.hi, self.cell_size, self.dims, s, k, r, index, d2, count)
+        return index, d2, count
+
+
+def estimate_normals(points, k: int = 30, radius: Optional[float] = None, direction=None, camera_location=None,
+                     cell_size: Optional[float] = None, device: int = 0, return_eigenvalues: bool = False):
+    """Normals of a cloud that has none -> fp32 [n, 3] device tensor (and, with return_eigenvalues, the eigenvalues fp64 [n, 3] ascending):
+    Open3D's PointCloud.estimate_normals with KDTreeSearchParamKNN(k) or, with `radius`, KDTreeSearchParamHybrid(radius, k).  Open3D is
+    not vendored: the meaning is restated from its documentation and parity with Open3D is unpinned; the statement is tests/_knn_ref.py.
+
+    Per point, over its neighbours in ``query_knn``'s order (itself included), in fp64: the covariance C of the neighbours, the Jacobi
+    eigen-decomposition of csrc/svd3.h, the unit eigenvector of the smallest eigenvalue, rounded to fp32 once.  The normal is zero when
+    there are fewer than 3 neighbours or the largest eigenvalue is not positive and finite -- the convention of PointCloud.normals and of
+    registration_icp: a zero normal leaves its pairs out; for exactly collinear neighbours the direction is unspecified.  Sign:
+    direction=v flips when n . v < 0, camera_location=c when n . (c - p) < 0 (the two exclude each other); with neither, the component
+    of largest magnitude is made positive, so that the result is deterministic.  No propagation of the orientation along a spanning tree.
+    The cell size changes the time, never the bits.  Raises ValueError on bad arguments before the GPU is touched."""
+    k = _check_k(k)
+    _check_radius(radius)
+    mode, vec = _check_orientation(direction, camera_location)
+    _check_cell_size(cell_size)
+    as_points(points, "points")
+    nn = NearestNeighbours(points, cell_size=cell_size, device=device)
+    with torch.cuda.device(nn.dev):
+        index, _, count = nn.query_knn(nn.target, k, radius)
+        n = len(nn)
+        normals = torch.empty(n, 3, dtype=torch.float32, device=nn.dev)
+        eig = torch.empty(n, 3, dtype=torch.float64, device=nn.dev) if return_eigenvalues else None
+        L.pc_normals(nn.target, index, count, k, mode, vec, normals, eig)
+    return (normals, eig) if return_eigenvalues else normals
+
+
+def knn_mean_distance(points, nb_neighbors: int = 20, cell_size: Optional[float] = None, device: int = 0) -> torch.Tensor:
+    """fp32 [n] device tensor: for every point the mean distance to its nb_neighbors nearest points of the same cloud, itself included --
+    fl32((sum_j (double) sqrtf(d2_j)) / count) in ``query_knn``'s order; NaN for a non-finite point."""
+    k = _check_k(nb_neighbors, "nb_neighbors")
+    _check_cell_size(cell_size)
+    as_points(points, "points")
+    nn = NearestNeighbours(points, cell_size=cell_size, device=device)
+    with torch.cuda.device(nn.dev):
+        _, d2, count = nn.query_knn(nn.target, k)
+        avg = torch.empty(len(nn), dtype=torch.float32, device=nn.dev)
+        L.pc_knn_mean_distance(d2, count, k, avg)
+    return avg
+
+
+def remove_statistical_outlier(points, nb_neighbors: int = 20, std_ratio: float = 2.0, cell_size: Optional[float] = None,
+                               device: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (the kept indices int64 ascending, the mask bool [n]), device tensors: Open3D's PointCloud.remove_statistical_outlier, which the
+    reference runs on its scene cloud with (20, 2.0) (restated, parity unpinned; tests/_knn_ref.py).
+
+    avg = ``knn_mean_distance``; over its finite entries bs_pc_stats gives n, sum and sum of squares in its fixed order; in fp64
+    mean = sum / n, std = sqrt(max(sumsq - n mean^2, 0) / (n - 1)) (0 for n < 2); a point is kept when (double) avg < mean + std_ratio std.
+    A non-finite point is never kept.  1 <= nb_neighbors <= 32.  Raises ValueError on bad arguments before the GPU is touched."""
+    if isinstance(std_ratio, bool) or not isinstance(std_ratio, (int, float, np.integer, np.floating)) or not math.isfinite(float(std_ratio)):
+        raise ValueError(f"std_ratio {std_ratio!r}: expected a finite number")
+    avg = knn_mean_distance(points, nb_neighbors, cell_size=cell_size, device=device)
+    with torch.cuda.device(avg.device):
+        ws = torch.empty(L.PC_STATS_WORKSPACE_BYTES, dtype=torch.uint8, device=avg.device)
+        out = torch.empty(L.PC_STATS_FIELDS, dtype=torch.float64, device=avg.device)
+        L.pc_stats(avg, (), ws, out)
+        rec = out.cpu().numpy()
+        n, total, sumsq = rec[1], rec[4], rec[5]
+        if n == 0:
+            threshold = math.nan
+        else:
+            mean = total / n
+            std = math.sqrt(max(sumsq - n * mean * mean, 0.0) / (n - 1)) if n >= 2 else 0.0
+            threshold = mean + float(std_ratio) * std
+        mask = avg.to(torch.float64) < threshold                     # (the compaction is plumbing: a comparison and torch.nonzero)
+        return torch.nonzero(mask).reshape(-1), mask
 
 
 def point_cloud_distance(source, target, cell_size: Optional[float] = None, device: int = 0, max_distance: Optional[float] = None,

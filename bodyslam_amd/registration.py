@@ -13,8 +13,9 @@ state -- status, iteration count, transform, log -- once per chunk: once a statu
 first instruction.  There is no CPU fallback: without a GPU the calls raise BodySlamHipError.
 
 Not built: scale estimation (point-to-point with Umeyama scale recovers a true 1.03 as 1.006 on the test surface: the scale comes from the
-trajectory, evaluation.similarity_transform, and ICP refines rigidly), robust kernels, normal estimation for clouds that have none, global
-registration, coloured and generalised ICP, multi-scale schedules.
+trajectory, evaluation.similarity_transform, and ICP refines rigidly), robust kernels, global registration, coloured and generalised ICP,
+multi-scale schedules.  (Normals for a cloud that has none: pointcloud.estimate_normals / PointCloud.estimate_normals, then
+target_normals= or a PointCloud target.)
 """
 from __future__ import annotations
 

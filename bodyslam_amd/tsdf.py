@@ -76,6 +76,29 @@ class PointCloud:
         from .pointcloud import point_cloud_distance
         return point_cloud_distance(self, target)[0].cpu().numpy().astype(np.float64)
 
+    def estimate_normals(self, k: int = 30, radius: Optional[float] = None, direction=None, camera_location=None):
+        """o3d.geometry.PointCloud.estimate_normals with a k-NN (or, with `radius`, hybrid) search: sets and returns ``self.normals`` --
+        numpy float32 [M, 3] when `points` is numpy, a device tensor when extract_pcd(host=False) made the cloud.
+        pointcloud.estimate_normals states the arithmetic and the sign rule; restated, parity with Open3D unpinned."""
+        from .pointcloud import estimate_normals
+        n = estimate_normals(self.points, k=k, radius=radius, direction=direction, camera_location=camera_location)
+        self.normals = n.cpu().numpy() if isinstance(self.points, np.ndarray) else n
+        return self.normals
+
+    def remove_statistical_outlier(self, nb_neighbors: int, std_ratio: float):
+        """o3d.geometry.PointCloud.remove_statistical_outlier -> (the PointCloud of the kept rows -- points, colours and normals --, their
+        indices int64 ascending: numpy for a numpy cloud, device tensors otherwise).  pointcloud.remove_statistical_outlier states the
+        rule; restated, parity with Open3D unpinned."""
+        from .pointcloud import remove_statistical_outlier
+        ind, _ = remove_statistical_outlier(self.points, nb_neighbors=nb_neighbors, std_ratio=std_ratio)
+
+        def rows(a):
+            if a is None:
+                return None
+            return a[ind.cpu().numpy()] if isinstance(a, np.ndarray) else a[ind.to(a.device)]
+        ind_out = ind.cpu().numpy() if isinstance(self.points, np.ndarray) else ind
+        return PointCloud(rows(self.points), rows(self.colors), rows(self.normals)), ind_out
+
 
 @dataclass
 class TriangleMesh:

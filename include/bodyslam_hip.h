@@ -678,6 +678,49 @@ int bs_pc_transform(const void* source, int32_t dtype, int64_t n, const double* 
 int bs_pc_stats(const float* dist, int64_t n, const float* thresholds, int32_t n_thresholds, void* workspace, int64_t workspace_bytes, double* out,
                 void* stream);
 
+/* ---- k nearest neighbours, normal estimation, statistical outlier removal --------------------------------------------------------------
+ * bs_pc_query_knn replaces Open3D's KDTreeFlann.search_knn_vector_3d and search_hybrid_vector_3d, bs_pc_normals PointCloud.estimate_normals
+ * (the reference calls it at BodySLAM_not_refactored/3DM/mapping_module.py:184; Open3D's default search there is k-NN with k = 30), and
+ * bs_pc_knn_mean_distance with bs_pc_stats PointCloud.remove_statistical_outlier (mapping_module.py:87, nb_neighbors = 20, std_ratio = 2).
+ * Restated from Open3D's documented meaning; parity with Open3D is UNPINNED.  The statement is tests/_knn_ref.py.
+ *   neighbours      the arithmetic of the block above: d2 = (dx dx + dy dy) + dz dz in fp32, no contraction; the neighbours of a source are
+ *                   the k lexicographically smallest (d2, original target index) among the finite target points, ascending.  With a radius
+ *                   (hybrid search; +inf: none) a candidate counts only when sqrtf(d2) <= radius, compared in fp32 -- the comparison
+ *                   max_distance uses; a target at exactly the radius is in.  A source that is the target's own point finds itself first
+ *                   (d2 = 0), as in Open3D.  1 <= k <= BS_PC_KNN_MAX.  For k = 1 the result is bs_pc_query_grid's.  Pure radius search
+ *                   with an unbounded list is not built
+ *   bs_pc_query_knn one thread per source [m, 3] fp32 (device) over the index of bs_pc_grid_scatter: the Chebyshev shells of
+ *                   bs_pc_query_grid (the same device function) keeping the k best in registers, until the list is full and its worst d2
+ *                   is strictly below the square of the bound on everything unvisited, every cell has been seen, or the shell covers
+ *                   the radius.  No shell cap and no brute-force fallback: a source far from every target, or a k above the number of
+ *                   targets in reach, walks on until one of the three holds (time, never the result).  index int32 [m, k] padded with
+ *                   -1, d2 fp32 [m, k] padded with +inf, count int32 [m] (all device); a source with a non-finite coordinate gets count
+ *                   0, index -1 and d2 NaN.  The radius becomes an fp32 cut-off on d2 on the host: the largest d2 with
+ *                   sqrtf(d2) <= radius
+ *   bs_pc_normals   one thread per point of points [n, 3] fp32 (device) with the lists index / count [n, k] of the cloud's query on
+ *                   itself, in fp64 over the neighbours j = 0 .. count - 1 in list order: q_j = (double) t[idx_j] - (double) p,
+ *                   S = sum q_j, M = sum q_j q_j^T added sequentially (one product and one add each, no contraction),
+ *                   C = M / count - (S / count)(S / count)^T, the 3 x 3 Jacobi SVD of C (symmetric PSD: its singular triplets are the
+ *                   eigenpairs); the normal is the normalised column of V with the smallest singular value (ties: the lowest column),
+ *                   rounded to fp32 once at the end.  Zero when count < 3 or the largest eigenvalue is not positive and finite (the
+ *                   convention of bs_icp_step: a zero normal leaves its pairs out); for exactly collinear neighbours the direction is
+ *                   unspecified (finite, and unit or zero).  Sign: BS_PC_ORIENT_DIRECTION flips when n . v < 0, BS_PC_ORIENT_CAMERA when
+ *                   n . (v - p) < 0 (fp64; vector: 3 host doubles), BS_PC_ORIENT_AXIS makes the component of largest magnitude positive
+ *                   (the first such on ties).  eigenvalues: NULL, or fp64 [n, 3] (device), ascending (zeros for an empty list)
+ *   bs_pc_knn_mean_distance   one thread per row: avg fp32 [m] = fl32((sum_j (double) sqrtf(d2[i, j])) / count[i]), j = 0 .. count - 1 in
+ *                   order; NaN for an empty list.  The outlier rule is the caller's: bs_pc_stats over avg gives n, sum and sum of squares;
+ *                   mean = sum / n, std = sqrt(max(sumsq - n mean^2, 0) / (n - 1)) (0 for n < 2), a point is kept when
+ *                   (double) avg < mean + std_ratio std
+ * No floating-point atomics: the same bits in every run, for every cell size. */
+#define BS_PC_KNN_MAX 32
+enum { BS_PC_ORIENT_AXIS = 0, BS_PC_ORIENT_DIRECTION = 1, BS_PC_ORIENT_CAMERA = 2 };
+int bs_pc_query_knn(const void* records, const int32_t* cell_start, int64_t n_records, const float* lo, const float* hi, float cell_size,
+                    const int32_t* dims, const float* source, int64_t m, int32_t k, float radius, int32_t* index, float* d2, int32_t* count,
+                    void* stream);
+int bs_pc_normals(const float* points, int64_t n, const int32_t* index, const int32_t* count, int32_t k, int32_t orientation,
+                  const double* vector, float* normals, double* eigenvalues, void* stream);
+int bs_pc_knn_mean_distance(const float* d2, const int32_t* count, int64_t m, int32_t k, float* avg, void* stream);
+
 /* ---- rigid ICP registration ------------------------------------------------------------------------------------------------------------
  * bs_icp_step + bs_icp_finish replace Open3D's pipelines.registration.registration_icp with TransformationEstimationPointToPlane or
  * TransformationEstimationPointToPoint (no scale) and ICPConvergenceCriteria, and, in BS_ICP_EVALUATE mode, evaluate_registration: what
