@@ -17,15 +17,9 @@
 
 namespace bs {
 
-struct TsdfCam {
-    double fx, fy, cx, cy;
-    double e[12];            // extrinsic, rows 0..2 of the 4x4 (world -> camera)
-    double ifx, ify;         // 1 / fx, 1 / fy (host-computed: the per-voxel code multiplies instead of dividing)
-};
-
 // ---- the table of volume units: an open-addressing hash table in HBM (Open3D: std::unordered_map<Vector3i, VolumeUnit>) ----------
 // key = three 21-bit biased unit indices; keys[h] == -1 is empty; slots[h] is the unit's block number (assigned in the second pass),
-// stamp[h] the id of the last frame that touched it.
+// fmask[h] the records of the pass under way that touch the unit (zero between passes).
 constexpr long long TS_EMPTY = -1ll;
 constexpr int TS_OFF = 1 << 20;
 
@@ -49,193 +43,25 @@ __device__ __forceinline__ float* ts_block(const int64_t* __restrict__ slab_base
     return reinterpret_cast<float*>(slab_base[slot / slab_units] + (int64_t)(slot % slab_units) * unit_bytes);
 }
 
-// ScalableTSDFVolume::Integrate, first half: every unit that meets the +-sdf_trunc box of a point of the strided depth sample is
-// looked up / inserted and stamped with this frame.  Thread = (sampled pixel, candidate offset inside the (span)^3 box).
-__global__ __launch_bounds__(256) void tsdf_touch_kernel(const float* __restrict__ depth, int H, int W, int stride, TsdfCam cam /* e = camera -> world */,
-                                                          double unit_length, double sdf_trunc, int span, long long* keys, int32_t* stamp,
-                                                          unsigned mask, int frame_id, int32_t* counters) {
-    const int cand = span * span * span;
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int ws = (W + stride - 1) / stride, hs = (H + stride - 1) / stride;
-    if (t >= (int64_t)ws * hs * cand) return;
-    const int c = (int)(t % cand), pix = (int)(t / cand);
-    const int i = (pix / ws) * stride, j = (pix % ws) * stride;
-    const double z = (double)depth[(int64_t)i * W + j];
-    if (!(z > 0.0)) return;
-    const double x = ((double)j - cam.cx) * z / cam.fx, y = ((double)i - cam.cy) * z / cam.fy;
-    const double p[3] = {cam.e[0] * x + cam.e[1] * y + cam.e[2] * z + cam.e[3], cam.e[4] * x + cam.e[5] * y + cam.e[6] * z + cam.e[7],
-                         cam.e[8] * x + cam.e[9] * y + cam.e[10] * z + cam.e[11]};
-    const int o[3] = {c / (span * span), (c / span) % span, c % span};
-    int u[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const int lo = (int)floor((p[a] - sdf_trunc) / unit_length), hi = (int)floor((p[a] + sdf_trunc) / unit_length);
-        u[a] = lo + o[a];
-        if (u[a] > hi) return;
-    }
-    const long long k = ts_pack(u[0], u[1], u[2]);
-    for (unsigned h = ts_hash(k, mask), n = 0; n <= mask; h = (h + 1) & mask, ++n) {
-        long long cur = keys[h];
-        if (cur == TS_EMPTY) cur = (long long)atomicCAS(reinterpret_cast<unsigned long long*>(keys + h), (unsigned long long)TS_EMPTY, (unsigned long long)k);
-        if (cur == TS_EMPTY || cur == k) {
-            stamp[h] = frame_id;
-            return;
-        }
-    }
-    counters[2] = 1;      // table full
-}
-
-// second half: entries stamped by this frame get a block number if they have none, and go on the frame's list -- unless the unit lies
-// wholly outside the view frustum.  Units are opened in a +-sdf_trunc box around every sampled point, far wider than the frustum at
-// endoscopic range (round 2, PMC: 90 % of the integrate kernel's threads projected outside the image and left): a unit whose
-// bounding sphere is behind the camera or projects wholly outside the image holds no voxel the integration would update, so it
-// is opened (as in Open3D) but not put on the list.  `view` = world -> camera, W x H the image; conservative bound, see below.
-__global__ __launch_bounds__(256) void tsdf_assign_kernel(const long long* __restrict__ keys, int32_t* slots, const int32_t* __restrict__ stamp,
-                                                           unsigned cap, int frame_id, int32_t* unit_index, int max_units, int32_t* counters,
-                                                           int32_t* touched, TsdfCam view, double unit_length, int W, int H, int cull) {
-    const unsigned h = blockIdx.x * 256 + threadIdx.x;
-    if (h >= cap || keys[h] == TS_EMPTY || stamp[h] != frame_id) return;
-    int s = slots[h];
-    if (s < 0) {
-        s = atomicAdd(counters + 0, 1);
-        if (s >= max_units) {
-            // more units than blocks (max_units = the blocks that EXIST: the caller keeps slabs allocated ahead of the map).  The
-            // count is put back, so the table entry stays without a block and a later frame -- after the caller has added slabs or
-            // raised the error -- can still assign one.
-            atomicSub(counters + 0, 1);
-            counters[2] = 2;
-            return;
-        }
-        slots[h] = s;
-        const long long k = keys[h];
-        unit_index[3 * s + 0] = (int)(k >> 42) - TS_OFF;
-        unit_index[3 * s + 1] = (int)((k >> 21) & ((1 << 21) - 1)) - TS_OFF;
-        unit_index[3 * s + 2] = (int)(k & ((1 << 21) - 1)) - TS_OFF;
-    }
-    if (cull) {
-        const long long k = keys[h];
-        const double c[3] = {((double)((int)(k >> 42) - TS_OFF) + 0.5) * unit_length, ((double)((int)((k >> 21) & ((1 << 21) - 1)) - TS_OFF) + 0.5) * unit_length,
-                             ((double)((int)(k & ((1 << 21) - 1)) - TS_OFF) + 0.5) * unit_length};
-        const double r = 0.8660254037844387 * unit_length;           // half the cube's diagonal
-        const double qx = view.e[0] * c[0] + view.e[1] * c[1] + view.e[2] * c[2] + view.e[3];
-        const double qy = view.e[4] * c[0] + view.e[5] * c[1] + view.e[6] * c[2] + view.e[7];
-        const double qz = view.e[8] * c[0] + view.e[9] * c[1] + view.e[10] * c[2] + view.e[11];
-        if (qz + r <= 0.0) return;                                   // wholly behind the camera
-        if (qz > r) {                                                // (a sphere that reaches the camera plane is never culled)
-            // a point p = q + d, |d| <= r, projects within  f r / (qz - r) * (1 + |qx| / qz)  pixels of q's projection:
-            // |px / pz - qx / qz| = |dx qz - qx dz| / (pz qz) <= r (qz + |qx|) / ((qz - r) qz)
-            const double inv = 1.0 / (qz - r);
-            const double ru = view.fx * r * inv * (1.0 + fabs(qx) / qz) + 1.0, rv = view.fy * r * inv * (1.0 + fabs(qy) / qz) + 1.0;
-            const double uc = qx * view.fx / qz + view.cx + 0.5, vc = qy * view.fy / qz + view.cy + 0.5;
-            if (uc + ru < 0.0 || uc - ru > (double)W || vc + rv < 0.0 || vc - rv > (double)H) return;
-        }
-    }
-    touched[atomicAdd(counters + 1, 1)] = s;
-}
-
-// Open3D UniformTSDFVolume::IntegrateWithDepthToCameraDistanceMultiplier, one thread per voxel.  Grid: blocks_per_unit x an UPPER
-// BOUND of the touched units, folded into blockIdx.x (no 65 535 limit); the number of units this frame really touched is read
-// from device memory (counters[1], written by tsdf_assign_kernel), so the host never has to wait for it.
-// (Units wholly outside the view frustum never reach `touched`: tsdf_assign_kernel.  A test per 256-voxel block was tried first and
-// cost what it saved: the block-uniform fp64 test is as many vector instructions as the per-voxel projection it replaces.)
-// what one frame says about one voxel (world position p): false = the voxel is not updated; otherwise the truncated sdf and the
-// pixel it was read at.  Shared by the frame-at-a-time and the frame-batched kernels: the same instructions, the same bits.
-__device__ __forceinline__ bool tsdf_observe(double px, double py, double pz, const TsdfCam& cam, const float* __restrict__ depth, int H, int W,
-                                             double sdf_trunc, float& tsdf, int64_t& pix) {
-    // (fused multiply-adds and ONE division: this function is all the frame-batched kernel does per voxel and frame -- 15 ms per 64
-    // frames were fp64 multiplies, adds and two divisions issued one by one, the build has -ffp-contract=off)
-    const double cz_ = fma(cam.e[8], px, fma(cam.e[9], py, fma(cam.e[10], pz, cam.e[11])));
-    if (!(cz_ > 0.0)) return false;
-    const double cx_ = fma(cam.e[0], px, fma(cam.e[1], py, fma(cam.e[2], pz, cam.e[3])));
-    const double cy_ = fma(cam.e[4], px, fma(cam.e[5], py, fma(cam.e[6], pz, cam.e[7])));
-    // 1 / cz: v_rcp_f64 and two Newton steps (five instructions, <= 1 ulp) instead of the fifteen-instruction IEEE division
-    double iz = __builtin_amdgcn_rcp(cz_);
-    iz = fma(iz, fma(-cz_, iz, 1.0), iz);
-    iz = fma(iz, fma(-cz_, iz, 1.0), iz);
-    const double u_f = fma(cx_ * cam.fx, iz, cam.cx + 0.5), v_f = fma(cy_ * cam.fy, iz, cam.cy + 0.5);
-    if (!(u_f >= 0.0001 && u_f < (double)W - 0.0001 && v_f >= 0.0001 && v_f < (double)H - 0.0001)) return false;
-    const int ui = (int)u_f, vi = (int)v_f;
-    pix = (int64_t)vi * W + ui;
-    const float d = depth[pix];
-    if (!(d > 0.0f)) return false;
-    // depth-to-camera-distance multiplier of the pixel (Open3D keeps it as a float image)
-    const float xx = (float)(((double)ui - cam.cx) * cam.ifx), yy = (float)(((double)vi - cam.cy) * cam.ify);
-    const float mult = sqrtf(xx * xx + yy * yy + 1.0f);
-    const float sdf = (float)(((double)d - cz_) * (double)mult);
-    if (!(sdf > -(float)sdf_trunc)) return false;
-    tsdf = fminf(1.0f, sdf * (float)(1.0 / sdf_trunc));
-    return true;
-}
-// the running weighted mean of a voxel (tsdf, weight, r, g, b) takes one observation
-__device__ __forceinline__ void tsdf_blend(float vox[5], float tsdf, const uint8_t* __restrict__ c) {
-    // (one division, by the weight -- a small integer -- and four multiplies: the four IEEE divisions were a third of the per-voxel work)
-    const float w0 = vox[1], w1 = w0 + 1.0f, rw = 1.0f / w1;
-    vox[0] = fmaf(vox[0], w0, tsdf) * rw;
-    if (c) {
-        vox[2] = fmaf(vox[2], w0, (float)c[0]) * rw;
-        vox[3] = fmaf(vox[3], w0, (float)c[1]) * rw;
-        vox[4] = fmaf(vox[4], w0, (float)c[2]) * rw;
-    }
-    vox[1] = w1;
-}
-
-__device__ __forceinline__ void tsdf_integrate_block(int work, const float* __restrict__ depth, const uint8_t* __restrict__ color, int H, int W,
-                                                     const TsdfCam& cam, const int32_t* __restrict__ unit_index, const int32_t* __restrict__ touched,
-                                                     int blocks_per_unit, const int64_t* __restrict__ slab_base, int slab_units, int res,
-                                                     double voxel_length, double sdf_trunc, int cull) {
-    const int ti = work / blocks_per_unit, bx = work - ti * blocks_per_unit;
-    const int u = touched[ti];
-    const int v = bx * 256 + threadIdx.x;
-    const int nvox = res * res * res;
-    const double unit_len = voxel_length * res, half = voxel_length * 0.5;
-    if (v >= nvox) return;
-    const int x = v / (res * res), y = (v / res) % res, z = v % res;
-    const double px = half + voxel_length * x + unit_len * unit_index[3 * u + 0];
-    const double py = half + voxel_length * y + unit_len * unit_index[3 * u + 1];
-    const double pz = half + voxel_length * z + unit_len * unit_index[3 * u + 2];
-    float tsdf;
-    int64_t pix;
-    if (!tsdf_observe(px, py, pz, cam, depth, H, W, sdf_trunc, tsdf, pix)) return;
-    float* vox = ts_block(slab_base, slab_units, (int64_t)nvox * 20, u) + (int64_t)v * 5;
-    float s[5] = {vox[0], vox[1], 0.0f, 0.0f, 0.0f};
-    if (color) {
-        s[2] = vox[2]; s[3] = vox[3]; s[4] = vox[4];
-    }
-    tsdf_blend(s, tsdf, color ? color + pix * 3 : nullptr);
-    vox[0] = s[0];
-    vox[1] = s[1];
-    if (color) {
-        vox[2] = s[2]; vox[3] = s[3]; vox[4] = s[4];
-    }
-}
-
-// a fixed grid walks the (touched unit, 256-voxel block) work items; their number comes from device memory
-__global__ __launch_bounds__(256) void tsdf_integrate_kernel(const float* __restrict__ depth, const uint8_t* __restrict__ color, int H, int W,
-                                                              TsdfCam cam, const int32_t* __restrict__ unit_index, const int32_t* __restrict__ touched,
-                                                              const int32_t* __restrict__ n_touched_dev, int blocks_per_unit,
-                                                              const int64_t* __restrict__ slab_base, int slab_units, int res, double voxel_length,
-                                                              double sdf_trunc, int cull) {
-    const long long total = (long long)(*n_touched_dev) * blocks_per_unit;
-    for (long long w = blockIdx.x; w < total; w += gridDim.x)
-        tsdf_integrate_block((int)w, depth, color, H, W, cam, unit_index, touched, blocks_per_unit, slab_base, slab_units, res, voxel_length, sdf_trunc, cull);
-}
-
-// ---- a batch of frames at once ----------------------------------------------------------------------------------------------------
-// A voxel's running mean takes the frames in order, but nothing else orders them: a batch of up to 64 frames is integrated by loading
-// every touched voxel ONCE, applying the frames that touch its unit in ascending order in registers, and storing it once -- the
-// same values bit for bit as 64 frame-at-a-time passes (each of which reads and writes the voxel through HBM), in three launches
-// instead of 192.  Which frames touch a unit is a 64-bit mask: the discovery kernel ORs the frame's bit into the unit's table entry,
-// the assignment kernel hands out blocks, applies the per-frame frustum test and leaves the surviving bits in unit_mask[block].
+// ---- ScalableTSDFVolume::Integrate for a batch of records ------------------------------------------------------------------------------
+// A voxel's running mean takes the frames in order, but nothing else orders them: a batch of up to 64 records is applied by loading
+// every touched voxel ONCE, applying the records that touch its unit in ascending order in registers, and storing it once -- the
+// same values bit for bit as 64 passes of one record each (each of which reads and writes the voxel through HBM), in three launches
+// instead of 192.  A single frame is a batch of one.  Which records touch a unit is a 64-bit mask: the discovery kernel ORs the
+// record's bit into the unit's table entry, the assignment kernel hands out blocks, applies the per-record frustum test and leaves the
+// surviving bits in unit_mask[block].
 struct TsdfFrame {            // one record per frame in device memory (bs_tsdf_frames_upload): BS_TSDF_FRAME_BYTES
     const float* depth;
     const uint8_t* color;
     double fx, fy, cx, cy;
     double pose[12];          // camera -> world, rows 0..2 (unit discovery back-projects with it)
     double view[12];          // world -> camera, rows 0..2: the `extrinsic` of ScalableTSDFVolume::Integrate
-    double ifx, ify;          // 1 / fx, 1 / fy
+    double ifx, ify;          // 1 / fx, 1 / fy (host-computed: the per-voxel code multiplies instead of dividing)
 };
 static_assert(sizeof(TsdfFrame) == BS_TSDF_FRAME_BYTES, "TsdfFrame layout is part of the C ABI");
 
+// first half: every unit that meets the +-sdf_trunc box of a point of the strided depth sample is looked up / inserted and marked
+// with its record's bit.  Thread = (sampled pixel, candidate offset inside the (span)^3 box), blockIdx.y = record.
 __global__ __launch_bounds__(256) void tsdf_touch_batch_kernel(const TsdfFrame* __restrict__ frames, int H, int W, int stride, double unit_length,
                                                                 double sdf_trunc, int span, long long* keys, unsigned long long* fmask, unsigned mask,
                                                                 int32_t* counters) {
@@ -272,6 +98,13 @@ __global__ __launch_bounds__(256) void tsdf_touch_batch_kernel(const TsdfFrame* 
     counters[2] = 1;      // table full
 }
 
+// second half: entries marked by this pass get a block number if they have none, and go on the pass's list with the records that
+// reach them.  Units are opened in a +-sdf_trunc box around every sampled point, far wider than the frustum at endoscopic range
+// (round 2, PMC: 90 % of the integrate kernel's threads projected outside the image and left): a unit whose bounding sphere is behind
+// a record's camera or projects wholly outside its image holds no voxel that record would update, so it is opened (as in Open3D) but
+// the record's bit is dropped; a unit no record reaches stays off the list.  Conservative bound, see below.
+// (A test per 256-voxel block in the integration was tried first and cost what it saved: the block-uniform fp64 test is as many vector
+// instructions as the per-voxel projection it replaces.)
 __global__ __launch_bounds__(256) void tsdf_assign_batch_kernel(const TsdfFrame* __restrict__ frames, const long long* __restrict__ keys, int32_t* slots,
                                                                  unsigned long long* fmask, unsigned cap, int32_t* unit_index, int max_units,
                                                                  int32_t* counters, int32_t* touched, unsigned long long* unit_mask, double unit_length,
@@ -285,10 +118,13 @@ __global__ __launch_bounds__(256) void tsdf_assign_batch_kernel(const TsdfFrame*
     int s = slots[h];
     if (s < 0) {
         s = atomicAdd(counters + 0, 1);
-        if (s >= max_units) {          // (the caller reserves what the discovery found before this kernel runs: only a full map gets here)
+        if (s >= max_units) {
+            // more units than blocks (max_units = the blocks that EXIST; a caller that read the discovery's count back has made them,
+            // one that streams keeps slabs allocated ahead of the map).  The count is put back, so the table entry stays without a
+            // block and a later pass -- after the caller has added slabs or raised the error -- can still assign one.
             atomicSub(counters + 0, 1);
             counters[2] = 2;
-            fmask[h] = 0ull;           // the table's frame masks are zero between batches: a stale bit would name another frame next time
+            fmask[h] = 0ull;           // the table's masks are zero between passes: a stale bit would name another record next time
             return;
         }
         slots[h] = s;
@@ -300,15 +136,17 @@ __global__ __launch_bounds__(256) void tsdf_assign_batch_kernel(const TsdfFrame*
     unsigned long long keep = m;
     if (cull) {
         const double c[3] = {((double)ix + 0.5) * unit_length, ((double)iy + 0.5) * unit_length, ((double)iz + 0.5) * unit_length};
-        const double r = 0.8660254037844387 * unit_length;
-        for (unsigned long long rest = m; rest; rest &= rest - 1) {          // the per-frame frustum test of tsdf_assign_kernel
+        const double r = 0.8660254037844387 * unit_length;           // half the cube's diagonal
+        for (unsigned long long rest = m; rest; rest &= rest - 1) {
             const int f = __builtin_ctzll(rest);
             const TsdfFrame& F = frames[f];
             const double qx = F.view[0] * c[0] + F.view[1] * c[1] + F.view[2] * c[2] + F.view[3];
             const double qy = F.view[4] * c[0] + F.view[5] * c[1] + F.view[6] * c[2] + F.view[7];
             const double qz = F.view[8] * c[0] + F.view[9] * c[1] + F.view[10] * c[2] + F.view[11];
-            bool out = qz + r <= 0.0;
-            if (!out && qz > r) {
+            bool out = qz + r <= 0.0;                                // wholly behind the camera
+            if (!out && qz > r) {                                    // (a sphere that reaches the camera plane is never culled)
+                // a point p = q + d, |d| <= r, projects within  f r / (qz - r) * (1 + |qx| / qz)  pixels of q's projection:
+                // |px / pz - qx / qz| = |dx qz - qx dz| / (pz qz) <= r (qz + |qx|) / ((qz - r) qz)
                 const double inv = 1.0 / (qz - r);
                 const double ru = F.fx * r * inv * (1.0 + fabs(qx) / qz) + 1.0, rv = F.fy * r * inv * (1.0 + fabs(qy) / qz) + 1.0;
                 const double uc = qx * F.fx / qz + F.cx + 0.5, vc = qy * F.fy / qz + F.cy + 0.5;
@@ -322,60 +160,46 @@ __global__ __launch_bounds__(256) void tsdf_assign_batch_kernel(const TsdfFrame*
     touched[atomicAdd(counters + 1, 1)] = s;
 }
 
-__global__ __launch_bounds__(256) void tsdf_integrate_batch_kernel(const TsdfFrame* __restrict__ frames, int H, int W, const int32_t* __restrict__ unit_index,
-                                                                    const int32_t* __restrict__ touched, const int32_t* __restrict__ n_touched_dev,
-                                                                    const unsigned long long* __restrict__ unit_mask, int blocks_per_unit,
-                                                                    const int64_t* __restrict__ slab_base, int slab_units, int res, double voxel_length,
-                                                                    double sdf_trunc) {
-    const long long total = (long long)(*n_touched_dev) * blocks_per_unit;
-    const int nvox = res * res * res;
-    const double unit_len = voxel_length * res, half = voxel_length * 0.5;
-    for (long long w = blockIdx.x; w < total; w += gridDim.x) {
-        const int ti = (int)(w / blocks_per_unit), bx = (int)(w - (long long)ti * blocks_per_unit);
-        const int u = touched[ti];
-        const int v = bx * 256 + threadIdx.x;
-        if (v >= nvox) continue;
-        const unsigned long long m = unit_mask[u];
-        // the frame loop is uniform over the block: the mask goes to scalar registers, a frame's record is read with scalar loads
-        unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)m), hi = __builtin_amdgcn_readfirstlane((unsigned)(m >> 32));
-        const int x = v / (res * res), y = (v / res) % res, z = v % res;
-        const double px = half + voxel_length * x + unit_len * unit_index[3 * u + 0];
-        const double py = half + voxel_length * y + unit_len * unit_index[3 * u + 1];
-        const double pz = half + voxel_length * z + unit_len * unit_index[3 * u + 2];
-        float* vox = ts_block(slab_base, slab_units, (int64_t)nvox * 20, u) + (int64_t)v * 5;
-        float s[5];
-        bool have = false;
-        for (int half_ = 0; half_ < 2; ++half_) {
-            unsigned bits = half_ ? hi : lo;
-            while (bits) {
-                const int f = __builtin_ctz(bits) + 32 * half_;
-                bits &= bits - 1;
-                const TsdfFrame& F = frames[f];
-                TsdfCam cam;
-                cam.fx = F.fx; cam.fy = F.fy; cam.cx = F.cx; cam.cy = F.cy; cam.ifx = F.ifx; cam.ify = F.ify;
-#pragma unroll
-                for (int i = 0; i < 12; ++i) cam.e[i] = F.view[i];
-                float tsdf;
-                int64_t pix;
-                if (!tsdf_observe(px, py, pz, cam, F.depth, H, W, sdf_trunc, tsdf, pix)) continue;
-                if (!have) {
-                    s[0] = vox[0]; s[1] = vox[1];
-                    if (F.color) {
-                        s[2] = vox[2]; s[3] = vox[3]; s[4] = vox[4];
-                    }
-                    have = true;
-                }
-                tsdf_blend(s, tsdf, F.color ? F.color + pix * 3 : nullptr);
-            }
-        }
-        if (have) {
-            vox[0] = s[0];
-            vox[1] = s[1];
-            if (frames[0].color) {
-                vox[2] = s[2]; vox[3] = s[3]; vox[4] = s[4];
-            }
-        }
+// Open3D UniformTSDFVolume::IntegrateWithDepthToCameraDistanceMultiplier: what one frame says about one voxel (world position p):
+// false = the voxel is not updated; otherwise the truncated sdf and the pixel it was read at.  An addition and the removal that undoes
+// it go through these instructions alike: the same decision, the same bits.
+__device__ __forceinline__ bool tsdf_observe(double px, double py, double pz, const TsdfFrame& F, int H, int W, double sdf_trunc, float& tsdf,
+                                             int64_t& pix) {
+    // (fused multiply-adds and ONE division: this function is all the batch kernel does per voxel and frame -- 15 ms per 64
+    // frames were fp64 multiplies, adds and two divisions issued one by one, the build has -ffp-contract=off)
+    const double cz_ = fma(F.view[8], px, fma(F.view[9], py, fma(F.view[10], pz, F.view[11])));
+    if (!(cz_ > 0.0)) return false;
+    const double cx_ = fma(F.view[0], px, fma(F.view[1], py, fma(F.view[2], pz, F.view[3])));
+    const double cy_ = fma(F.view[4], px, fma(F.view[5], py, fma(F.view[6], pz, F.view[7])));
+    // 1 / cz: v_rcp_f64 and two Newton steps (five instructions, <= 1 ulp) instead of the fifteen-instruction IEEE division
+    double iz = __builtin_amdgcn_rcp(cz_);
+    iz = fma(iz, fma(-cz_, iz, 1.0), iz);
+    iz = fma(iz, fma(-cz_, iz, 1.0), iz);
+    const double u_f = fma(cx_ * F.fx, iz, F.cx + 0.5), v_f = fma(cy_ * F.fy, iz, F.cy + 0.5);
+    if (!(u_f >= 0.0001 && u_f < (double)W - 0.0001 && v_f >= 0.0001 && v_f < (double)H - 0.0001)) return false;
+    const int ui = (int)u_f, vi = (int)v_f;
+    pix = (int64_t)vi * W + ui;
+    const float d = F.depth[pix];
+    if (!(d > 0.0f)) return false;
+    // depth-to-camera-distance multiplier of the pixel (Open3D keeps it as a float image)
+    const float xx = (float)(((double)ui - F.cx) * F.ifx), yy = (float)(((double)vi - F.cy) * F.ify);
+    const float mult = sqrtf(xx * xx + yy * yy + 1.0f);
+    const float sdf = (float)(((double)d - cz_) * (double)mult);
+    if (!(sdf > -(float)sdf_trunc)) return false;
+    tsdf = fminf(1.0f, sdf * (float)(1.0 / sdf_trunc));
+    return true;
+}
+// the running weighted mean of a voxel (tsdf, weight, r, g, b) takes one observation
+__device__ __forceinline__ void tsdf_blend(float vox[5], float tsdf, const uint8_t* __restrict__ c) {
+    // (one division, by the weight -- a small integer -- and four multiplies: the four IEEE divisions were a third of the per-voxel work)
+    const float w0 = vox[1], w1 = w0 + 1.0f, rw = 1.0f / w1;
+    vox[0] = fmaf(vox[0], w0, tsdf) * rw;
+    if (c) {
+        vox[2] = fmaf(vox[2], w0, (float)c[0]) * rw;
+        vox[3] = fmaf(vox[3], w0, (float)c[1]) * rw;
+        vox[4] = fmaf(vox[4], w0, (float)c[2]) * rw;
     }
+    vox[1] = w1;
 }
 
 // ---- frames taken out again: map correction after a pose-graph update ----------------------------------------------
@@ -403,24 +227,28 @@ __device__ __forceinline__ bool tsdf_unblend(float vox[5], float tsdf, const uin
     return true;
 }
 
-// tsdf_integrate_batch_kernel with a sign per record: bit f of remove_mask (a kernel argument: scalar registers) set = record f is
-// taken out, clear = it is added.  Records are applied in ascending order in registers, the voxel is loaded once and stored once, the
-// frame loop is uniform over the block.  A removal that finds weight < 1 is skipped and reported through *flag (counters[2] = 3).
-__global__ __launch_bounds__(256) void tsdf_update_batch_kernel(const TsdfFrame* __restrict__ frames, int H, int W, const int32_t* __restrict__ unit_index,
-                                                                 const int32_t* __restrict__ touched, const int32_t* __restrict__ n_touched_dev,
-                                                                 const unsigned long long* __restrict__ unit_mask, int blocks_per_unit,
-                                                                 const int64_t* __restrict__ slab_base, int slab_units, int res, double voxel_length,
-                                                                 double sdf_trunc, unsigned long long remove_mask, int32_t* __restrict__ flag) {
+// the integration itself, one thread per voxel.  A fixed grid walks the (touched unit, 256-voxel block) work items; their number is read from
+// device memory (counters[1], written by tsdf_assign_batch_kernel), so the host never has to wait for it.  Records are applied in
+// ascending order in registers, the voxel is loaded once and stored once, the frame loop is uniform over the block.
+// SIGNED = false: every record is added, remove_mask and flag are not looked at.  SIGNED = true: bit f of remove_mask (a kernel
+// argument: scalar registers) set = record f is taken out, clear = it is added; a removal that finds weight < 1 is skipped and
+// reported through *flag (counters[2] = 3).
+template <bool SIGNED>
+__global__ __launch_bounds__(256) void tsdf_apply_batch_kernel(const TsdfFrame* __restrict__ frames, int H, int W, const int32_t* __restrict__ unit_index,
+                                                                const int32_t* __restrict__ touched, const int32_t* __restrict__ n_touched_dev,
+                                                                const unsigned long long* __restrict__ unit_mask, int blocks_per_unit,
+                                                                const int64_t* __restrict__ slab_base, int slab_units, int res, double voxel_length,
+                                                                double sdf_trunc, unsigned long long remove_mask, int32_t* __restrict__ flag) {
     const long long total = (long long)(*n_touched_dev) * blocks_per_unit;
     const int nvox = res * res * res;
     const double unit_len = voxel_length * res, half = voxel_length * 0.5;
-    const bool with_color = frames[0].color != nullptr;
     for (long long w = blockIdx.x; w < total; w += gridDim.x) {
         const int ti = (int)(w / blocks_per_unit), bx = (int)(w - (long long)ti * blocks_per_unit);
         const int u = touched[ti];
         const int v = bx * 256 + threadIdx.x;
         if (v >= nvox) continue;
         const unsigned long long m = unit_mask[u];
+        // the frame loop is uniform over the block: the mask goes to scalar registers, a frame's record is read with scalar loads
         unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)m), hi = __builtin_amdgcn_readfirstlane((unsigned)(m >> 32));
         const int x = v / (res * res), y = (v / res) % res, z = v % res;
         const double px = half + voxel_length * x + unit_len * unit_index[3 * u + 0];
@@ -434,25 +262,20 @@ __global__ __launch_bounds__(256) void tsdf_update_batch_kernel(const TsdfFrame*
             while (bits) {
                 const int f = __builtin_ctz(bits) + 32 * half_;
                 bits &= bits - 1;
-                const bool remove = (remove_mask >> f) & 1ull;
                 const TsdfFrame& F = frames[f];
-                TsdfCam cam;
-                cam.fx = F.fx; cam.fy = F.fy; cam.cx = F.cx; cam.cy = F.cy; cam.ifx = F.ifx; cam.ify = F.ify;
-#pragma unroll
-                for (int i = 0; i < 12; ++i) cam.e[i] = F.view[i];
                 float tsdf;
                 int64_t pix;
-                if (!tsdf_observe(px, py, pz, cam, F.depth, H, W, sdf_trunc, tsdf, pix)) continue;
+                if (!tsdf_observe(px, py, pz, F, H, W, sdf_trunc, tsdf, pix)) continue;
                 if (!have) {
                     s[0] = vox[0]; s[1] = vox[1];
-                    s[2] = s[3] = s[4] = 0.0f;
-                    if (with_color) {
+                    if (SIGNED) s[2] = s[3] = s[4] = 0.0f;
+                    if (F.color) {
                         s[2] = vox[2]; s[3] = vox[3]; s[4] = vox[4];
                     }
                     have = true;
                 }
                 const uint8_t* c = F.color ? F.color + pix * 3 : nullptr;
-                if (!remove) {
+                if (!SIGNED || !((remove_mask >> f) & 1ull)) {
                     tsdf_blend(s, tsdf, c);
                 } else if (!tsdf_unblend(s, tsdf, c)) {
                     *flag = 3;        // a frame was removed that the voxel never held
@@ -464,7 +287,7 @@ __global__ __launch_bounds__(256) void tsdf_update_batch_kernel(const TsdfFrame*
         if (have) {
             vox[0] = s[0];
             vox[1] = s[1];
-            if (with_color || wiped) {
+            if (frames[0].color || wiped) {
                 vox[2] = s[2]; vox[3] = s[3]; vox[4] = s[4];
             }
         }
@@ -892,74 +715,6 @@ static bool det_ok(const double* m) {
     return det > 1e-12 || det < -1e-12;
 }
 
-static void tsdf_cam(TsdfCam& cam, const double* K, const double* m12) {
-    cam.fx = K[0]; cam.fy = K[1]; cam.cx = K[2]; cam.cy = K[3];
-    cam.ifx = 1.0 / K[0]; cam.ify = 1.0 / K[1];
-    for (int i = 0; i < 12; ++i) cam.e[i] = m12[i];
-}
-
-extern "C" int bs_tsdf_touch(const float* depth, int32_t H, int32_t W, int32_t stride, const double* K, const double* pose, double unit_length,
-                             double sdf_trunc, void* table_keys, int32_t* table_slots, int32_t* table_stamp, int32_t table_cap, int32_t frame_id,
-                             int32_t* unit_index, int32_t max_units, int32_t* counters, int32_t* touched, void* stream) {
-    if (!initialized()) { set_error("bs_tsdf_touch: call bs_init first"); return BS_ERR_NOT_INIT; }
-    BS_REQUIRE(depth && K && pose && table_keys && table_slots && table_stamp && unit_index && counters && touched, "bs_tsdf_touch: null argument");
-    BS_REQUIRE(H > 0 && W > 0 && stride > 0 && unit_length > 0.0 && sdf_trunc > 0.0 && max_units > 0, "bs_tsdf_touch: bad geometry");
-    BS_REQUIRE(table_cap >= 256 && (table_cap & (table_cap - 1)) == 0, "bs_tsdf_touch: table_cap=%d must be a power of two >= 256", table_cap);
-    TsdfCam cam;
-    tsdf_cam(cam, K, pose);
-    const int span = (int)floor(2.0 * sdf_trunc / unit_length) + 2;          // hi - lo + 1 never exceeds this
-    BS_REQUIRE(span <= 64, "bs_tsdf_touch: sdf_trunc / unit_length too large");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    BS_CHECK_HIP(hipMemsetAsync(counters + 1, 0, sizeof(int32_t), st));    // n_touched (n_units persists; the overflow flag is sticky: the caller clears it)
-    const int64_t threads = (int64_t)cdiv(W, stride) * cdiv(H, stride) * span * span * span;
-    hipLaunchKernelGGL(tsdf_touch_kernel, dim3((unsigned)cdiv64(threads, 256)), dim3(256), 0, st, depth, H, W, stride, cam, unit_length, sdf_trunc, span,
-                       reinterpret_cast<long long*>(table_keys), table_stamp, (unsigned)(table_cap - 1), frame_id, counters);
-    BS_CHECK_LAUNCH();
-    // world -> camera for the frustum test of the units: the inverse of the 3x4 `pose` (general affine inverse)
-    TsdfCam view = cam;
-    {
-        const double* m = pose;
-        const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g = m[8], h = m[9], i = m[10];
-        const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
-        const double id = 1.0 / det;
-        const double inv[9] = {(e * i - f * h) * id, (c * h - b * i) * id, (b * f - c * e) * id, (f * g - d * i) * id, (a * i - c * g) * id,
-                               (c * d - a * f) * id, (d * h - e * g) * id, (b * g - a * h) * id, (a * e - b * d) * id};
-        for (int r = 0; r < 3; ++r) {
-            for (int q = 0; q < 3; ++q) view.e[4 * r + q] = inv[3 * r + q];
-            view.e[4 * r + 3] = -(inv[3 * r] * m[3] + inv[3 * r + 1] * m[7] + inv[3 * r + 2] * m[11]);
-        }
-    }
-    const int cull = diag_env("BS_TSDF_NO_CULL") == nullptr && det_ok(pose);
-    hipLaunchKernelGGL(tsdf_assign_kernel, dim3(cdiv(table_cap, 256)), dim3(256), 0, st, reinterpret_cast<const long long*>(table_keys), table_slots,
-                       table_stamp, (unsigned)table_cap, frame_id, unit_index, max_units, counters, touched, view, unit_length, W, H, cull);
-    BS_CHECK_LAUNCH();
-    return BS_OK;
-}
-
-extern "C" int bs_tsdf_integrate(const float* depth, const uint8_t* color, int32_t H, int32_t W, const double* K, const double* extrinsic,
-                                 const int32_t* unit_index, const int32_t* touched, int32_t n_touched, const int64_t* slab_base, int32_t slab_units,
-                                 int32_t res, double voxel_length, double sdf_trunc, const int32_t* n_touched_dev, void* stream) {
-    if (!initialized()) { set_error("bs_tsdf_integrate: call bs_init first"); return BS_ERR_NOT_INIT; }
-    BS_REQUIRE(n_touched >= 0 && H > 0 && W > 0 && res > 0 && res <= 64 && slab_units > 0 && voxel_length > 0.0 && sdf_trunc > 0.0,
-               "bs_tsdf_integrate: bad geometry");
-    if (n_touched == 0) return BS_OK;
-    BS_REQUIRE(depth && K && extrinsic && unit_index && touched && slab_base && n_touched_dev, "bs_tsdf_integrate: null argument");
-    TsdfCam cam;
-    tsdf_cam(cam, K, extrinsic);
-    const int nvox = res * res * res, bpu = cdiv(nvox, 256);
-    BS_REQUIRE((long long)bpu * n_touched < 0x7fffffffll, "bs_tsdf_integrate: too many units for one launch");
-    // n_touched (host) only sizes the grid; the kernel reads the true count from n_touched_dev, so a caller that has not read it back
-    // passes any generous value (a few blocks per CU walk the work items)
-    const long long want = (long long)bpu * n_touched;
-    const unsigned grid = (unsigned)(want < 16ll * cu_count() ? want : 16ll * cu_count());
-    const int cull = 0;
-    hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), depth, color, H, W,
-                       cam, unit_index, touched, n_touched_dev, bpu, slab_base, slab_units, res, voxel_length, sdf_trunc, cull);
-    BS_CHECK_LAUNCH();
-    return BS_OK;
-}
-
-// ---- the frame-batched path ---------------------------------------------------------------------------------------------------------
 static bool affine_inverse(const double* m, double* out12) {      // rows 0..2 of the inverse of the affine 4x4 whose rows 0..2 are m
     const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g = m[8], h = m[9], i = m[10];
     const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
@@ -1038,63 +793,53 @@ extern "C" int bs_tsdf_touch_batch(const void* frames_dev, int32_t n_frames, int
     return BS_OK;
 }
 
-extern "C" int bs_tsdf_integrate_batch(const void* frames_dev, int32_t n_frames, int32_t H, int32_t W, const void* table_keys, int32_t* table_slots,
-                                       void* table_fmask, int32_t table_cap, int32_t* unit_index, int32_t max_units, int32_t* counters, int32_t* touched,
-                                       void* unit_mask, const int64_t* slab_base, int32_t slab_units, int32_t res, double voxel_length, double sdf_trunc,
-                                       void* stream) {
-    if (!initialized()) { set_error("bs_tsdf_integrate_batch: call bs_init first"); return BS_ERR_NOT_INIT; }
+// what bs_tsdf_integrate_batch and bs_tsdf_update_batch share: the checks, the block assignment with its frustum test, the pass over
+// the touched voxels.  is_signed picks the kernel that reads remove_mask.
+static int tsdf_apply_batch(const char* who, bool is_signed, const void* frames_dev, int32_t n_frames, int32_t H, int32_t W, const void* table_keys,
+                            int32_t* table_slots, void* table_fmask, int32_t table_cap, int32_t* unit_index, int32_t max_units, int32_t* counters,
+                            int32_t* touched, void* unit_mask, const int64_t* slab_base, int32_t slab_units, int32_t res, double voxel_length,
+                            double sdf_trunc, uint64_t remove_mask, void* stream) {
+    if (!initialized()) { set_error("%s: call bs_init first", who); return BS_ERR_NOT_INIT; }
     BS_REQUIRE(frames_dev && table_keys && table_slots && table_fmask && unit_index && counters && touched && unit_mask && slab_base,
-               "bs_tsdf_integrate_batch: null argument");
+               "%s: null argument", who);
     BS_REQUIRE(n_frames > 0 && n_frames <= BS_TSDF_BATCH_MAX && H > 0 && W > 0 && res > 0 && res <= 64 && slab_units > 0 && voxel_length > 0.0 &&
                    sdf_trunc > 0.0 && max_units > 0,
-               "bs_tsdf_integrate_batch: bad geometry");
-    BS_REQUIRE(table_cap >= 256 && (table_cap & (table_cap - 1)) == 0, "bs_tsdf_integrate_batch: table_cap=%d must be a power of two >= 256", table_cap);
+               "%s: bad geometry", who);
+    BS_REQUIRE(table_cap >= 256 && (table_cap & (table_cap - 1)) == 0, "%s: table_cap=%d must be a power of two >= 256", who, table_cap);
+    BS_REQUIRE(n_frames == BS_TSDF_BATCH_MAX || (remove_mask >> n_frames) == 0ull, "%s: remove_mask names a record past n_frames=%d", who, n_frames);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const TsdfFrame* frames = static_cast<const TsdfFrame*>(frames_dev);
-    BS_CHECK_HIP(hipMemsetAsync(counters + 1, 0, sizeof(int32_t), st));
+    BS_CHECK_HIP(hipMemsetAsync(counters + 1, 0, sizeof(int32_t), st));    // the units this call updates (n_units persists; the overflow flag is sticky: the caller clears it)
     const int cull = diag_env("BS_TSDF_NO_CULL") == nullptr;
     hipLaunchKernelGGL(tsdf_assign_batch_kernel, dim3(cdiv(table_cap, 256)), dim3(256), 0, st, frames, reinterpret_cast<const long long*>(table_keys),
                        table_slots, reinterpret_cast<unsigned long long*>(table_fmask), (unsigned)table_cap, unit_index, max_units, counters, touched,
                        reinterpret_cast<unsigned long long*>(unit_mask), voxel_length * res, W, H, cull);
     BS_CHECK_LAUNCH();
+    // max_units only bounds the grid; the kernel reads the true count from counters[1] (a few blocks per CU walk the work items)
     const int nvox = res * res * res, bpu = cdiv(nvox, 256);
     const long long want = (long long)bpu * max_units;
     const unsigned grid = (unsigned)(want < 16ll * cu_count() ? want : 16ll * cu_count());
-    hipLaunchKernelGGL(tsdf_integrate_batch_kernel, dim3(grid), dim3(256), 0, st, frames, H, W, unit_index, touched, counters + 1,
-                       reinterpret_cast<const unsigned long long*>(unit_mask), bpu, slab_base, slab_units, res, voxel_length, sdf_trunc);
+    hipLaunchKernelGGL(is_signed ? tsdf_apply_batch_kernel<true> : tsdf_apply_batch_kernel<false>, dim3(grid), dim3(256), 0, st, frames, H, W, unit_index,
+                       touched, counters + 1, reinterpret_cast<const unsigned long long*>(unit_mask), bpu, slab_base, slab_units, res, voxel_length,
+                       sdf_trunc, (unsigned long long)remove_mask, counters + 2);
     BS_CHECK_LAUNCH();
     return BS_OK;
 }
 
-// bs_tsdf_integrate_batch's launches with tsdf_update_batch_kernel as the third: the same assignment, frustum test and masks
+extern "C" int bs_tsdf_integrate_batch(const void* frames_dev, int32_t n_frames, int32_t H, int32_t W, const void* table_keys, int32_t* table_slots,
+                                       void* table_fmask, int32_t table_cap, int32_t* unit_index, int32_t max_units, int32_t* counters, int32_t* touched,
+                                       void* unit_mask, const int64_t* slab_base, int32_t slab_units, int32_t res, double voxel_length, double sdf_trunc,
+                                       void* stream) {
+    return tsdf_apply_batch("bs_tsdf_integrate_batch", false, frames_dev, n_frames, H, W, table_keys, table_slots, table_fmask, table_cap, unit_index,
+                            max_units, counters, touched, unit_mask, slab_base, slab_units, res, voxel_length, sdf_trunc, 0ull, stream);
+}
+
 extern "C" int bs_tsdf_update_batch(const void* frames_dev, int32_t n_frames, int32_t H, int32_t W, const void* table_keys, int32_t* table_slots,
                                     void* table_fmask, int32_t table_cap, int32_t* unit_index, int32_t max_units, int32_t* counters, int32_t* touched,
                                     void* unit_mask, const int64_t* slab_base, int32_t slab_units, int32_t res, double voxel_length, double sdf_trunc,
                                     uint64_t remove_mask, void* stream) {
-    if (!initialized()) { set_error("bs_tsdf_update_batch: call bs_init first"); return BS_ERR_NOT_INIT; }
-    BS_REQUIRE(frames_dev && table_keys && table_slots && table_fmask && unit_index && counters && touched && unit_mask && slab_base,
-               "bs_tsdf_update_batch: null argument");
-    BS_REQUIRE(n_frames > 0 && n_frames <= BS_TSDF_BATCH_MAX && H > 0 && W > 0 && res > 0 && res <= 64 && slab_units > 0 && voxel_length > 0.0 &&
-                   sdf_trunc > 0.0 && max_units > 0,
-               "bs_tsdf_update_batch: bad geometry");
-    BS_REQUIRE(table_cap >= 256 && (table_cap & (table_cap - 1)) == 0, "bs_tsdf_update_batch: table_cap=%d must be a power of two >= 256", table_cap);
-    BS_REQUIRE(n_frames == BS_TSDF_BATCH_MAX || (remove_mask >> n_frames) == 0ull, "bs_tsdf_update_batch: remove_mask names a record past n_frames=%d", n_frames);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const TsdfFrame* frames = static_cast<const TsdfFrame*>(frames_dev);
-    BS_CHECK_HIP(hipMemsetAsync(counters + 1, 0, sizeof(int32_t), st));
-    const int cull = diag_env("BS_TSDF_NO_CULL") == nullptr;
-    hipLaunchKernelGGL(tsdf_assign_batch_kernel, dim3(cdiv(table_cap, 256)), dim3(256), 0, st, frames, reinterpret_cast<const long long*>(table_keys),
-                       table_slots, reinterpret_cast<unsigned long long*>(table_fmask), (unsigned)table_cap, unit_index, max_units, counters, touched,
-                       reinterpret_cast<unsigned long long*>(unit_mask), voxel_length * res, W, H, cull);
-    BS_CHECK_LAUNCH();
-    const int nvox = res * res * res, bpu = cdiv(nvox, 256);
-    const long long want = (long long)bpu * max_units;
-    const unsigned grid = (unsigned)(want < 16ll * cu_count() ? want : 16ll * cu_count());
-    hipLaunchKernelGGL(tsdf_update_batch_kernel, dim3(grid), dim3(256), 0, st, frames, H, W, unit_index, touched, counters + 1,
-                       reinterpret_cast<const unsigned long long*>(unit_mask), bpu, slab_base, slab_units, res, voxel_length, sdf_trunc,
-                       (unsigned long long)remove_mask, counters + 2);
-    BS_CHECK_LAUNCH();
-    return BS_OK;
+    return tsdf_apply_batch("bs_tsdf_update_batch", true, frames_dev, n_frames, H, W, table_keys, table_slots, table_fmask, table_cap, unit_index,
+                            max_units, counters, touched, unit_mask, slab_base, slab_units, res, voxel_length, sdf_trunc, remove_mask, stream);
 }
 
 extern "C" int bs_tsdf_extract(const int32_t* unit_index, int32_t units, const void* table_keys, const int32_t* table_slots, int32_t table_cap,

@@ -282,8 +282,8 @@ class BodySlamPipeline:
 
         and nothing of it waits for the GPU per frame: the odometry of a batch is tracked on the device and read back once
         (``RGBDOdometry.track``), the UKF / chain / pose graph are host arithmetic on a few numbers (as in the reference), the map
-        steps are enqueued without a round trip (``TSDF.build_3D_map(sync=False)``; block capacity is reserved a batch ahead and
-        checked at the batch end).  ``tsdf_factory()`` makes the fresh TSDF of a rebuild (default: a copy of ``tsdf``'s parameters).
+        steps of a batch are one pass over the map (``TSDF.build_3D_map_batch``: one round trip that makes exactly the blocks its
+        frames need; the unit counts and the overflow flag are checked at the batch end).  ``tsdf_factory()`` makes the fresh TSDF of a rebuild (default: a copy of ``tsdf``'s parameters).
         With ``self.map_correction = "incremental"`` (or "auto") the map is not rebuilt after a pose-graph step that moved poses but
         corrected in place: the moved frames are taken out and put back with their new poses (``TSDF.apply_batch``), the volume passed
         in stays the loop's map; the rebuild at ``rebuild_every`` stays a rebuild.

@@ -5,9 +5,10 @@ depth_sampling_stride=8)``: ``build_3D_map(rgbd, intrinsic, extrinsic)`` integra
 accumulated pose as ``extrinsic``), ``extract_pcd`` / ``save_pcd`` read the surface points back (:126,191,195).  Same class, method
 names and defaults here.  The voxels live in HBM (one contiguous block of res^3 x 5 fp32 per volume unit, allocated in slabs and
 zero-filled once) and are integrated / extracted by the HIP kernels of csrc/tsdf.hip; which units exist is an open-addressing hash
-table in HBM (Open3D: an unordered_map on the host), filled per frame from the strided depth sample exactly as Open3D does.  With the reference's parameters a
+table in HBM (Open3D: an unordered_map on the host), filled per frame from the strided depth sample exactly as Open3D does.  There is
+one integration path: a pass over the map applies up to 64 frame records, ``build_3D_map`` is that pass on one record.  With the reference's parameters a
 unit is 3.2 cm wide and a point opens the ~7^3 units within 0.1 m of it; a 640x480 frame of a surface at 12 cm touches ~1 600 units
-= 1 GB of voxel state and takes ~1 ms (measured, tools/probes/tsdf_full_size.py: unit discovery 0.1 ms, integrate kernel 0.27 ms),
+= 1 GB of voxel state (tools/probes/tsdf_full_size.py; times in profiles/tsdf_one_path.txt),
 metre-scale scenes proportionally more: the voxel store is sized for 288 GB of HBM.  Open3D is not vendored and not installable offline: parity against it is unpinned (oracle/tsdf_ref.py
 restates the same algorithm in numpy; tests/ compare the two).  ``extract_pcd`` returns points, colours and normals, as Open3D's
 ``extract_point_cloud``; ``extract_mesh`` / ``save_mesh`` (tsdf.py:42-52, called on the last frame at 3DM/slam.py:189-193) run marching
@@ -171,13 +172,19 @@ class TSDF:
         self.slab_base = torch.zeros(self.max_slabs, dtype=torch.int64, device=d)
         self.table_keys = torch.full((self.table_cap,), -1, dtype=torch.int64, device=d)
         self.table_slots = torch.full((self.table_cap,), -1, dtype=torch.int32, device=d)
-        self.table_stamp = torch.full((self.table_cap,), -1, dtype=torch.int32, device=d)
         self.unit_index = torch.zeros(self.max_units, 3, dtype=torch.int32, device=d)
         self.counters = torch.zeros(3, dtype=torch.int32, device=d)
         self.touched = torch.zeros(self.max_units, dtype=torch.int32, device=d)
-        self.n_units, self.frame_id = 0, 0                                # frame_id: discovery passes so far (the stamp of the unit table)
-        self.frames_integrated = 0
+        self._alloc_pass_scratch()
+        self.n_units, self.frames_integrated = 0, 0
         self._max_new_per_frame, self._frames_since_sync = 0, 0
+
+    def _alloc_pass_scratch(self):
+        """what a pass over the map works in and leaves behind clean: the table's record masks (zero between passes), the masks per
+        block and the frame records"""
+        self.table_fmask = torch.zeros(self.table_cap, dtype=torch.int64, device=self.dev)
+        self.unit_mask = torch.zeros(self.max_units, dtype=torch.int64, device=self.dev)
+        self.frames_dev = torch.zeros(BATCH_MAX * 256, dtype=torch.uint8, device=self.dev)          # BS_TSDF_FRAME_BYTES per frame
 
     # ---- block capacity ------------------------------------------------------------------------------
     @property
@@ -203,14 +210,17 @@ class TSDF:
         return self.n_units
 
     def discover(self, rgbd: "RGBDImage", intrinsic: "PinholeCameraIntrinsic", extrinsic) -> None:
-        """unit discovery of a frame WITHOUT integrating it (no round trip): the units it needs enter the table and take blocks as far as
-        blocks exist.  ``reserve_discovered()`` then makes the missing blocks -- two cheap passes over a batch of frames replace a guess
-        at how many units a stream will open."""
-        self._touch_integrate(rgbd, intrinsic, extrinsic, integrate=False)
+        """unit discovery of a frame WITHOUT integrating it (no round trip): the units it needs enter the table, without blocks.
+        ``reserve_discovered()`` then makes the missing blocks -- two cheap passes over a batch of frames replace a guess at how
+        many units a stream will open."""
+        self._discover([rgbd], intrinsic, [extrinsic])
+        self.table_fmask.zero_()              # no pass follows that would clear it: a stale bit would name a frame of the next pass
+        self._frames_since_sync += 1
 
     def reserve_discovered(self, margin: int = 256) -> int:
         """after a run of discover() calls: one round trip for the unit count and the number of table entries still without a block;
-        allocates what is missing (+ margin) and clears the overflow flag those frames may have raised.  Returns the blocks added."""
+        allocates what is missing (+ margin), so that the frames can be streamed (each takes its blocks as it is integrated), and
+        clears the overflow flag.  Returns the blocks added."""
         n_units = int(self.counters[0])
         missing = int(((self.table_keys != -1) & (self.table_slots < 0)).sum())
         before = self.alloc_units
@@ -225,7 +235,7 @@ class TSDF:
         n_units, n_touched, overflow = (int(v) for v in self.counters.cpu())
         if overflow:
             self.counters[2] = 0
-            if overflow == 3:          # tsdf_update_batch_kernel: the removal was skipped there, no weight went below 0
+            if overflow == 3:          # tsdf_apply_batch_kernel<true>: the removal was skipped there, no weight went below 0
                 raise L.BodySlamHipError("TSDF: a frame was removed that the voxel never held (deintegrate / apply_batch need the images and the "
                                          "extrinsic the frame was integrated with)")
             raise L.BodySlamHipError("TSDF: " + ("unit table full" if overflow == 1 else
@@ -238,94 +248,29 @@ class TSDF:
 
     # ---- the reference's surface -----------------------------------------------------------------
     def build_3D_map(self, rgbd: RGBDImage, intrinsic: PinholeCameraIntrinsic, extrinsic, sync: bool = True) -> None:
-        self._touch_integrate(rgbd, intrinsic, extrinsic, sync=sync)
-
-    def _touch_integrate(self, rgbd: RGBDImage, intrinsic: PinholeCameraIntrinsic, extrinsic, sync: bool = False, integrate: bool = True) -> None:
-        """ScalableTSDFVolume.integrate(rgbd, intrinsic, extrinsic).  sync=True (one frame at a time, as the reference calls it): the
-        unit count is read back (12 bytes) and slabs are added on demand.  sync=False: nothing is read back -- the frame is enqueued
-        against the blocks that exist (reserve / reserve_ahead) and ``sync()`` later collects the counts and the overflow flag."""
-        d_dev = (rgbd.depth if isinstance(rgbd.depth, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(rgbd.depth, dtype=np.float32))))
-        d_dev = d_dev.to(device=self.dev, dtype=torch.float32).contiguous()                    # numpy, host or device tensors
-        H, W = d_dev.shape
-        E = np.ascontiguousarray(np.asarray(self._np(extrinsic), dtype=np.float64))
-        K = np.array([intrinsic.fx, intrinsic.fy, intrinsic.cx, intrinsic.cy], dtype=np.float64)
-        pose12 = np.ascontiguousarray(np.linalg.inv(E)[:3].reshape(12))
-        e12 = np.ascontiguousarray(E[:3].reshape(12))
-        c_dev = None
-        if rgbd.color is not None:
-            c_dev = rgbd.color if isinstance(rgbd.color, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(rgbd.color, dtype=np.uint8)))
-            c_dev = c_dev.to(device=self.dev, dtype=torch.uint8).contiguous()
-        lib, st = L.load_library(), L.stream_ptr()
-        if not self.slabs:
-            self.reserve(1)
-
-        def touch():
-            self.frame_id += 1
-            L.check(lib.bs_tsdf_touch(L.p(d_dev), H, W, self.stride, K.ctypes.data_as(C.c_void_p), pose12.ctypes.data_as(C.c_void_p), self.unit_length,
-                                      self.sdf_trunc, L.p(self.table_keys), L.p(self.table_slots), L.p(self.table_stamp), self.table_cap, self.frame_id,
-                                      L.p(self.unit_index), self.alloc_units, L.p(self.counters), L.p(self.touched), st), "bs_tsdf_touch")
-
-        integrate_too = integrate
-
-        def integrate(n_hint):
-            # (K / pose are copied into the kernel arguments at launch: nothing here has to outlive the call)
-            L.check(lib.bs_tsdf_integrate(L.p(d_dev), L.p(c_dev), H, W, K.ctypes.data_as(C.c_void_p), e12.ctypes.data_as(C.c_void_p), L.p(self.unit_index),
-                                          L.p(self.touched), n_hint, L.p(self.slab_base), self.slab_units, self.res, self.voxel_length, self.sdf_trunc,
-                                          L.p(self.counters[1:]), st), "bs_tsdf_integrate")
-
-        self._frames_since_sync += 1
-        self.frames_integrated += int(integrate_too)
-        if not sync:
-            touch()
-            if integrate_too:
-                integrate(self.alloc_units)
-            return
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        ev[0].record()
-        touch()
-        ev[1].record()
-        while True:
-            n_units, n_touched, overflow = (int(v) for v in self.counters.cpu())          # the one host round trip of the step (12 bytes)
-            if overflow == 2 and self.alloc_units < self.max_units:
-                # more new units than blocks existed: add slabs and discover again (a fresh frame id re-stamps this frame's units)
-                self.counters[2] = 0
-                self.reserve(max(2 * self.alloc_units, self.alloc_units + self.slab_units))
-                touch()
-                continue
-            break
-        if overflow:
-            self.counters[2] = 0
-            raise L.BodySlamHipError("TSDF: " + ("unit table full" if overflow == 1 else f"more than max_units={self.max_units} volume units")
-                                     + "; construct TSDF with a larger max_units")
-        self._max_new_per_frame = max(self._max_new_per_frame, n_units - self.n_units)
-        self._frames_since_sync = 0
-        self.n_units, self.last_units = n_units, n_touched
-        ev[2].record()
-        integrate(max(n_touched, 1))
-        ev[3].record()
-        ev[3].synchronize()
-        self.last_touch_ms, self.last_kernel_ms = ev[0].elapsed_time(ev[1]), ev[2].elapsed_time(ev[3])      # diagnostics
+        """ScalableTSDFVolume.integrate(rgbd, intrinsic, extrinsic): a pass of one record.  sync=True (one frame at a time, as the
+        reference calls it): the blocks the frame needs are counted (one round trip) and made first.  sync=False: nothing is read
+        back -- the frame is enqueued against the blocks that exist (reserve / reserve_ahead) and ``sync()`` later collects the counts
+        and the overflow flag."""
+        self._batch_pass([rgbd], intrinsic, [extrinsic], None, sync=sync)
 
     def build_3D_map_batch(self, rgbds: Sequence["RGBDImage"], intrinsic: "PinholeCameraIntrinsic", extrinsics) -> None:
-        """``build_3D_map`` for a run of frames, in order, as ONE pass over the map (csrc/tsdf.hip, "a batch of frames at once"): every
-        voxel the run touches is loaded once, takes its frames in ascending order in registers and is stored once.  The blocks end
-        up bit for bit as the frame-by-frame calls leave them; the cost is three launches and one 12-byte round trip (the block
-        reservation) per 64 frames instead of three launches per frame.  Device images (torch tensors) are used in place."""
+        """``build_3D_map`` for a run of frames, in order, as ONE pass over the map (csrc/tsdf.hip, "Integrate for a batch of records"):
+        every voxel the run touches is loaded once, takes its frames in ascending order in registers and is stored once.  The blocks
+        end up bit for bit as the frame-by-frame calls leave them; the cost is three launches and one round trip (the block
+        reservation) per 64 frames instead of per frame.  Device images (torch tensors) are used in place."""
         n = len(rgbds)
         assert len(extrinsics) == n
         for a in range(0, n, BATCH_MAX):
             self._batch_pass(rgbds[a:a + BATCH_MAX], intrinsic, extrinsics[a:a + BATCH_MAX], None)
 
-    def _batch_pass(self, chunk, intrinsic: "PinholeCameraIntrinsic", extrinsics, remove) -> None:
-        """one pass over the map for at most BATCH_MAX records: discovery, the 12-byte round trip that makes the blocks, the update.
-        remove = None: every record is added (bs_tsdf_integrate_batch); else a bool per record, True = taken out (bs_tsdf_update_batch)"""
+    def _discover(self, chunk, intrinsic: "PinholeCameraIntrinsic", extrinsics):
+        """the records of at most BATCH_MAX frames go to the device and their units into the table: afterwards bit f of table_fmask
+        marks the units record f touches.  Returns (records, H, W, the device images): the records point at the images, so the
+        caller holds on to them until everything that reads the records is enqueued."""
         lib, st = L.load_library(), L.stream_ptr()
         if not self.slabs:
             self.reserve(1)
-        if getattr(self, "table_fmask", None) is None:
-            self.table_fmask = torch.zeros(self.table_cap, dtype=torch.int64, device=self.dev)
-            self.unit_mask = torch.zeros(self.max_units, dtype=torch.int64, device=self.dev)
-            self.frames_dev = torch.zeros(BATCH_MAX * 256, dtype=torch.uint8, device=self.dev)      # BS_TSDF_FRAME_BYTES per frame
         K = np.array([intrinsic.fx, intrinsic.fy, intrinsic.cx, intrinsic.cy], dtype=np.float64)
         m = len(chunk)
         depth = [self._image(r.depth, torch.float32) for r in chunk]
@@ -343,18 +288,34 @@ class TSDF:
                                           L.p(self.frames_dev), st), "bs_tsdf_frames_upload")
         L.check(lib.bs_tsdf_touch_batch(L.p(self.frames_dev), m, H, W, self.stride, self.unit_length, self.sdf_trunc, L.p(self.table_keys),
                                         L.p(self.table_fmask), self.table_cap, L.p(self.counters), st), "bs_tsdf_touch_batch")
-        # the one round trip of the batch: how many blocks the discovered units need
-        # (+ the overflow flag the discovery may have raised: 1 = unit table full)
-        need = torch.stack([self.counters[0].to(torch.int64), ((self.table_keys != -1) & (self.table_slots < 0)).sum(),
-                            self.counters[2].to(torch.int64)]).cpu()
-        if int(need[2]) == 1 or int(need[0]) + int(need[1]) > self.max_units:
-            # nothing of this batch has been integrated yet: clear the flag and the batch's frame bits, then refuse
-            self.counters[2] = 0
-            self.table_fmask.zero_()
-            raise L.BodySlamHipError("TSDF: " + ("unit table full" if int(need[2]) == 1 else
-                                                 f"the batch needs {int(need[0]) + int(need[1])} volume units, more than max_units={self.max_units}")
-                                     + "; construct TSDF with a larger max_units")
-        self.reserve(int(need[0]) + int(need[1]))
+        return m, H, W, (depth, color)
+
+    def _batch_pass(self, chunk, intrinsic: "PinholeCameraIntrinsic", extrinsics, remove, sync: bool = True) -> None:
+        """one pass over the map for at most BATCH_MAX records: discovery, the round trip that makes the blocks (sync=False: none, the
+        blocks that exist have to do and ``sync()`` tells whether they did), the update.
+        remove = None: every record is added (bs_tsdf_integrate_batch); else a bool per record, True = taken out (bs_tsdf_update_batch)"""
+        lib, st = L.load_library(), L.stream_ptr()
+        m, H, W, images = self._discover(chunk, intrinsic, extrinsics)
+        if sync:
+            # the one round trip of the pass: the units that have blocks, the units of this pass that need one
+            # (+ the overflow flag the discovery may have raised: 1 = unit table full)
+            need = torch.stack([self.counters[0].to(torch.int64), ((self.table_fmask != 0) & (self.table_slots < 0)).sum(),
+                                self.counters[2].to(torch.int64)]).cpu()
+            n_units = int(need[0]) + int(need[1])
+            if int(need[2]) == 1 or n_units > self.max_units:
+                # nothing of this pass has been integrated yet: clear the flag and the pass's record bits, then refuse
+                self.counters[2] = 0
+                self.table_fmask.zero_()
+                raise L.BodySlamHipError("TSDF: " + ("unit table full" if int(need[2]) == 1 else
+                                                     f"the batch needs {n_units} volume units, more than max_units={self.max_units}")
+                                         + "; construct TSDF with a larger max_units")
+            self.reserve(n_units)
+            # every unit of the pass has a block once it has run, so the count is known without another round trip -- extract_pcd /
+            # extract_mesh right after it see the whole map
+            self._max_new_per_frame = max(self._max_new_per_frame, -(-(n_units - self.n_units) // m))
+            self.n_units, self._frames_since_sync = n_units, 0
+        else:
+            self._frames_since_sync += m
         args = (L.p(self.frames_dev), m, H, W, L.p(self.table_keys), L.p(self.table_slots), L.p(self.table_fmask), self.table_cap, L.p(self.unit_index),
                 self.alloc_units, L.p(self.counters), L.p(self.touched), L.p(self.unit_mask), L.p(self.slab_base), self.slab_units, self.res,
                 self.voxel_length, self.sdf_trunc)
@@ -366,16 +327,12 @@ class TSDF:
             L.check(lib.bs_tsdf_update_batch(*args, mask, st), "bs_tsdf_update_batch")
             removed = sum(1 for f in range(m) if remove[f])
         self.frames_integrated += m - 2 * removed
-        self._frames_since_sync += m
-        # (the assignment cannot run out of blocks after the reserve above; its flag is still collected by sync())
-        # every discovered unit has a block now (unless the map is full: sync() reports that), so the count is known without
-        # another round trip -- extract_pcd / extract_mesh right after a batch see the whole map
-        self.n_units = min(int(need[0]) + int(need[1]), self.alloc_units)
+        del images                            # (enqueued: the allocator frees in stream order)
 
     def apply_batch(self, rgbds: Sequence["RGBDImage"], intrinsic: "PinholeCameraIntrinsic", extrinsics, remove: Sequence[bool]) -> None:
         """Records with a sign: ``remove[k]`` False integrates record k as ``build_3D_map_batch`` does, True takes it out of the map
         again -- it must carry the images and the extrinsic it was integrated with.  Records are applied in the given order, in chunks
-        of at most BS_TSDF_BATCH_MAX consecutive records; each chunk is one discovery, one 12-byte round trip and one pass that loads
+        of at most BS_TSDF_BATCH_MAX consecutive records; each chunk is one discovery, one round trip and one pass that loads
         every touched voxel once (csrc/tsdf.hip, "frames taken out again"), with ``build_3D_map_batch``'s capacity checks before
         anything of the chunk is applied.  Units are never freed: a unit whose voxels all returned to weight 0 keeps its (all-zero)
         block, which extract_pcd / extract_mesh / raycast ignore.  Removing a frame the map never held is reported by ``sync()``."""
@@ -397,8 +354,9 @@ class TSDF:
 
     def build_copy_3D_map(self, rgbd, intrinsic, extrinsic) -> "TSDF":
         other = copy.copy(self)
-        for name in ("table_keys", "table_slots", "table_stamp", "unit_index", "counters", "touched"):
+        for name in ("table_keys", "table_slots", "unit_index", "counters", "touched"):
             setattr(other, name, getattr(self, name).clone())
+        other._alloc_pass_scratch()
         other.slabs = [s.clone() for s in self.slabs]
         other.slab_base = torch.zeros_like(self.slab_base)
         for n, sl in enumerate(other.slabs):

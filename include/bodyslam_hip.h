@@ -388,44 +388,32 @@ int bs_pose_chain_from(const float* t_rel, int32_t N, const double* g0_dev, doub
  *   blocks      one per volume unit: res^3 voxels x 5 fp32 (tsdf, weight, r, g, b), voxel x*res^2 + y*res + z, zero-filled; block s
  *               lives at slab_base[s / slab_units] + (s % slab_units) * res^3 * 20 bytes (slab_base: int64 device array)
  *   unit table  open addressing: table_keys int64 [table_cap] (-1 = empty; table_cap a power of two), table_slots int32 [table_cap]
- *               (-1 until a block is assigned), table_stamp int32 [table_cap]; unit_index int32 [max_units, 3]
- *   counters    int32 [3]: number of units (persists across calls), units touched by the last bs_tsdf_touch, overflow flag
- *               (1: table full, 2: more new units than blocks -- sticky: set by any frame since the caller last cleared it, so a
- *               stream of frames can be checked once at its end)
+ *               (-1 until a block is assigned), table_fmask uint64 [table_cap] (bit f = record f of the pass under way touches the
+ *               unit; zero between passes); unit_index int32 [max_units, 3]; unit_mask uint64 [max_units] and touched int32
+ *               [max_units] (scratch of a pass: the records that reach a block, the blocks of the pass)
+ *   counters    int32 [3]: number of units (persists across calls), units updated by the last integrate or update call, overflow
+ *               flag (1: table full, 2: more new units than blocks, 3: see the update call -- sticky: set by any call since the
+ *               caller last cleared it, so a stream of frames can be checked once at its end)
  *
- * bs_tsdf_touch: ScalableTSDFVolume::Integrate's unit discovery -- every unit that meets the +-sdf_trunc box of a point of the
- *   depth image sampled every `stride` pixels (depth fp32 [H, W] metres, <= 0 invalid; pose = rows 0..2 of the camera->world 4x4,
- *   i.e. extrinsic^-1; K = (fx, fy, cx, cy); both host doubles) is inserted, gets a block number and -- unless its bounding sphere
- *   lies wholly outside the view frustum, where the integration updates nothing -- goes on `touched` (int32 [max_units]);
- *   frame_id must differ from call to call.
- * bs_tsdf_integrate: UniformTSDFVolume::IntegrateWithDepthToCameraDistanceMultiplier on the units of `touched`
- *   (extrinsic = rows 0..2 of the world->camera 4x4; color u8 [H, W, 3] or NULL).  Their number is read on the device from
- *   n_touched_dev (= counters + 1); the host value n_touched only sizes the grid (any value >= 1 works), so a stream of frames is
- *   integrated without reading anything back.  The blocks handed out must exist: bs_tsdf_touch's max_units is the number of blocks
- *   the caller has allocated (it raises overflow flag 2 rather than hand out a block that does not exist).
- * bs_tsdf_extract: ScalableTSDFVolume::ExtractPointCloud (points, colours, normals) over blocks 0 .. units-1 in two passes:
- *   points == NULL counts into unit_count int32 [units]; otherwise unit_offset int64 [units] (exclusive prefix sums of the counts)
- *   places each unit's points, points / colors fp32 [total, 3]; normals fp32 [total, 3] or NULL: ScalableTSDFVolume::GetNormalAt,
- *   the normalised central difference of the trilinearly interpolated tsdf (GetTSDFAt) at +-0.99 voxel_length. */
-int bs_tsdf_touch(const float* depth, int32_t H, int32_t W, int32_t stride, const double* K, const double* pose, double unit_length,
-                  double sdf_trunc, void* table_keys, int32_t* table_slots, int32_t* table_stamp, int32_t table_cap, int32_t frame_id,
-                  int32_t* unit_index, int32_t max_units, int32_t* counters, int32_t* touched, void* stream);
-int bs_tsdf_integrate(const float* depth, const uint8_t* color, int32_t H, int32_t W, const double* K, const double* extrinsic,
-                      const int32_t* unit_index, const int32_t* touched, int32_t n_touched, const int64_t* slab_base, int32_t slab_units,
-                      int32_t res, double voxel_length, double sdf_trunc, const int32_t* n_touched_dev, void* stream);
-/* A batch of frames at once (the reference integrates frame by frame, 3DM/slam.py:179; a voxel's running mean takes the frames in
- * order and nothing else orders them, so up to BS_TSDF_BATCH_MAX frames are integrated by loading every touched voxel once, applying
- * the frames that touch its unit in ascending order in registers and storing it once -- bit for bit what that many
- * bs_tsdf_touch + bs_tsdf_integrate calls leave in the blocks, in three launches).
+ * There is one integration path, and a single frame is a batch of one record (n_frames = 1).  The reference integrates frame by
+ * frame (3DM/slam.py:179); a voxel's running mean takes the frames in order and nothing else orders them, so up to
+ * BS_TSDF_BATCH_MAX frames are integrated by loading every touched voxel once, applying the frames that touch its unit in
+ * ascending order in registers and storing it once -- bit for bit what that many calls with one record each leave in the blocks,
+ * in three launches.
  *   bs_tsdf_frames_upload    writes the batch's frame records (BS_TSDF_FRAME_BYTES each) to frames_dev: depth[f] / color[f] = the frames' device
- *                            images (color NULL or all entries NULL: no colours), K = (fx, fy, cx, cy), extrinsics / poses = host
- *                            doubles [n_frames, 16]: the world->camera 4x4 of every frame and its inverse
- *   bs_tsdf_touch_batch      unit discovery of all frames: inserts the units and ORs bit f into table_fmask (uint64 [table_cap], zero
- *                            between batches) of every unit frame f touches.  No blocks are handed out: the caller reads counters[0]
- *                            and counts the entries with a key but no slot, makes the missing blocks, then calls
- *   bs_tsdf_integrate_batch  block assignment (max_units = the blocks that exist; overflow flag 2 otherwise), the per-frame frustum
- *                            test, unit_mask (uint64 [max_units]) and `touched`, then the integration; counters[1] = the units updated;
- *                            table_fmask is zero again afterwards */
+ *                            images (depth fp32 [H, W] metres, <= 0 invalid; color u8 [H, W, 3]; color NULL or all entries NULL: no
+ *                            colours), K = (fx, fy, cx, cy), extrinsics / poses = host doubles [n_frames, 16]: the world->camera 4x4
+ *                            of every frame and its inverse
+ *   bs_tsdf_touch_batch      ScalableTSDFVolume::Integrate's unit discovery for all frames: every unit that meets the +-sdf_trunc box of
+ *                            a point of frame f's depth image sampled every `stride` pixels is inserted and gets bit f in table_fmask.
+ *                            No blocks are handed out: a caller that can wait reads counters[0] and counts the entries with a mask but
+ *                            no slot, makes the missing blocks, then calls
+ *   bs_tsdf_integrate_batch  block assignment (max_units = the blocks that exist: overflow flag 2 is raised rather than a block handed
+ *                            out that does not exist, so a stream of frames may be enqueued against blocks allocated ahead and
+ *                            checked once at its end), the per-frame frustum test (a unit whose bounding sphere lies wholly outside
+ *                            a frame's view holds no voxel that frame updates), unit_mask and `touched`, then
+ *                            UniformTSDFVolume::IntegrateWithDepthToCameraDistanceMultiplier on those units; counters[1] = the
+ *                            units updated; table_fmask is zero again afterwards */
 #define BS_TSDF_BATCH_MAX 64
 #define BS_TSDF_FRAME_BYTES 256
 int bs_tsdf_frames_upload(const float* const* depth, const uint8_t* const* color, const double* K, const double* extrinsics, const double* poses,
@@ -447,6 +435,10 @@ int bs_tsdf_update_batch(const void* frames_dev, int32_t n_frames, int32_t H, in
                          void* table_fmask, int32_t table_cap, int32_t* unit_index, int32_t max_units, int32_t* counters, int32_t* touched,
                          void* unit_mask, const int64_t* slab_base, int32_t slab_units, int32_t res, double voxel_length, double sdf_trunc,
                          uint64_t remove_mask, void* stream);
+/* ScalableTSDFVolume::ExtractPointCloud (points, colours, normals) over blocks 0 .. units-1 in two passes: points == NULL counts into
+ * unit_count int32 [units]; otherwise unit_offset int64 [units] (exclusive prefix sums of the counts) places each unit's points,
+ * points / colors fp32 [total, 3]; normals fp32 [total, 3] or NULL: ScalableTSDFVolume::GetNormalAt, the normalised central
+ * difference of the trilinearly interpolated tsdf (GetTSDFAt) at +-0.99 voxel_length. */
 int bs_tsdf_extract(const int32_t* unit_index, int32_t units, const void* table_keys, const int32_t* table_slots, int32_t table_cap,
                     const int64_t* slab_base, int32_t slab_units, int32_t res, double voxel_length, int32_t* unit_count,
                     const int64_t* unit_offset, float* points, float* colors, float* normals, void* stream);
@@ -477,7 +469,7 @@ int bs_tsdf_mesh(const int32_t* unit_index, int32_t units, const void* table_key
  *   [n_views, H, W, 3] (world), normal fp32 [n_views, H, W, 3] (GetNormalAt of the point, as bs_tsdf_extract writes it), color u8
  *   [n_views, H, W, 3]; zeros where there is no hit; vertex, normal and color may each be NULL and are then not computed.
  *   The map is only read, through the unit table (an entry without a block is empty space): neither the unit count nor a host
- *   round trip is needed, so the call may follow un-synchronised bs_tsdf_touch / bs_tsdf_integrate calls on the same stream.
+ *   round trip is needed, so the call may follow un-synchronised bs_tsdf_touch_batch / bs_tsdf_integrate_batch calls on the same stream.
  *   n_views == 0 returns BS_OK. */
 #define BS_TSDF_RAYCAST_VIEWS 32
 int bs_tsdf_raycast(const double* K, const double* extrinsics, int32_t n_views, int32_t H, int32_t W, double depth_min, double depth_max,

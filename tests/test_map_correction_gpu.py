@@ -1,4 +1,4 @@
-"""TSDF de-integration and map correction on the GPU (TSDF.apply_batch / deintegrate, csrc/tsdf.hip tsdf_update_batch_kernel;
+"""TSDF de-integration and map correction on the GPU (TSDF.apply_batch / deintegrate, csrc/tsdf.hip tsdf_apply_batch_kernel<true>;
 map_correction.plan_map_correction; run_slam_loop's map_correction modes).
 
 What is exact is compared exactly: weights (small integers), emptied blocks (bit-equal to zeros), one pass against one record at a

@@ -276,6 +276,37 @@ def test_raycast_table_entry_without_block_is_empty_space():
     assert (out.depth > 0).float().mean() > 0.8
 
 
+@pytest.mark.parametrize("seen,kept", [(0, 1), (1, 0)])
+def test_discover_leaves_no_bits_for_the_next_pass(seen, kept):
+    """discover(frame `seen`) marks units in table_fmask and no pass follows that clears it: a bit left behind would name record 0 of
+    the next pass, and frame `kept` would be integrated into the units only frame `seen` opened.  (Toy frame 0 opens no unit that
+    frame 1 does not; frame 1 opens two that frame 0 does not, oracle/tsdf_ref.py -- hence the second case.)"""
+    from bodyslam_amd.tsdf import TSDF, RGBDImage
+
+    def volume():
+        return TSDF(0.01, 0.04, volume_unit_resolution=8, depth_sampling_stride=4, max_units=8192)
+
+    fr = toy_frames()
+    (Ps, cols, ds), (Pk, colk, dk) = fr[seen], fr[kept]
+    prod = volume()
+    prod.discover(RGBDImage(cols, ds), intr(), np.linalg.inv(Ps))
+    opened = int((prod.table_keys != -1).sum())
+    assert opened > 0 and not prod.table_fmask.any()
+    prod.reserve_discovered()
+    prod.build_3D_map(RGBDImage(colk, dk), intr(), np.linalg.inv(Pk))
+    fresh = volume()
+    fresh.build_3D_map(RGBDImage(colk, dk), intr(), np.linalg.inv(Pk))
+    assert prod.sync()[0] == prod.n_units and set(fresh.index) <= set(prod.index)
+    for key in fresh.index:
+        assert np.array_equal(prod.unit(key), fresh.unit(key)), key
+    # the units only the discovered frame opened: in the table, without a block or with one that holds zeros
+    if (seen, kept) == (1, 0):
+        assert int((prod.table_keys != -1).sum()) > len(fresh.index)
+    for key in set(prod.index) - set(fresh.index):
+        assert not prod.unit(key).any(), key
+    assert sum(int(s.count_nonzero()) for s in prod.slabs) == sum(int(s.count_nonzero()) for s in fresh.slabs) > 0
+
+
 def test_raycast_refuses_bad_arguments():
     from bodyslam_amd._lib import BodySlamHipError
     prod = build_toy(0.01, 0.04)

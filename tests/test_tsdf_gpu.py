@@ -29,18 +29,27 @@ def sort_rows(p, c):
     return p[o], c[o]
 
 
+@pytest.mark.parametrize("batched", [False, True])
 @pytest.mark.parametrize("res,stride", [(8, 4), (4, 8)])
-def test_tsdf_matches_oracle(res, stride, tmp_path):
+def test_tsdf_matches_oracle(res, stride, batched, tmp_path):
+    """batched=False: a pass per frame; True: the three frames in one build_3D_map_batch call (they meet in registers)"""
     from bodyslam_amd.tsdf import TSDF, PinholeCameraIntrinsic, RGBDImage
     from oracle.tsdf_ref import TSDFRef
     vl, trunc = 0.01, 0.04
     prod = TSDF(vl, trunc, volume_unit_resolution=res, depth_sampling_stride=stride, slab_bytes=1 << 16)   # several slabs
     ref = TSDFRef(vl, trunc, res=res, stride=stride)
     intr = PinholeCameraIntrinsic(W, H, *K)
+    rgbds, extrinsics = [], []
     for seed in range(3):
         depth, color, E = scene(seed)
-        prod.build_3D_map(RGBDImage(color, depth), intr, torch.from_numpy(E) if seed == 1 else E)
+        rgbds.append(RGBDImage(color, depth))
+        extrinsics.append(torch.from_numpy(E) if seed == 1 else E)
         ref.integrate(depth, color, K, E)
+    if batched:
+        prod.build_3D_map_batch(rgbds, intr, extrinsics)
+    else:
+        for r, E in zip(rgbds, extrinsics):
+            prod.build_3D_map(r, intr, E)
     assert set(prod.index) == set(ref.units)
     worst = 0.0
     for key, vox in ref.units.items():
@@ -92,8 +101,9 @@ def test_tsdf_matches_oracle(res, stride, tmp_path):
 
 
 def test_tsdf_copy_and_reference_parameters():
-    """build_copy_3D_map leaves the original untouched; the reference's own parameters (1 mm voxels, 0.1 m truncation, 32^3 units,
-    stride 8) run on a small image: a point opens the ~7^3 units around it."""
+    """build_copy_3D_map leaves the original untouched -- its blocks, and the scratch of its passes, which the copy must not share;
+    the reference's own parameters (1 mm voxels, 0.1 m truncation, 32^3 units, stride 8) run on a small image: a point opens the
+    ~7^3 units around it."""
     from bodyslam_amd.tsdf import TSDF, PinholeCameraIntrinsic, RGBDImage
     depth = np.zeros((16, 16), np.float32)
     depth[8, 8] = 0.3
@@ -102,7 +112,12 @@ def test_tsdf_copy_and_reference_parameters():
     t.build_3D_map(RGBDImage(None, depth), intr, np.eye(4))
     n = len(t.index)
     assert 6 ** 3 <= n <= 8 ** 3
+    t.build_3D_map_batch([RGBDImage(None, np.zeros_like(depth))], intr, [np.eye(4)])      # a batch call that changes no voxel
+    before = [s.clone() for s in t.slabs]
     t2 = t.build_copy_3D_map(RGBDImage(None, depth), intr, np.eye(4))
+    for name in ("table_fmask", "unit_mask", "frames_dev"):
+        assert getattr(t2, name).data_ptr() != getattr(t, name).data_ptr(), name
+    assert len(t.slabs) == len(before) and all(torch.equal(a, b) for a, b in zip(t.slabs, before))
     # only the voxels that project onto the one measured pixel are updated (most opened units stay empty): the unit that holds
     # the surface point (0, 0, 0.3) is one of them
     L_ = 0.001 * 32
@@ -222,8 +237,8 @@ def test_tsdf_streamed_and_culled_equal_the_synchronous_path():
 
 def test_tsdf_frame_batch_equals_frame_by_frame():
     """build_3D_map_batch: a run of frames integrated in one pass over the map (every touched voxel loaded once, its frames applied in
-    order in registers) leaves the same units and the same voxels, bit for bit, as build_3D_map frame by frame -- with colours and
-    without, across a chunk border (65 frames > the 64-frame mask), into a map that already holds frames, and with culling off"""
+    order in registers) leaves the same units and the same voxels, bit for bit, as build_3D_map frame by frame (a pass of one
+    record per frame: there the frames meet through HBM) -- with colours and without, across a chunk border (65 frames > the 64-frame mask), into a map that already holds frames, and with culling off"""
     import os
     from bodyslam_amd.tsdf import TSDF, PinholeCameraIntrinsic, RGBDImage
     vl, trunc = 0.01, 0.04

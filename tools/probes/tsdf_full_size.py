@@ -1,5 +1,7 @@
 """Probe: the TSDF map at the reference's own parameters (1 mm voxels, 0.1 m truncation, 32^3 units, stride 8; 3DM/tsdf.py:6-12)
-on 640x480 frames -- units opened per frame, host unit discovery time, integrate kernel time and HBM rate, extraction time."""
+on 640x480 frames resident on the device -- units touched and opened per frame, the time of a synchronous build_3D_map call (HIP
+events around it: upload of the record, unit discovery, the round trip that makes the blocks, assignment and integration) and the
+HBM rate that is of the touched voxel state, extraction time."""
 import os
 import sys
 import time
@@ -15,23 +17,32 @@ H, W = 480, 640
 K = (383.1901395, 383.1901395, 276.4727783203125, 124.3335933685303)          # slam.py:25-28
 v, u = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
 rng = np.random.default_rng(0)
-color = rng.integers(0, 256, size=(H, W, 3)).astype(np.uint8)
+color = torch.from_numpy(rng.integers(0, 256, size=(H, W, 3)).astype(np.uint8)).cuda()
 intr = PinholeCameraIntrinsic(W, H, *K)
 t = TSDF()
+ms = []
 for f in range(int(sys.argv[1]) if len(sys.argv) > 1 else 3):
-    depth = (0.12 + 0.03 * np.sin(u / 90.0 + 0.3 * f) * np.cos(v / 70.0)).astype(np.float32)      # an endoscopic working distance
+    depth = torch.from_numpy((0.12 + 0.03 * np.sin(u / 90.0 + 0.3 * f) * np.cos(v / 70.0)).astype(np.float32)).cuda()   # an endoscopic working distance
     pose = np.eye(4)
     pose[:3, 3] = (0.002 * f, 0.0, 0.001 * f)
     E = np.linalg.inv(pose)
-    n0 = len(t.index)
+    n0 = t.n_units
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    torch.cuda.synchronize()
     tw = time.perf_counter()
+    ev[0].record()
     t.build_3D_map(RGBDImage(color, depth), intr, E)
-    nv = t.last_units * 32 ** 3
+    ev[1].record()
     t1 = time.perf_counter()
-    print(f"frame {f}: {t.last_units} units touched ({len(t.index) - n0} new), {nv / 1e6:.0f} M voxels = {nv * 20 / 1e9:.2f} GB of voxel state; "
-          f"unit discovery (device hash table) {t.last_touch_ms:.3f} ms, integrate kernel {t.last_kernel_ms:.3f} ms (HIP events; upper bound of its "
-          f"traffic, 40 B x every voxel of the touched units: {nv * 40 / (t.last_kernel_ms * 1e-3) / 1e12:.2f} TB/s); whole build_3D_map call "
-          f"{(t1 - tw) * 1e3:.1f} ms wall", flush=True)
+    ev[1].synchronize()
+    n_units, touched = t.sync()
+    nv = touched * 32 ** 3
+    ms.append(ev[0].elapsed_time(ev[1]))
+    print(f"frame {f}: {touched} units touched ({n_units - n0} new), {nv / 1e6:.0f} M voxels = {nv * 20 / 1e9:.2f} GB of voxel state; build_3D_map "
+          f"{ms[-1]:.3f} ms (HIP events; upper bound of the integration's traffic, 40 B x every voxel of the touched units: "
+          f"{nv * 40 / (ms[-1] * 1e-3) / 1e12:.2f} TB/s), host side of the call {(t1 - tw) * 1e3:.2f} ms", flush=True)
+if len(ms) > 2:
+    print(f"build_3D_map, frames 2 onwards: median {float(np.median(ms[2:])):.3f} ms, min {min(ms[2:]):.3f} ms")
 t0 = time.perf_counter()
 pcd = t.extract_pcd()
 torch.cuda.synchronize()
