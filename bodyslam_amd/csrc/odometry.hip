@@ -400,8 +400,9 @@ using namespace bs;
 
 extern "C" int bs_depth_u16_to_m(const uint16_t* depth_u16, int64_t n, double depth_scale, double depth_trunc, float* out, void* stream) {
     ODO_ENTRY("bs_depth_u16_to_m");
-    BS_REQUIRE(depth_u16 && out && n >= 0 && depth_scale > 0.0, "bs_depth_u16_to_m: bad argument");
-    if (n == 0) return BS_OK;
+    BS_REQUIRE(n >= 0 && depth_scale > 0.0, "bs_depth_u16_to_m: bad argument");
+    if (n == 0) return BS_OK;        // (an empty tensor's pointers are null: nothing to check)
+    BS_REQUIRE(depth_u16 && out, "bs_depth_u16_to_m: null argument");
     hipLaunchKernelGGL(depth_u16_to_m_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), depth_u16, n,
                        (float)depth_scale, (float)depth_trunc, out);
     BS_CHECK_LAUNCH();
