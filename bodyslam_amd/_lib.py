@@ -170,6 +170,13 @@ _SIGS = {
                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pc_normals": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pc_knn_mean_distance": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p],
+    # voxel down-sampling (csrc/voxel.hip); the origin is a pointer to 3 host doubles
+    "bs_pc_voxel_assign": [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_voxel_flags": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_voxel_accumulate": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_voxel_finish": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     # rigid ICP registration (csrc/icp.hip); lo, hi and dims are pointers to host arrays
     "bs_icp_step": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                     C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -986,6 +993,74 @@ def pc_knn_mean_distance(d2, count, k, avg):
         assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()
     assert d2.numel() == m * k and avg.numel() == m
     check(load_library().bs_pc_knn_mean_distance(p(d2), p(count), m, k, p(avg), stream_ptr()), "bs_pc_knn_mean_distance")
+
+
+PC_VOXEL_AXIS_BITS, PC_VOXEL_EMPTY_KEY, PC_VOXEL_NO_POINT = 21, -1, 0x7fffffff             # (the empty key as the int64 a torch fill_ takes)
+PC_VOXEL_TABLE_FULL, PC_VOXEL_OUT_OF_RANGE, PC_VOXEL_BAD_ATTRIBUTE = 1, 2, 4
+
+
+def _i64(*ts):
+    for t in ts:
+        assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous(), "int64 contiguous device tensors"
+
+
+def _voxel_attrs(points, *attrs):
+    for a in attrs:
+        if a is not None:
+            _pts(a)
+            assert tuple(a.shape) == tuple(points.shape)
+
+
+def pc_voxel_assign(points, origin, voxel_size, keys, first, slot_of_point, status):
+    """points fp32 [n, 3]; origin: 3 host doubles; keys int64 [slots] filled with PC_VOXEL_EMPTY_KEY, first int32 [slots] filled with
+    PC_VOXEL_NO_POINT (slots: a power of two above n), slot_of_point int32 [n], status int32 [1] zeroed: all on the device"""
+    _pts(points)
+    _i64(keys)
+    _i32(first, slot_of_point, status)
+    n, slots = points.shape[0], keys.numel()
+    assert first.numel() == slots and slot_of_point.numel() == n and status.numel() >= 1
+    o_, o_p = _host(origin, "float64", 3)
+    check(load_library().bs_pc_voxel_assign(p(points), n, o_p, float(voxel_size), p(keys), p(first), slots, p(slot_of_point), p(status), stream_ptr()),
+          "bs_pc_voxel_assign")
+
+
+def pc_voxel_flags(slot_of_point, first, leader, is_first):
+    """slot_of_point, leader, is_first int32 [n], first int32 [slots]: all on the device"""
+    _i32(slot_of_point, first, leader, is_first)
+    n = slot_of_point.numel()
+    assert leader.numel() == n and is_first.numel() == n
+    check(load_library().bs_pc_voxel_flags(p(slot_of_point), p(first), first.numel(), n, p(leader), p(is_first), stream_ptr()), "bs_pc_voxel_flags")
+
+
+def pc_voxel_accumulate(points, colors, normals, origin, shift, leader, rank, sums, counts, first_index, row_of_point, status):
+    """points and, or None, colors / normals fp32 [n, 3]; leader, rank (the inclusive scan of is_first), row_of_point int32 [n]; sums int64
+    [m, 3 + 3 per attribute] and counts int32 [m], zeroed; first_index int32 [m]; status int32 [1]: all on the device"""
+    _pts(points)
+    _voxel_attrs(points, colors, normals)
+    _i64(sums)
+    _i32(leader, rank, counts, first_index, row_of_point, status)
+    n, m = points.shape[0], counts.numel()
+    terms = 3 + 3 * (colors is not None) + 3 * (normals is not None)
+    assert leader.numel() == n and rank.numel() == n and row_of_point.numel() == n and first_index.numel() == m and sums.numel() == m * terms
+    o_, o_p = _host(origin, "float64", 3)
+    check(load_library().bs_pc_voxel_accumulate(p(points), p(colors), p(normals), n, o_p, int(shift), p(leader), p(rank), m, p(sums), p(counts),
+                                                p(first_index), p(row_of_point), p(status), stream_ptr()), "bs_pc_voxel_accumulate")
+
+
+def pc_voxel_finish(points, colors, normals, sums, counts, first_index, origin, shift, unit_normals, out_points, out_colors, out_normals):
+    """the inputs of pc_voxel_accumulate after it; out_points and, with their inputs, out_colors / out_normals fp32 [m, 3] (device)"""
+    _pts(points, out_points)
+    _voxel_attrs(points, colors, normals)
+    _voxel_attrs(out_points, out_colors, out_normals)
+    _i64(sums)
+    _i32(counts, first_index)
+    n, m = points.shape[0], counts.numel()
+    terms = 3 + 3 * (colors is not None) + 3 * (normals is not None)
+    assert (colors is None) == (out_colors is None) and (normals is None) == (out_normals is None)
+    assert out_points.shape[0] == m and first_index.numel() == m and sums.numel() == m * terms
+    o_, o_p = _host(origin, "float64", 3)
+    check(load_library().bs_pc_voxel_finish(p(points), p(colors), p(normals), n, p(sums), p(counts), p(first_index), m, o_p, int(shift),
+                                            int(bool(unit_normals)), p(out_points), p(out_colors), p(out_normals), stream_ptr()), "bs_pc_voxel_finish")
 
 
 ICP_POINT_TO_POINT, ICP_POINT_TO_PLANE = 0, 1

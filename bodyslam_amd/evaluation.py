@@ -534,7 +534,7 @@ def _distance_stats(rec: np.ndarray) -> DistanceStats:
 
 
 _ICP_KEYS = ("max_correspondence_distance", "init", "estimation", "target_normals", "max_iteration", "relative_fitness", "relative_rmse", "cell_size",
-             "device")
+             "device", "voxel_size")       # (voxel_size is the evaluation's own: _align_icp takes it out before registration_icp is called)
 
 
 def _check_align(align, icp) -> Optional[dict]:
@@ -557,6 +557,9 @@ def _check_align(align, icp) -> Optional[dict]:
     if kw["estimation"] not in REG.ESTIMATIONS:
         raise ValueError(f"unknown estimation {kw['estimation']!r}: one of {REG.ESTIMATIONS}")
     REG._check_criteria(kw.get("max_iteration", 30), kw.get("relative_fitness", 1e-6), kw.get("relative_rmse", 1e-6))
+    if kw.get("voxel_size") is not None:
+        from .pointcloud import _check_voxel_size
+        kw["voxel_size"] = _check_voxel_size(kw["voxel_size"])
     return kw
 
 
@@ -565,24 +568,39 @@ def _align_icp(p, g, p_normals, g_normals, A, kw, dev):
     import dataclasses
 
     from . import registration as REG
+    from . import pointcloud as PC
     kw = dict(kw)
     radius, est, init = kw.pop("max_correspondence_distance"), kw.pop("estimation"), kw.pop("init")
+    h = kw.pop("voxel_size", None)                                 # (not a keyword of registration_icp, whose signature is pinned)
     normals = kw.pop("target_normals", None)
     if normals is None:
         normals = g_normals
+
+    def thinned(cloud, n):
+        """the registration's (cloud, normals): as they are, or with voxel_size one point and one unit normal per voxel"""
+        if h is None:
+            return cloud, n
+        if n is not None:
+            n = REG._as_normals(n, int(cloud.shape[0])).to(dev)
+        r = PC.voxel_down_sample(cloud, h, normals=n, unit_normals=True)
+        return r.points, r.normals
     if est == "auto" and normals is None and p_normals is not None:
         # the map has normals and the scan has none: gt -> pred by point-to-plane, inverted.  Normals follow `transform` by the inverse
         # transpose of its linear part (R / s for a similarity); their length does not matter to the normal equations' solution
         n = REG._as_normals(p_normals, int(p.shape[0])).to(dev).contiguous()
         if A is not None:
             N = np.concatenate([np.linalg.inv(A[:, :3]).T, np.zeros((3, 1))], 1)
+            if h is not None:                                      # (the thinning averages normals of |a| <= 2: take the scale out)
+                N *= abs(np.linalg.det(A[:, :3])) ** (1.0 / 3.0)
             turned = torch.empty(n.shape[0], 3, dtype=torch.float32, device=dev)
             L.pc_transform(n, N, turned)
             n = turned
-        back = REG.registration_icp(g, p, radius, init=np.linalg.inv(init), estimation="point_to_plane", target_normals=n, **kw)
+        (src, _), (tgt, n) = thinned(g, None), thinned(p, n)
+        back = REG.registration_icp(src, tgt, radius, init=np.linalg.inv(init), estimation="point_to_plane", target_normals=n, **kw)
         res = dataclasses.replace(back, transformation=np.linalg.inv(back.transformation))
     else:
-        res = REG.registration_icp(p, g, radius, init=init, estimation=est, target_normals=normals, **kw)
+        (src, _), (tgt, normals) = thinned(p, None), thinned(g, normals)
+        res = REG.registration_icp(src, tgt, radius, init=init, estimation=est, target_normals=normals, **kw)
     moved = torch.empty(p.shape[0], 3, dtype=torch.float32, device=dev)
     L.pc_transform(p, res.transformation[:3], moved)
     return moved, res
@@ -612,7 +630,10 @@ def evaluate_reconstruction_aligned(pred, gt, thresholds: Sequence[float] = (0.0
     scale is `transform`'s), and the result is applied on the device before the two distance queries; it is returned as
     ReconstructionMetrics.alignment.  Normals for point-to-plane come from icp["target_normals"] or a PointCloud gt; when gt has none and
     pred has them (a TSDF, MAP or PointCloud), estimation "auto" registers gt -> pred by point-to-plane and inverts the result (fitness and
-    rmse are then those of that direction).  align=None: evaluate_reconstruction itself.  (A function of its own: evaluate_reconstruction's
+    rmse are then those of that direction).  icp["voxel_size"] = h: the usual recipe -- both clouds are thinned by
+    pointcloud.voxel_down_sample(h, unit_normals=True), the target's normals averaged along (they must then be finite with |a| <= 2), the
+    registration runs on the thinned clouds in the same direction, and its transform is applied to the full pred: the two distance queries
+    see the full clouds as before; fitness and rmse are those of the thinned pair.  align=None: evaluate_reconstruction itself.  (A function of its own: evaluate_reconstruction's
     parameter list is pinned by tests/test_pointcloud_cpu.py.)"""
     return _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, align, icp)
 

@@ -14,11 +14,18 @@ from everything to the brute-force kernel.  There is no CPU fallback: without a 
 ``query_knn`` extends the same walk from the minimum to the k smallest under the same total order (csrc/knn.hip; Open3D's
 search_knn_vector_3d / search_hybrid_vector_3d), and two things stand on it: ``estimate_normals`` (PointCloud.estimate_normals) and
 ``remove_statistical_outlier`` (PointCloud.remove_statistical_outlier).  Restated, parity with Open3D unpinned; the statement is
-tests/_knn_ref.py.  Not built: pure radius search with an unbounded list, voxel down-sampling, orientation propagation, k > 32.
+tests/_knn_ref.py.
+
+``voxel_down_sample`` (PointCloud.voxel_down_sample, PointCloud.voxel_down_sample_and_trace) thins a cloud to one point per occupied cube
+(csrc/voxel.hip: a hash table of voxel keys, integer sums, rows in order of first appearance; Open3D's PointCloud.voxel_down_sample,
+mapping_module.py:72,156,187).  Restated, parity with Open3D unpinned; the statement is tests/_voxel_ref.py.
+
+Not built: pure radius search with an unbounded list, orientation propagation, k > 32, Open3D's cubic-id trace format.
 """
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import numpy as np
@@ -311,6 +318,132 @@ def remove_statistical_outlier(points, nb_neighbors: int = 20, std_ratio: float 
             threshold = mean + float(std_ratio) * std
         mask = avg.to(torch.float64) < threshold                     # (the compaction is plumbing: a comparison and torch.nonzero)
         return torch.nonzero(mask).reshape(-1), mask
+
+
+@dataclass
+class VoxelDownSample:
+    """voxel_down_sample's result, device tensors; m voxels in order of first appearance"""
+    points: torch.Tensor                    # fp32 [m, 3]
+    colors: Optional[torch.Tensor]          # fp32 [m, 3], None when no colours were given
+    normals: Optional[torch.Tensor]         # fp32 [m, 3], None when no normals were given
+    counts: torch.Tensor                    # int32 [m]: the points in the voxel
+    first_index: torch.Tensor               # int32 [m]: the voxel's lowest point index
+    row_of_point: torch.Tensor              # int32 [n]: the row every input point went to, -1 for a non-finite point
+
+
+def _check_voxel_size(voxel_size) -> float:
+    if isinstance(voxel_size, bool) or not isinstance(voxel_size, (int, float, np.integer, np.floating)):
+        raise ValueError(f"voxel_size {voxel_size!r}: expected a positive finite number")
+    h = float(voxel_size)
+    if not (h > 0.0 and math.isfinite(h)):
+        raise ValueError(f"voxel_size {voxel_size!r}: expected a positive finite number")
+    return h
+
+
+def _as_attribute(a, what: str, n: int) -> Optional[torch.Tensor]:
+    if a is None:
+        return None
+    if isinstance(a, np.ndarray):
+        a = torch.from_numpy(np.ascontiguousarray(a)) if a.dtype in (np.float32, np.float64) else a
+    if not isinstance(a, torch.Tensor) or a.dtype not in (torch.float32, torch.float64) or tuple(a.shape) != (n, 3):
+        raise ValueError(f"{what}: expected a float32 or float64 array or tensor of shape [{n}, 3]")
+    return a.detach()
+
+
+def voxel_geometry(lo: np.ndarray, hi: np.ndarray, h: float) -> Tuple[np.ndarray, int]:
+    """-> (the origin o = (double) lo - 0.5 h as float64 [3], the shift s = 32 - e with max((double) hi - o) = f 2^e, 0.5 <= f < 1) of the voxel
+    grid over the fp32 bounds lo, hi; ValueError when an axis would need 2^21 voxels or more"""
+    o = lo.astype(np.float64) - 0.5 * h
+    ext = hi.astype(np.float64) - o
+    with np.errstate(over="ignore", invalid="ignore"):
+        top = np.floor(ext / h)
+    if not bool((top < 2.0 ** L.PC_VOXEL_AXIS_BITS).all()):
+        raise ValueError(f"voxel_size {h!r} too small: {float(top.max()):.0f} voxels along an axis, at most 2^{L.PC_VOXEL_AXIS_BITS}")
+    return o, 32 - int(math.frexp(float(ext.max()))[1])
+
+
+def voxel_table_slots(n: int) -> int:
+    """the default table: the smallest power of two that is at least 2 n (the kernels need a power of two above n)"""
+    return 1 << max(int(2 * n - 1).bit_length(), 1)
+
+
+def voxel_down_sample(points, voxel_size, colors=None, normals=None, unit_normals=False, device: int = 0) -> VoxelDownSample:
+    """One point per occupied cube of edge voxel_size: Open3D's PointCloud.voxel_down_sample, which the reference runs on its clouds with
+    0.005, 0.009 and 0.05 m (3DM/mapping_module.py:72,156,187) -> VoxelDownSample, device tensors.  Open3D is not vendored: the meaning is
+    restated from its documentation and parity with Open3D is unpinned; the statement is tests/_voxel_ref.py, and the result is bit-equal
+    to it: the same bits in every run, for every order the atomics arrive in.
+
+    points: as ``as_points`` takes them (fp64 is rounded to fp32 once); a point with a non-finite coordinate belongs to no voxel.  With
+    lo, hi the fp32 bounds of the finite points and h = voxel_size as a double: the grid's origin is o = (double) lo - 0.5 h; a point's
+    voxel floor(((double) p - o) / h) per axis in fp64, each component below 2^21 (else ValueError, decided from the bounds before any
+    voxel kernel runs).  Rows come in order of first appearance.  A voxel's position is the mean of its points in exact integer
+    arithmetic -- Q = rint(((double) p - o) 2^s) with s chosen so that the extent fills 32 bits, S = sum Q, fl32(o + S / count / 2^s): off
+    the fp64 mean by less than extent 2^-32 plus half an fp32 ulp -- and a voxel of exactly one point returns that point's bits, its
+    colour's and normal's too.  colors, normals: [n, 3] fp32 or fp64, every component of a point in a voxel finite with |a| <= 2 (else
+    ValueError after the call's read-back), averaged alike with 30 fractional bits: the plain mean, as Open3D documents.  unit_normals
+    scales every averaged normal to unit length in fp64 before the rounding (zero when its length is not positive): what
+    registration_icp wants from a thinned cloud.  counts, first_index and row_of_point play the role of voxel_down_sample_and_trace in
+    tensor form; Open3D's own trace format (the cubic-id matrix) is not built.  Without a finite point every output is empty.  Raises
+    ValueError on bad arguments before the GPU is touched; there is no CPU fallback."""
+    h = _check_voxel_size(voxel_size)
+    t = as_points(points, "points")
+    n = int(t.shape[0])
+    c, nr = _as_attribute(colors, "colors", n), _as_attribute(normals, "normals", n)
+    if not torch.cuda.is_available():
+        L.init(0)                              # raises BodySlamHipError: no CPU fallback
+    dev = t.device if t.is_cuda else torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        L.init(dev.index)
+        pts = t.to(dev).to(torch.float32).contiguous()
+        c, nr = (None if a is None else a.to(dev).to(torch.float32).contiguous() for a in (c, nr))
+        raw = torch.empty(8, dtype=torch.int32, device=dev)
+        L.pc_bounds(pts, raw)
+        lo, hi, n_finite = _decode_bounds(raw.cpu().numpy().view(np.uint32))
+        if n_finite == 0:
+            def empty(given=True):
+                return torch.empty(0, 3, dtype=torch.float32, device=dev) if given else None
+            none = torch.empty(0, dtype=torch.int32, device=dev)
+            return VoxelDownSample(empty(), empty(c is not None), empty(nr is not None), none, none.clone(),
+                                   torch.full((n,), -1, dtype=torch.int32, device=dev))
+        origin, shift = voxel_geometry(lo, hi, h)
+        return _voxel_rows(pts, c, nr, origin, h, shift, bool(unit_normals), voxel_table_slots(n))
+
+
+def _voxel_rows(pts, colors, normals, origin, h, shift, unit_normals, slots) -> VoxelDownSample:
+    """the four launches over fp32 device tensors, with the table size as an argument (the result does not depend on it)"""
+    dev, n = pts.device, int(pts.shape[0])
+    i32 = dict(dtype=torch.int32, device=dev)
+    keys = torch.full((slots,), L.PC_VOXEL_EMPTY_KEY, dtype=torch.int64, device=dev)           # (the fills and the scan are plumbing)
+    first = torch.full((slots,), L.PC_VOXEL_NO_POINT, **i32)
+    slot_of_point, leader, is_first, row_of_point = (torch.empty(n, **i32) for _ in range(4))
+    status = torch.zeros(1, **i32)
+    L.pc_voxel_assign(pts, origin, h, keys, first, slot_of_point, status)
+    L.pc_voxel_flags(slot_of_point, first, leader, is_first)
+    rank = torch.cumsum(is_first, 0).to(torch.int32)                                            # integer, exact
+    m = int(rank[-1].cpu())
+    if m == 0:                                                                                   # (only with a status bit set)
+        _voxel_status(int(status.cpu()), h)
+        raise L.BodySlamHipError("voxel_down_sample: no voxel for the finite points")
+    terms = 3 + 3 * (colors is not None) + 3 * (normals is not None)
+    sums = torch.zeros(m, terms, dtype=torch.int64, device=dev)
+    counts = torch.zeros(m, **i32)
+    first_index = torch.empty(m, **i32)
+    L.pc_voxel_accumulate(pts, colors, normals, origin, shift, leader, rank, sums, counts, first_index, row_of_point, status)
+    out = [None if a is None else torch.empty(m, 3, dtype=torch.float32, device=dev) for a in (pts, colors, normals)]
+    L.pc_voxel_finish(pts, colors, normals, sums, counts, first_index, origin, shift, unit_normals, *out)
+    _voxel_status(int(status.cpu()), h)
+    return VoxelDownSample(out[0], out[1], out[2], counts, first_index, row_of_point)
+
+
+def _voxel_status(word: int, h: float) -> None:
+    if word & L.PC_VOXEL_TABLE_FULL:
+        raise L.BodySlamHipError("voxel_down_sample: the voxel table is full")
+    if word & L.PC_VOXEL_OUT_OF_RANGE:
+        raise ValueError(f"voxel_size {h!r} too small: a voxel coordinate outside [0, 2^{L.PC_VOXEL_AXIS_BITS})")
+    if word & L.PC_VOXEL_BAD_ATTRIBUTE:
+        raise ValueError("colors / normals: every component must be finite with |a| <= 2")
+    if word:
+        raise L.BodySlamHipError(f"voxel_down_sample: status {word}")
 
 
 def point_cloud_distance(source, target, cell_size: Optional[float] = None, device: int = 0, max_distance: Optional[float] = None,

@@ -100,6 +100,24 @@ class PointCloud:
         ind_out = ind.cpu().numpy() if isinstance(self.points, np.ndarray) else ind
         return PointCloud(rows(self.points), rows(self.colors), rows(self.normals)), ind_out
 
+    def voxel_down_sample(self, voxel_size: float) -> "PointCloud":
+        """o3d.geometry.PointCloud.voxel_down_sample: one point per occupied cube of edge voxel_size, with the mean position, colour and
+        normal of the cube's points (the plain mean: a normal is not re-normalised), rows in order of first appearance -- numpy for a
+        numpy cloud, device tensors otherwise.  pointcloud.voxel_down_sample states the arithmetic; restated, parity with Open3D unpinned."""
+        return self.voxel_down_sample_and_trace(voxel_size)[0]
+
+    def voxel_down_sample_and_trace(self, voxel_size: float):
+        """-> (the thinned PointCloud, row_of_point int32 [M] -- the output row of every input point, -1 for a non-finite one --, counts int32
+        [m]): the role of o3d.geometry.PointCloud.voxel_down_sample_and_trace in tensor form.  Open3D's own trace (the cubic-id matrix and
+        the index lists) is not built, and it takes no bounds: the grid is the one of pointcloud.voxel_down_sample."""
+        from .pointcloud import voxel_down_sample
+        r = voxel_down_sample(self.points, voxel_size, colors=self.colors, normals=self.normals)
+        host = isinstance(self.points, np.ndarray)
+
+        def out(a):
+            return a.cpu().numpy() if host and a is not None else a
+        return PointCloud(out(r.points), out(r.colors), out(r.normals)), out(r.row_of_point), out(r.counts)
+
 
 @dataclass
 class TriangleMesh:

@@ -713,6 +713,53 @@ int bs_pc_normals(const float* points, int64_t n, const int32_t* index, const in
                   const double* vector, float* normals, double* eigenvalues, void* stream);
 int bs_pc_knn_mean_distance(const float* d2, const int32_t* count, int64_t m, int32_t k, float* avg, void* stream);
 
+/* ---- voxel down-sampling -----------------------------------------------------------------------------------------------------------------
+ * The four bs_pc_voxel_* launches replace Open3D's PointCloud.voxel_down_sample, which the reference calls at
+ * BodySLAM_not_refactored/3DM/mapping_module.py:72,156,187 (0.005, 0.009 and 0.05 m), and return what voxel_down_sample_and_trace is used
+ * for as three index arrays.  Restated from Open3D's documented meaning; parity with Open3D is UNPINNED, and Open3D's own trace format (the
+ * [m, 8] cubic-id matrix) is not built.  The statement is tests/_voxel_ref.py.  points [n, 3] fp32 (device); a point with a non-finite
+ * coordinate belongs to no voxel.  The caller computes, on the host, from bs_pc_bounds' lo and hi and the voxel size h (a double):
+ * origin o = (double) lo - 0.5 h (3 host doubles); that floor(((double) hi - o) / h) < 2^BS_PC_VOXEL_AXIS_BITS on every axis; and the
+ * shift s = 32 - e, where max over the axes of (double) hi - o = f 2^e with 0.5 <= f < 1.
+ *   voxel           v = floor(((double) p - o) / h) per axis in fp64, one subtraction and one division, no contraction;
+ *                   key = vz << 42 | vy << 21 | vx
+ *   rows            in order of first appearance: row r is the voxel whose lowest point index is the r-th smallest
+ *   position        Q = rint(ldexp((double) p - o, s)) as int64, 0 <= Q <= 2^32; S = sum Q over the voxel, exact;
+ *                   fl32(o + ldexp((double) S / (double) count, -s)).  A voxel of exactly one point returns that point's bits (and its
+ *                   colour's and normal's; unit_normals excepted)
+ *   colours, normals   Q = rint((double) a 2^30); every component of a point in a voxel must be finite with |a| <= 2, else the status bit
+ *                   BS_PC_VOXEL_BAD_ATTRIBUTE; fl32(ldexp((double) S / (double) count, -30)), the plain mean.  unit_normals: the three
+ *                   means d scaled by 1 / sqrt((d0 d0 + d1 d1) + d2 d2) in fp64 before the rounding, zero when the length is not positive
+ *   bs_pc_voxel_assign      one thread per point inserts its key into the table keys [slots] of 64-bit words (device; filled with
+ *                   BS_PC_VOXEL_EMPTY_KEY by the caller) by compare-and-swap with linear probing, takes the minimum of its index into
+ *                   first int32 [slots] (device; filled with BS_PC_VOXEL_NO_POINT by the caller) and stores slot_of_point int32 [n]
+ *                   (-1: in no voxel).  slots: a power of two above n.  After `slots` probes without a free slot or a match the thread sets
+ *                   BS_PC_VOXEL_TABLE_FULL and gives up: no loop is unbounded.  A voxel coordinate outside [0, 2^21) -- an origin that
+ *                   does not belong to the points -- sets BS_PC_VOXEL_OUT_OF_RANGE.  status int32 [1] (device, zeroed by the caller)
+ *   bs_pc_voxel_flags       leader int32 [n] = first[slot_of_point] (-1: none), is_first int32 [n] = (leader == the point's index).  The
+ *                   caller scans is_first inclusively: rank int32 [n]; the voxel led by point j is row rank[j] - 1, and m = rank[n - 1]
+ *   bs_pc_voxel_accumulate  one thread per point adds its 3, 6 or 9 terms (position, then colours, then normals; colors / normals NULL when
+ *                   absent) to sums [m, terms] of 64-bit words and 1 to counts int32 [m] (device, both zeroed by the caller) with integer
+ *                   atomics; a run of adjacent lanes of a wave with the same row is summed in the wave first and its last lane issues the
+ *                   atomics (integer addition is associative: the same sums).  Writes row_of_point int32 [n] (-1: in no voxel) and
+ *                   first_index int32 [m]
+ *   bs_pc_voxel_finish      one thread per row: out_points fp32 [m, 3], out_colors / out_normals fp32 [m, 3] or NULL with their inputs
+ * No floating-point atomics, and the phases are separate launches: the same bits in every run, for every table size and every slot. */
+#define BS_PC_VOXEL_AXIS_BITS 21
+#define BS_PC_VOXEL_EMPTY_KEY 0xffffffffffffffffull
+#define BS_PC_VOXEL_NO_POINT 0x7fffffff
+enum { BS_PC_VOXEL_TABLE_FULL = 1, BS_PC_VOXEL_OUT_OF_RANGE = 2, BS_PC_VOXEL_BAD_ATTRIBUTE = 4 };
+int bs_pc_voxel_assign(const float* points, int64_t n, const double* origin, double voxel_size, void* keys, int32_t* first, int64_t slots,
+                       int32_t* slot_of_point, int32_t* status, void* stream);
+int bs_pc_voxel_flags(const int32_t* slot_of_point, const int32_t* first, int64_t slots, int64_t n, int32_t* leader, int32_t* is_first,
+                      void* stream);
+int bs_pc_voxel_accumulate(const float* points, const float* colors, const float* normals, int64_t n, const double* origin, int32_t shift,
+                           const int32_t* leader, const int32_t* rank, int64_t m, void* sums, int32_t* counts, int32_t* first_index,
+                           int32_t* row_of_point, int32_t* status, void* stream);
+int bs_pc_voxel_finish(const float* points, const float* colors, const float* normals, int64_t n, const void* sums, const int32_t* counts,
+                       const int32_t* first_index, int64_t m, const double* origin, int32_t shift, int32_t unit_normals, float* out_points,
+                       float* out_colors, float* out_normals, void* stream);
+
 /* ---- rigid ICP registration ------------------------------------------------------------------------------------------------------------
  * bs_icp_step + bs_icp_finish replace Open3D's pipelines.registration.registration_icp with TransformationEstimationPointToPlane or
  * TransformationEstimationPointToPoint (no scale) and ICPConvergenceCriteria, and, in BS_ICP_EVALUATE mode, evaluate_registration: what
