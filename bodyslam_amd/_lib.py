@@ -177,6 +177,19 @@ _SIGS = {
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pc_voxel_finish": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                            C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    # triangle-mesh scene (csrc/mesh_scene.hip); every pointer is a device pointer
+    "bs_mesh_records": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_cast_brute": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6,
+    "bs_mesh_closest_brute": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int32] +
+                             [C.c_void_p] * 6,
+    "bs_mesh_grid_count": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p],
+    "bs_mesh_grid_scatter": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_mesh_cast_grid": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                          C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 8,
+    "bs_mesh_closest_grid": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_int64,
+                             C.c_float, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8,
+    "bs_mesh_sample_weights": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_sample": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64] + [C.c_void_p] * 5,
     # rigid ICP registration (csrc/icp.hip); lo, hi and dims are pointers to host arrays
     "bs_icp_step": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                     C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -1096,3 +1109,154 @@ def icp_finish(partial, m, lo, hi, estimation, mode, max_iteration, relative_fit
     assert partial.numel() >= -(-m // ICP_BLOCK) * ICP_PARTIAL_FIELDS and state.numel() >= ICP_STATE_FIELDS + ICP_LOG_FIELDS * int(max_iteration)
     check(load_library().bs_icp_finish(p(partial), int(m), lo_p, hi_p, int(estimation), int(mode), int(max_iteration), float(relative_fitness),
                                        float(relative_rmse), p(state), stream_ptr()), "bs_icp_finish")
+
+
+# ---- triangle-mesh scene (csrc/mesh_scene.hip) ------------------------------------------------------------------------------------------
+MESH_MAX_TRIANGLES, MESH_MAX_SAMPLED_TRIANGLES = 1 << 29, 1 << 22
+
+
+def _f32(t, *shape):
+    assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape, (t.dtype, tuple(t.shape), shape)
+
+
+def _mesh_records(records, n_triangles):
+    assert records.dtype == torch.float32 and records.is_cuda and records.is_contiguous() and records.dim() == 3
+    assert tuple(records.shape[1:]) == (3, 4) and 0 <= n_triangles <= records.shape[0]
+
+
+def mesh_records(vertices, triangles, records, kept):
+    """vertices fp32 [V, 3], triangles int32 [T, 3], records fp32 [T, 3, 4], kept int32 [1]: all on the device"""
+    _pts(vertices)
+    _i32(triangles, kept)
+    T = triangles.shape[0]
+    assert triangles.dim() == 2 and triangles.shape[1] == 3 and kept.numel() >= 1
+    _mesh_records(records, T)
+    check(load_library().bs_mesh_records(p(vertices), vertices.shape[0], p(triangles), T, p(records), p(kept), stream_ptr()), "bs_mesh_records")
+
+
+def _mesh_query(records, n_triangles, rows, width, fallback_list, m, keys, geom_start, geometry_ids, primitive_ids, uvs):
+    _mesh_records(records, n_triangles)
+    n = rows.shape[0]
+    _f32(rows, n, width)
+    _f32(uvs, n, 2)
+    _i32(geom_start, geometry_ids, primitive_ids)
+    assert geometry_ids.numel() == n and primitive_ids.numel() == n and geom_start.numel() >= 1
+    assert keys is None or (keys.dtype == torch.int64 and keys.is_cuda and keys.is_contiguous() and keys.numel() >= m)
+    if fallback_list is None:
+        assert m == n
+    else:
+        _i32(fallback_list)
+        assert 1 <= m <= fallback_list.numel()
+
+
+def mesh_cast_brute(records, n_triangles, rays, fallback_list, m, keys, geom_start, t_hit, geometry_ids, primitive_ids, uvs, normals):
+    """rays fp32 [n, 6]; fallback_list: int32 device tensor of m ray rows, or None for all m = n rays; keys int64 [>= m] scratch; geom_start
+    int32 [n_geom + 1]; the outputs fp32 [n], int32 [n], int32 [n], fp32 [n, 2], fp32 [n, 3]"""
+    _mesh_query(records, n_triangles, rays, 6, fallback_list, m, keys, geom_start, geometry_ids, primitive_ids, uvs)
+    n = rays.shape[0]
+    _f32(t_hit, n)
+    _f32(normals, n, 3)
+    check(load_library().bs_mesh_cast_brute(p(records), int(n_triangles), p(rays), n, p(fallback_list), int(m), p(keys), p(geom_start),
+                                            geom_start.numel() - 1, p(t_hit), p(geometry_ids), p(primitive_ids), p(uvs), p(normals), stream_ptr()),
+          "bs_mesh_cast_brute")
+
+
+def mesh_closest_brute(records, n_triangles, query, fallback_list, m, max_distance, keys, geom_start, points, distance, geometry_ids, primitive_ids,
+                       uvs):
+    """query fp32 [n, 3]; the outputs fp32 [n, 3], fp32 [n], int32 [n], int32 [n], fp32 [n, 2]; the rest as mesh_cast_brute"""
+    _mesh_query(records, n_triangles, query, 3, fallback_list, m, keys, geom_start, geometry_ids, primitive_ids, uvs)
+    n = query.shape[0]
+    _f32(points, n, 3)
+    _f32(distance, n)
+    check(load_library().bs_mesh_closest_brute(p(records), int(n_triangles), p(query), n, p(fallback_list), int(m), float(max_distance), p(keys),
+                                               p(geom_start), geom_start.numel() - 1, p(points), p(distance), p(geometry_ids), p(primitive_ids),
+                                               p(uvs), stream_ptr()), "bs_mesh_closest_brute")
+
+
+def _mesh_grid(grid):
+    """grid: (lo, hi, cell_size, dims, pad) -> the host arrays (kept alive by the caller) and their addresses"""
+    lo, hi, h, dims, pad = grid
+    return _host(lo, "float32", 3), _host(hi, "float32", 3), float(h), _host(dims, "int32", 3), float(pad)
+
+
+def mesh_grid_count(records, n_triangles, grid, counts):
+    """counts int32 [cells], zeroed: += 1 for every (kept triangle, cell its padded box overlaps)"""
+    _mesh_records(records, n_triangles)
+    _i32(counts)
+    (lo_, lo_p), (hi_, hi_p), h, (d_, d_p), pad = _mesh_grid(grid)
+    assert counts.numel() >= int(d_[0]) * int(d_[1]) * int(d_[2])
+    check(load_library().bs_mesh_grid_count(p(records), int(n_triangles), lo_p, hi_p, h, d_p, pad, p(counts), stream_ptr()), "bs_mesh_grid_count")
+
+
+def mesh_grid_scatter(records, n_triangles, grid, cursor, refs):
+    """cursor int32 [cells]: a copy of the exclusive scan (advanced by the call); refs int32 [n_refs]"""
+    _mesh_records(records, n_triangles)
+    _i32(cursor, refs)
+    (lo_, lo_p), (hi_, hi_p), h, (d_, d_p), pad = _mesh_grid(grid)
+    assert cursor.numel() >= int(d_[0]) * int(d_[1]) * int(d_[2])
+    check(load_library().bs_mesh_grid_scatter(p(records), int(n_triangles), lo_p, hi_p, h, d_p, pad, p(cursor), refs.numel(), p(refs), stream_ptr()),
+          "bs_mesh_grid_scatter")
+
+
+def _mesh_index(refs, cell_start, d_, fallback_list, fallback_count, n):
+    _i32(refs, cell_start, fallback_list, fallback_count)
+    assert cell_start.numel() == int(d_[0]) * int(d_[1]) * int(d_[2]) + 1 and fallback_list.numel() >= n and fallback_count.numel() >= 1
+
+
+def mesh_cast_grid(records, n_triangles, refs, cell_start, grid, origin_limit, rays, geom_start, t_hit, geometry_ids, primitive_ids, uvs, normals,
+                   fallback_list, fallback_count):
+    """the outputs of mesh_cast_brute for every ray the walk finishes; the others on fallback_list int32 [>= n] (fallback_count int32 [1])"""
+    n = rays.shape[0]
+    _mesh_query(records, n_triangles, rays, 6, None, n, None, geom_start, geometry_ids, primitive_ids, uvs)
+    _f32(t_hit, n)
+    _f32(normals, n, 3)
+    (lo_, lo_p), (hi_, hi_p), h, (d_, d_p), pad = _mesh_grid(grid)
+    _mesh_index(refs, cell_start, d_, fallback_list, fallback_count, n)
+    check(load_library().bs_mesh_cast_grid(p(records), int(n_triangles), p(refs), p(cell_start), lo_p, hi_p, h, d_p, pad, float(origin_limit), p(rays), n,
+                                           p(geom_start), geom_start.numel() - 1, p(t_hit), p(geometry_ids), p(primitive_ids), p(uvs), p(normals),
+                                           p(fallback_list), p(fallback_count), stream_ptr()), "bs_mesh_cast_grid")
+
+
+def mesh_closest_grid(records, n_triangles, refs, cell_start, grid, query, max_distance, shell_cap, geom_start, points, distance, geometry_ids,
+                      primitive_ids, uvs, fallback_list, fallback_count):
+    """the outputs of mesh_closest_brute for every point the walk finishes; the others on fallback_list"""
+    n = query.shape[0]
+    _mesh_query(records, n_triangles, query, 3, None, n, None, geom_start, geometry_ids, primitive_ids, uvs)
+    _f32(points, n, 3)
+    _f32(distance, n)
+    (lo_, lo_p), (hi_, hi_p), h, (d_, d_p), pad = _mesh_grid(grid)
+    _mesh_index(refs, cell_start, d_, fallback_list, fallback_count, n)
+    check(load_library().bs_mesh_closest_grid(p(records), int(n_triangles), p(refs), p(cell_start), lo_p, hi_p, h, d_p, pad, p(query), n,
+                                              float(max_distance), int(shell_cap), p(geom_start), geom_start.numel() - 1, p(points), p(distance),
+                                              p(geometry_ids), p(primitive_ids), p(uvs), p(fallback_list), p(fallback_count), stream_ptr()),
+          "bs_mesh_closest_grid")
+
+
+def mesh_sample_weights(records, area, top, weights):
+    """records fp32 [T, 3, 4]; area fp64 [T] and top int64 [1]: scratch; weights int64 [T]"""
+    T = records.shape[0]
+    _mesh_records(records, T)
+    _i64(top, weights)
+    assert area.dtype == torch.float64 and area.is_cuda and area.is_contiguous() and area.numel() == T and weights.numel() == T and top.numel() >= 1
+    check(load_library().bs_mesh_sample_weights(p(records), T, p(area), p(top), p(weights), stream_ptr()), "bs_mesh_sample_weights")
+
+
+def mesh_sample(records, cum, triangles, vertex_colors, seed, first, points, colors, normals, index):
+    """cum int64 [T]: the inclusive scan of the weights; triangles int32 [T, 3], vertex_colors fp32 [V, 3] and colors fp32 [n, 3]: all three or
+    None; points, normals fp32 [n, 3], index int32 [n]"""
+    T, n = records.shape[0], points.shape[0]
+    _mesh_records(records, T)
+    _i64(cum)
+    _i32(index)
+    _f32(points, n, 3)
+    _f32(normals, n, 3)
+    assert cum.numel() == T and index.numel() == n and (colors is None) == (vertex_colors is None)
+    n_vertices = 1
+    if colors is not None:
+        _pts(vertex_colors)
+        _f32(colors, n, 3)
+        _i32(triangles)
+        assert tuple(triangles.shape) == (T, 3)
+        n_vertices = vertex_colors.shape[0]
+    check(load_library().bs_mesh_sample(p(records), T, p(cum), p(triangles) if colors is not None else None, p(vertex_colors), n_vertices,
+                                        int(seed), int(first), n, p(points), p(colors), p(normals), p(index), stream_ptr()), "bs_mesh_sample")

@@ -42,8 +42,10 @@ struct PcMinSink {
 // that searches the grid: each record goes to sink.add(record); after a shell the search is complete when sink.bounded(lb * lb) -- what
 // the sink keeps is strictly below the bound on everything unvisited --, when every cell has been seen, or when the shell covers
 // max_distance: true.  false: the source was still searching after shell `shell_cap` (the caller finishes it some other way).
-template <typename Sink>
-__device__ __forceinline__ bool pc_walk(const f32x4* __restrict__ records, const int32_t* __restrict__ cell_start, const PcGrid& g, float sx,
+// Rec: what a cell lists -- the 16-byte point records here, int32 triangle references in mesh_scene.hip (a triangle is listed in every cell its
+// padded box overlaps, so after shell r the box of an unseen triangle is disjoint from the visited block and the bound holds for all its points).
+template <typename Sink, typename Rec = f32x4>
+__device__ __forceinline__ bool pc_walk(const Rec* __restrict__ records, const int32_t* __restrict__ cell_start, const PcGrid& g, float sx,
                                         float sy, float sz, float max_distance, int32_t shell_cap, Sink& sink) {
     const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
     const int cx = pc_cell(sx, g.lo[0], g.h, nx), cy = pc_cell(sy, g.lo[1], g.h, ny), cz = pc_cell(sz, g.lo[2], g.h, nz);

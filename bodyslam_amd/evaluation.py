@@ -638,9 +638,48 @@ def evaluate_reconstruction_aligned(pred, gt, thresholds: Sequence[float] = (0.0
     return _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, align, icp)
 
 
-def _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, align, icp) -> ReconstructionMetrics:
+GT_MESH = ("vertices", "surface")
+
+
+def evaluate_reconstruction_surface(pred, gt, thresholds: Sequence[float] = (0.001, 0.002, 0.005), transform=None,
+                                    max_distance: Optional[float] = None, align: Optional[str] = None, icp: Optional[dict] = None,
+                                    gt_mesh: str = "surface", n_gt_samples: Optional[int] = None) -> ReconstructionMetrics:
+    """evaluate_reconstruction against the SURFACE of a ground-truth mesh rather than its vertices (against a coarse scan, accuracy measured
+    to vertices is wrong by up to half an edge length).  gt_mesh="surface": gt must be a tsdf.TriangleMesh (else ValueError); accuracy is
+    pred -> surface by raycasting.RaycastingScene.compute_distance; completeness is surface samples -> pred by the nearest-neighbour query,
+    the samples being gt.sample_points_uniformly(n_gt_samples or the number of pred points, seed=0); n_gt in the result counts the
+    samples.  With align="icp" the samples and their face normals are the registration's target, so point-to-plane needs no normal
+    estimation.  The statistics are bs_pc_stats' as before.  gt_mesh="vertices" is evaluate_reconstruction_aligned(..., align, icp) itself,
+    the same bits.  (A function of its own: the parameter lists of evaluate_reconstruction and evaluate_reconstruction_aligned are pinned
+    by tests/test_pointcloud_cpu.py and tests/test_icp_cpu.py.)"""
+    return _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, align, icp, gt_mesh, n_gt_samples)
+
+
+def _check_gt_mesh(gt_mesh, gt, n_gt_samples) -> bool:
+    from .tsdf import TriangleMesh
+    if gt_mesh not in GT_MESH:
+        raise ValueError(f"unknown gt_mesh {gt_mesh!r}: one of {GT_MESH}")
+    if n_gt_samples is not None and (isinstance(n_gt_samples, bool) or not isinstance(n_gt_samples, (int, np.integer)) or
+                                     not 1 <= n_gt_samples < 2 ** 31):
+        raise ValueError(f"n_gt_samples {n_gt_samples!r}: expected None or an integer in [1, 2^31)")
+    if gt_mesh == "vertices":
+        if n_gt_samples is not None:
+            raise ValueError('n_gt_samples given without gt_mesh="surface"')
+        return False
+    if not isinstance(gt, TriangleMesh):
+        raise ValueError(f'gt_mesh="surface" needs a tsdf.TriangleMesh as gt, got {type(gt).__name__}')
+    from .raycasting import as_triangles
+    _, t = as_triangles(gt)
+    if t.shape[0] < 1 or t.shape[0] > L.MESH_MAX_SAMPLED_TRIANGLES:
+        raise ValueError(f"gt: a mesh of {t.shape[0]} triangles, expected 1 .. 2^22")
+    return True
+
+
+def _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, align, icp, gt_mesh="vertices",
+                             n_gt_samples=None) -> ReconstructionMetrics:
     from . import pointcloud as PC
     from .tsdf import MAP, TSDF
+    surface = _check_gt_mesh(gt_mesh, gt, n_gt_samples)
     taus = _check_thresholds(thresholds)
     PC._check_max_distance(max_distance)
     A = None if transform is None else PC.affine_rows(transform)
@@ -650,7 +689,7 @@ def _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, alig
         from .tsdf import PointCloud
         p_normals = pred.normals if isinstance(pred, PointCloud) else None
         g_normals = gt.normals if isinstance(gt, PointCloud) else None
-        if kw["estimation"] == "point_to_plane" and kw.get("target_normals") is None and g_normals is None:
+        if kw["estimation"] == "point_to_plane" and kw.get("target_normals") is None and g_normals is None and not surface:
             raise ValueError('icp: estimation "point_to_plane" needs target_normals (or a PointCloud gt with normals)')
     if not isinstance(pred, (TSDF, MAP)):
         p = PC.as_points(pred, "pred")
@@ -676,9 +715,20 @@ def _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, alig
             L.pc_transform(p, A, moved)
             p = moved
         p = p.to(torch.float32)
+        if surface:                                        # g: samples of the surface, with their face normals
+            g, _, g_normals, _ = PC.sample_mesh(gt.vertices, gt.triangles, n_gt_samples or int(p.shape[0]), seed=0, device=dev.index)
+            if g.shape[0] == 0:
+                raise ValueError("gt: the mesh has no triangle of positive area")
+            g, g_normals = g.to(dev), g_normals.to(dev)
         if kw is not None:
             p, alignment = _align_icp(p, g, p_normals, g_normals, A, kw, dev)
-        d_pg, _ = PC.NearestNeighbours(g).query(p, max_distance=max_distance)
+        if surface:
+            from .raycasting import RaycastingScene
+            scene = RaycastingScene(device=dev.index)
+            scene.add_triangles(gt)
+            d_pg = scene.compute_distance(p, max_distance=max_distance)
+        else:
+            d_pg, _ = PC.NearestNeighbours(g).query(p, max_distance=max_distance)
         d_gp, _ = PC.NearestNeighbours(p).query(g, max_distance=max_distance)
         ra, rc = distance_stats_record(d_pg, taus), distance_stats_record(d_gp, taus)
     acc, comp = _distance_stats(ra), _distance_stats(rc)

@@ -20,7 +20,12 @@ tests/_knn_ref.py.
 (csrc/voxel.hip: a hash table of voxel keys, integer sums, rows in order of first appearance; Open3D's PointCloud.voxel_down_sample,
 mapping_module.py:72,156,187).  Restated, parity with Open3D unpinned; the statement is tests/_voxel_ref.py.
 
-Not built: pure radius search with an unbounded list, orientation propagation, k > 32, Open3D's cubic-id trace format.
+``sample_mesh`` (TriangleMesh.sample_points_uniformly, mapping_module.py:289) draws points of a triangle mesh uniformly by area
+(csrc/mesh_scene.hip: integer weights, an integer scan, a counter-based hash -- a sample depends on (seed, its number) alone).  Restated,
+parity with Open3D unpinned; the statement is tests/_mesh_scene_ref.py.  Distances to the surface itself: bodyslam_amd/raycasting.py.
+
+Not built: pure radius search with an unbounded list, orientation propagation, k > 32, Open3D's cubic-id trace format, Poisson-disk
+sampling of a mesh.
 """
 from __future__ import annotations
 
@@ -444,6 +449,65 @@ def _voxel_status(word: int, h: float) -> None:
         raise ValueError("colors / normals: every component must be finite with |a| <= 2")
     if word:
         raise L.BodySlamHipError(f"voxel_down_sample: status {word}")
+
+
+def _check_count(n, what: str, lo: int, hi: int) -> int:
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not lo <= n < hi:
+        raise ValueError(f"{what} {n!r}: expected an integer in [{lo}, {hi})")
+    return int(n)
+
+
+def sample_mesh(vertices, triangles, number_of_points, vertex_colors=None, seed: int = 0, first: int = 0, device: int = 0):
+    """Points drawn uniformly by area from a triangle mesh: Open3D's TriangleMesh.sample_points_uniformly, which the reference runs on its
+    mesh at 3DM/mapping_module.py:289 -> (points fp32 [n, 3], colors fp32 [n, 3] or None, normals fp32 [n, 3], triangle int32 [n]), device
+    tensors.  Open3D is not vendored: the meaning is restated from its documentation and parity with Open3D is unpinned; the statement is
+    tests/_mesh_scene_ref.py, and the result is bit-equal to it.
+
+    vertices [V, 3] fp32 or fp64 (rounded to fp32 once), triangles [T, 3] integers, T <= 2^22, numpy or torch, host or device; an index
+    outside [0, V) is a ValueError.  A triangle with a non-finite vertex or a zero fp32 cross product has weight 0.  Weights are integers,
+    w = floor(area / max area 2^40) with fp64 areas, scanned exactly; sample i (numbered from `first`: a cloud may be drawn in batches,
+    each sample depends on (seed, i) alone) takes three values of a counter-based hash of (seed, i): the first picks the triangle by
+    multiply-high against the total and a bisection of the scan, the others give r1, r2 = (k + 0.5) 2^-24 and the point
+    (1 - s) A + s (1 - r2) B + s r2 C with s = sqrt(r1), in one fixed fp32 expression.  colors: the same weights on vertex_colors [V, 3];
+    normals: the unit (v1 - v0) x (v2 - v0) of the sample's triangle.  A mesh without a triangle of positive weight returns empty tensors.
+    Raises ValueError on bad arguments before any kernel runs; there is no CPU fallback."""
+    from .raycasting import as_triangles, check_indices
+    n = _check_count(number_of_points, "number_of_points", 1, 2 ** 31)
+    seed, first = _check_count(seed, "seed", 0, 2 ** 64), _check_count(first, "first", 0, 2 ** 63)
+    v, t = as_triangles(vertices, triangles)
+    if t.shape[0] > L.MESH_MAX_SAMPLED_TRIANGLES:
+        raise ValueError(f"triangles: {t.shape[0]} rows, at most 2^22 can be sampled")
+    c = _as_attribute(vertex_colors, "vertex_colors", int(v.shape[0]))
+    if not torch.cuda.is_available():
+        L.init(0)                              # raises BodySlamHipError: no CPU fallback
+    dev = v.device if v.is_cuda else torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        L.init(dev.index)
+        v, t = v.to(dev), t.to(dev)
+        check_indices(t, int(v.shape[0]))
+        v, t = v.to(torch.float32).contiguous(), t.to(torch.int32).contiguous()
+        c = None if c is None else c.to(dev).to(torch.float32).contiguous()
+        T = int(t.shape[0])
+        f = dict(dtype=torch.float32, device=dev)
+
+        def empty():
+            return (torch.empty(0, 3, **f), None if c is None else torch.empty(0, 3, **f), torch.empty(0, 3, **f),
+                    torch.empty(0, dtype=torch.int32, device=dev))
+        if T == 0:
+            return empty()
+        records = torch.empty(T, 3, 4, **f)
+        kept = torch.empty(1, dtype=torch.int32, device=dev)
+        L.mesh_records(v, t, records, kept)
+        weights = torch.empty(T, dtype=torch.int64, device=dev)
+        L.mesh_sample_weights(records, torch.empty(T, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.int64, device=dev), weights)
+        cum = torch.cumsum(weights, 0)                                       # the scan is plumbing: int64, exact (T 2^40 <= 2^62)
+        if int(cum[-1].cpu()) == 0:
+            return empty()
+        points, normals = torch.empty(n, 3, **f), torch.empty(n, 3, **f)
+        colors = None if c is None else torch.empty(n, 3, **f)
+        index = torch.empty(n, dtype=torch.int32, device=dev)
+        L.mesh_sample(records, cum, t if c is not None else None, c, seed, first, points, colors, normals, index)
+    return points, colors, normals, index
 
 
 def point_cloud_distance(source, target, cell_size: Optional[float] = None, device: int = 0, max_distance: Optional[float] = None,

@@ -125,6 +125,21 @@ class TriangleMesh:
     vertex_colors: np.ndarray               # [V, 3] float32 in [0, 1]
     triangles: np.ndarray                   # [T, 3] int32, wound so that the normal points from tsdf < 0 to tsdf > 0
 
+    def sample_points_uniformly(self, number_of_points: int, seed: int = 0, host: Optional[bool] = None):
+        """o3d.geometry.TriangleMesh.sample_points_uniformly -> (the PointCloud of number_of_points samples drawn uniformly by area -- points,
+        colours interpolated from vertex_colors with the sample's barycentric weights, normals = the unit face normal --, the int32 triangle
+        index of every sample).  host: numpy arrays (True) or device tensors (False); None: numpy for a mesh of numpy arrays.  A mesh
+        without a triangle of positive area returns an empty cloud.  pointcloud.sample_mesh states the arithmetic: a sample depends on
+        (seed, its number) alone, the same bits in every run; restated, parity with Open3D unpinned."""
+        from .pointcloud import sample_mesh
+        if host is None:
+            host = isinstance(self.vertices, np.ndarray)
+        pts, col, nrm, idx = sample_mesh(self.vertices, self.triangles, number_of_points, vertex_colors=self.vertex_colors, seed=seed)
+
+        def out(a):
+            return a.cpu().numpy() if host and a is not None else a
+        return PointCloud(out(pts), out(col), out(nrm)), out(idx)
+
 
 @dataclass
 class RaycastFrame:

@@ -760,6 +760,73 @@ int bs_pc_voxel_finish(const float* points, const float* colors, const float* no
                        const int32_t* first_index, int64_t m, const double* origin, int32_t shift, int32_t unit_normals, float* out_points,
                        float* out_colors, float* out_normals, void* stream);
 
+/* ---- triangle-mesh scene: ray casting, closest points, surface samples -----------------------------------------------------------------
+ * The bs_mesh_* launches replace Open3D's t.geometry.RaycastingScene (add_triangles, cast_rays, compute_closest_points, compute_distance)
+ * and TriangleMesh.sample_points_uniformly, which the reference calls at BodySLAM_not_refactored/3DM/mapping_module.py:204-237,289 and
+ * 3DM/synthetic_depth_generator.py:24-97.  Restated from Open3D's documented interface; parity with Open3D / Embree is UNPINNED.  The
+ * statement is tests/_mesh_scene_ref.py; the arithmetic is at the top of csrc/mesh_scene.hip, and every result is bit-equal to the statement.
+ * All pointers are device pointers.  A scene is the concatenation of its geometries: vertices fp32 [V, 3], triangles int32 [T, 3] with the
+ * indices of later geometries already offset; geom_start int32 [n_geom + 1] holds the first global triangle of every geometry and T.
+ *   bs_mesh_records        records: 3 T 16-byte words -- (v0, bit-cast global index, -1 when the triangle is not kept), (v1, 0), (v2, 0).
+ *                          Not kept: a non-finite vertex, a non-finite or zero fp32 cross product, an index outside [0, V) (the caller
+ *                          refuses those first; the kernel never reads outside `vertices`).  kept int32 [1]: how many are
+ *   bs_mesh_cast_brute     rays fp32 [*, 6] (origin, direction; the direction is not normalised); list int32 [m] of ray rows or NULL for the
+ *                          rows 0 .. m - 1; keys: m 64-bit words of scratch.  Per listed ray, the minimum of (t, global index) over the kept
+ *                          triangles: t_hit fp32 in units of |d| (+inf: a miss), geometry_ids and primitive_ids int32 (-1, the bit pattern
+ *                          0xFFFFFFFF: a miss; primitive ids are local to their geometry), primitive_uvs fp32 [*, 2] with
+ *                          p = (1 - u - v) v0 + u v1 + v v2, primitive_normals fp32 [*, 3] = the unit (v1 - v0) x (v2 - v0), not turned
+ *                          towards the ray, zero for a miss.  A ray with a non-finite component or a zero direction is a miss
+ *   bs_mesh_closest_brute  query fp32 [*, 3]; list and keys as above.  Per listed point, the minimum of (d2, global index): points fp32
+ *                          [*, 3], distance = sqrt(d2), the ids and uvs as above.  Nothing within max_distance (compared with the fp32
+ *                          distance; +inf for none), or no kept triangle: points NaN, distance +inf, ids -1, uvs 0.  A non-finite query:
+ *                          points and distance NaN, ids -1
+ *   bs_mesh_sample_weights area fp64 [T] and top (one 64-bit word) are scratch; weights int64 [T] = floor(area / max area 2^40), 0 for a
+ *                          triangle that is not kept.  The caller scans them inclusively (integers: exact): cum int64 [T]
+ *   bs_mesh_sample         samples first .. first + n - 1 of the stream `seed`: points, normals fp32 [n, 3], index int32 [n] (the global
+ *                          triangle), and colors fp32 [n, 3] from vertex_colors fp32 [V, 3] through triangles (all three NULL together).
+ *                          cum[T - 1] must be positive.  A sample depends on (seed, its number) alone
+ *   bs_mesh_grid_count / _scatter   the index: a uniform grid over lo, hi (host float [3]: the bounds of the kept triangles' vertices) with the
+ *                          point grid's cell function (bs_pc_grid_count); a kept triangle is referenced from every cell between
+ *                          cell(min - pad) and cell(max + pad) per axis.  counts int32 [cells] zeroed by the caller, who scans them; cursor: a
+ *                          copy of the exclusive scan; refs int32 [n_refs].  The order of the references in a cell is not fixed and no result
+ *                          depends on it.  pad >= 2^-9 of the largest extent + 2^-14 (max |lo|, |hi| + that extent): the bound at the top of
+ *                          csrc/mesh_scene.hip stands on it
+ *   bs_mesh_cast_grid      one thread per ray walks the cells from the ray's entry into the box (a 3-D DDA, at most nx + ny + nz + 3 steps) and
+ *                          writes bs_mesh_cast_brute's outputs, the same bits; a ray with an origin coordinate beyond origin_limit (8 times
+ *                          max |lo|, |hi| + the extent) or a direction component outside 2^-60 .. 2^60 goes onto fallback_list int32 [m]
+ *                          (fallback_count int32 [1]) for bs_mesh_cast_brute with that list
+ *   bs_mesh_closest_grid   one thread per point walks the Chebyshev shells of the point grid (pc_walk) over the references; a point still
+ *                          searching after shell_cap goes onto the list for bs_mesh_closest_brute
+ * list rows are checked against n_rows, the rows of the ray / query array.  No floating-point atomics: the same bits in every run, for every
+ * cell size.  Not built: BVHs, occlusion tests, intersection counts and lists, signed distance, occupancy. */
+#define BS_MESH_MAX_TRIANGLES 536870912         /* 2^29 */
+#define BS_MESH_MAX_SAMPLED_TRIANGLES (1 << 22)
+int bs_mesh_records(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, void* records, int32_t* kept,
+                    void* stream);
+int bs_mesh_cast_brute(const void* records, int64_t n_triangles, const float* rays, int64_t n_rows, const int32_t* list, int64_t m, void* keys,
+                       const int32_t* geom_start, int32_t n_geom, float* t_hit, int32_t* geometry_ids, int32_t* primitive_ids,
+                       float* primitive_uvs, float* primitive_normals, void* stream);
+int bs_mesh_closest_brute(const void* records, int64_t n_triangles, const float* query, int64_t n_rows, const int32_t* list, int64_t m,
+                          float max_distance,
+                          void* keys, const int32_t* geom_start, int32_t n_geom, float* points, float* distance, int32_t* geometry_ids,
+                          int32_t* primitive_ids, float* primitive_uvs, void* stream);
+int bs_mesh_grid_count(const void* records, int64_t n_triangles, const float* lo, const float* hi, float cell_size, const int32_t* dims, float pad,
+                       int32_t* counts, void* stream);
+int bs_mesh_grid_scatter(const void* records, int64_t n_triangles, const float* lo, const float* hi, float cell_size, const int32_t* dims, float pad,
+                         int32_t* cursor, int64_t n_refs, int32_t* refs, void* stream);
+int bs_mesh_cast_grid(const void* records, int64_t n_triangles, const int32_t* refs, const int32_t* cell_start, const float* lo, const float* hi,
+                      float cell_size, const int32_t* dims, float pad, float origin_limit, const float* rays, int64_t m, const int32_t* geom_start,
+                      int32_t n_geom, float* t_hit, int32_t* geometry_ids, int32_t* primitive_ids, float* primitive_uvs, float* primitive_normals,
+                      int32_t* fallback_list, int32_t* fallback_count, void* stream);
+int bs_mesh_closest_grid(const void* records, int64_t n_triangles, const int32_t* refs, const int32_t* cell_start, const float* lo, const float* hi,
+                         float cell_size, const int32_t* dims, float pad, const float* query, int64_t m, float max_distance, int32_t shell_cap,
+                         const int32_t* geom_start, int32_t n_geom, float* points, float* distance, int32_t* geometry_ids, int32_t* primitive_ids,
+                         float* primitive_uvs, int32_t* fallback_list, int32_t* fallback_count, void* stream);
+int bs_mesh_sample_weights(const void* records, int64_t n_triangles, double* area, void* top, int64_t* weights, void* stream);
+int bs_mesh_sample(const void* records, int64_t n_triangles, const int64_t* cum, const int32_t* triangles, const float* vertex_colors,
+                   int64_t n_vertices, uint64_t seed, uint64_t first, int64_t n, float* points, float* colors, float* normals, int32_t* index,
+                   void* stream);
+
 /* ---- rigid ICP registration ------------------------------------------------------------------------------------------------------------
  * bs_icp_step + bs_icp_finish replace Open3D's pipelines.registration.registration_icp with TransformationEstimationPointToPlane or
  * TransformationEstimationPointToPoint (no scale) and ICPConvergenceCriteria, and, in BS_ICP_EVALUATE mode, evaluate_registration: what
