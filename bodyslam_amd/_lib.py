@@ -190,6 +190,18 @@ _SIGS = {
                              C.c_float, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8,
     "bs_mesh_sample_weights": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_mesh_sample": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64] + [C.c_void_p] * 5,
+    # mesh topology and clean-up (csrc/mesh_ops.hip); every pointer is a device pointer
+    "bs_mesh_edge_insert": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_edge_flags": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_edge_rows": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6,
+    "bs_mesh_cc_hook": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_cc_compress": [C.c_void_p, C.c_int64, C.c_void_p],
+    "bs_mesh_cc_roots": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_mesh_cc_clusters": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_segment_sum": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_mesh_triangle_geometry": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_vertex_normals": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_mesh_laplacian_step": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p, C.c_void_p],
     # rigid ICP registration (csrc/icp.hip); lo, hi and dims are pointers to host arrays
     "bs_icp_step": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                     C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -1260,3 +1272,121 @@ def mesh_sample(records, cum, triangles, vertex_colors, seed, first, points, col
         n_vertices = vertex_colors.shape[0]
     check(load_library().bs_mesh_sample(p(records), T, p(cum), p(triangles) if colors is not None else None, p(vertex_colors), n_vertices,
                                         int(seed), int(first), n, p(points), p(colors), p(normals), p(index), stream_ptr()), "bs_mesh_sample")
+
+
+# ---- mesh topology and clean-up (csrc/mesh_ops.hip) -------------------------------------------------------------------------------------
+MESH_EDGE_EMPTY_KEY, MESH_EDGE_NO_HALF, MESH_EDGE_TABLE_FULL = -1, 0x7fffffff, 1            # (the empty key as the int64 a torch fill_ takes)
+MESH_TRIANGLE_VALID, MESH_TRIANGLE_KEPT = 1, 2
+
+
+def _tri(triangles):
+    _i32(triangles)
+    assert triangles.dim() == 2 and triangles.shape[1] == 3 and triangles.shape[0] >= 1
+    return triangles.shape[0]
+
+
+def mesh_edge_insert(triangles, n_vertices, keys, first_half, count, forward, slot_of_half, status):
+    """triangles int32 [T, 3]; keys int64 [slots] filled with MESH_EDGE_EMPTY_KEY, first_half int32 [slots] filled with MESH_EDGE_NO_HALF, count
+    and forward int32 [slots] zeroed (slots: a power of two), slot_of_half int32 [3 T], status int32 [2] zeroed: all on the device"""
+    T = _tri(triangles)
+    _i64(keys)
+    _i32(first_half, count, forward, slot_of_half, status)
+    slots = keys.numel()
+    assert first_half.numel() == slots and count.numel() == slots and forward.numel() == slots and slot_of_half.numel() == 3 * T and status.numel() >= 2
+    check(load_library().bs_mesh_edge_insert(p(triangles), T, int(n_vertices), p(keys), p(first_half), p(count), p(forward), slots, p(slot_of_half),
+                                             p(status), stream_ptr()), "bs_mesh_edge_insert")
+
+
+def mesh_edge_flags(slot_of_half, first_half, leader, is_first):
+    """slot_of_half, leader, is_first int32 [3 T], first_half int32 [slots]: all on the device"""
+    _i32(slot_of_half, first_half, leader, is_first)
+    n = slot_of_half.numel()
+    assert leader.numel() == n and is_first.numel() == n
+    check(load_library().bs_mesh_edge_flags(p(slot_of_half), p(first_half), first_half.numel(), n, p(leader), p(is_first), stream_ptr()),
+          "bs_mesh_edge_flags")
+
+
+def mesh_edge_rows(triangles, slot_of_half, count, forward, leader, rank, edges, edge_count, edge_forward, edge_first_triangle, edge_of_half):
+    """rank int32 [3 T]: the inclusive scan of is_first; edges int32 [E, 2], edge_count / edge_forward / edge_first_triangle int32 [E],
+    edge_of_half int32 [3 T]"""
+    T = _tri(triangles)
+    _i32(slot_of_half, count, forward, leader, rank, edges, edge_count, edge_forward, edge_first_triangle, edge_of_half)
+    E = edge_count.numel()
+    assert count.numel() == forward.numel() and tuple(edges.shape) == (E, 2) and edge_forward.numel() == E and edge_first_triangle.numel() == E
+    assert all(t.numel() == 3 * T for t in (slot_of_half, leader, rank, edge_of_half))
+    check(load_library().bs_mesh_edge_rows(p(triangles), T, p(slot_of_half), p(count), p(forward), count.numel(), p(leader), p(rank), E, p(edges),
+                                           p(edge_count), p(edge_forward), p(edge_first_triangle), p(edge_of_half), stream_ptr()), "bs_mesh_edge_rows")
+
+
+def mesh_cc_hook(edge_of_half, edge_first_triangle, parent, changed):
+    """edge_of_half int32 [3 T], edge_first_triangle int32 [E], parent int32 [T], changed int32 [1]"""
+    _i32(edge_of_half, edge_first_triangle, parent, changed)
+    T = parent.numel()
+    assert edge_of_half.numel() == 3 * T and changed.numel() >= 1
+    check(load_library().bs_mesh_cc_hook(p(edge_of_half), p(edge_first_triangle), T, edge_first_triangle.numel(), p(parent), p(changed), stream_ptr()),
+          "bs_mesh_cc_hook")
+
+
+def mesh_cc_compress(parent):
+    _i32(parent)
+    check(load_library().bs_mesh_cc_compress(p(parent), parent.numel(), stream_ptr()), "bs_mesh_cc_compress")
+
+
+def mesh_cc_roots(parent, edge_of_half, is_root):
+    _i32(parent, edge_of_half, is_root)
+    T = parent.numel()
+    assert edge_of_half.numel() == 3 * T and is_root.numel() == T
+    check(load_library().bs_mesh_cc_roots(p(parent), p(edge_of_half), T, p(is_root), stream_ptr()), "bs_mesh_cc_roots")
+
+
+def mesh_cc_clusters(parent, edge_of_half, rank, triangle_clusters, cluster_n_triangles):
+    """rank int32 [T]: the inclusive scan of is_root; triangle_clusters int32 [T]; cluster_n_triangles int32 [C] zeroed"""
+    _i32(parent, edge_of_half, rank, triangle_clusters, cluster_n_triangles)
+    T = parent.numel()
+    assert edge_of_half.numel() == 3 * T and rank.numel() == T and triangle_clusters.numel() == T
+    check(load_library().bs_mesh_cc_clusters(p(parent), p(edge_of_half), p(rank), T, cluster_n_triangles.numel(), p(triangle_clusters),
+                                             p(cluster_n_triangles), stream_ptr()), "bs_mesh_cc_clusters")
+
+
+def mesh_segment_sum(values, start, out):
+    """values fp64 [n], start int64 [segments + 1], out fp64 [segments]"""
+    _f64(values, out)
+    _i64(start)
+    assert start.numel() == out.numel() + 1 and out.numel() >= 1
+    check(load_library().bs_mesh_segment_sum(p(values), values.numel(), p(start), out.numel(), p(out), stream_ptr()), "bs_mesh_segment_sum")
+
+
+def mesh_triangle_geometry(vertices, triangles, flags=None, normals=None, cross=None, area=None):
+    """vertices fp32 [V, 3], triangles int32 [T, 3]; any of flags int32 [T], normals fp32 [T, 3], cross fp64 [T, 3], area fp64 [T]"""
+    _pts(vertices)
+    T = _tri(triangles)
+    _f64(cross, area)
+    if flags is not None:
+        _i32(flags)
+        assert flags.numel() == T
+    if normals is not None:
+        _f32(normals, T, 3)
+    assert (cross is None or tuple(cross.shape) == (T, 3)) and (area is None or area.numel() == T)
+    check(load_library().bs_mesh_triangle_geometry(p(vertices), vertices.shape[0], p(triangles), T, p(flags), p(normals), p(cross), p(area),
+                                                   stream_ptr()), "bs_mesh_triangle_geometry")
+
+
+def mesh_vertex_normals(cross, corner_order, vertex_start, normals):
+    """cross fp64 [T, 3], corner_order int64 [3 T], vertex_start int64 [V + 1], normals fp32 [V, 3]"""
+    _f64(cross)
+    _i64(corner_order, vertex_start)
+    _pts(normals)
+    T, V = cross.shape[0], normals.shape[0]
+    assert tuple(cross.shape) == (T, 3) and corner_order.numel() == 3 * T and vertex_start.numel() == V + 1
+    check(load_library().bs_mesh_vertex_normals(p(cross), T, p(corner_order), p(vertex_start), V, p(normals), stream_ptr()), "bs_mesh_vertex_normals")
+
+
+def mesh_laplacian_step(src, nbr_start, nbr, lam, clamp, out):
+    """src, out fp32 [V, 3] (distinct), nbr_start int64 [V + 1], nbr int32 [M]"""
+    _pts(src, out)
+    _i64(nbr_start)
+    _i32(nbr)
+    V = src.shape[0]
+    assert out.shape[0] == V and nbr_start.numel() == V + 1 and src.data_ptr() != out.data_ptr()
+    check(load_library().bs_mesh_laplacian_step(p(src), V, p(nbr_start), p(nbr) if nbr.numel() else None, nbr.numel(), float(lam), int(bool(clamp)),
+                                                p(out), stream_ptr()), "bs_mesh_laplacian_step")

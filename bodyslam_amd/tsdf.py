@@ -119,11 +119,118 @@ class PointCloud:
         return PointCloud(out(r.points), out(r.colors), out(r.normals)), out(r.row_of_point), out(r.counts)
 
 
-@dataclass
+@dataclass(init=False)
 class TriangleMesh:
     vertices: np.ndarray                    # [V, 3] float32
     vertex_colors: np.ndarray               # [V, 3] float32 in [0, 1]
     triangles: np.ndarray                   # [T, 3] int32, wound so that the normal points from tsdf < 0 to tsdf > 0
+    # (extract_mesh(host=False) fills the fields with device tensors of the same shapes and rows)
+    # The normals are two trailing optional arguments of the constructor and plain attributes, not dataclass fields: the field list is the
+    # mesh's identity (tests/test_mesh_scene_cpu.py pins it), the normals are derived from it and go stale when it changes.
+    triangle_normals = None                 # [T, 3] float32, set by compute_triangle_normals
+    vertex_normals = None                   # [V, 3] float32, set by compute_vertex_normals
+
+    def __init__(self, vertices, vertex_colors, triangles, triangle_normals=None, vertex_normals=None):
+        self.vertices, self.vertex_colors, self.triangles = vertices, vertex_colors, triangles
+        self.triangle_normals, self.vertex_normals = triangle_normals, vertex_normals
+
+    # ---- topology and clean-up: thin wrappers of bodyslam_amd/mesh.py, which states the rules; restated from Open3D's documentation, parity with
+    # Open3D unpinned.  Results are numpy for a mesh of numpy arrays and device tensors for a mesh of device tensors.  Open3D's vertex-manifold
+    # and self-intersection tests, and hence is_watertight, are not built.
+    def _host(self) -> bool:
+        return isinstance(self.vertices, np.ndarray)
+
+    def _out(self, x):
+        return x.cpu().numpy() if self._host() and isinstance(x, torch.Tensor) else x
+
+    def edge_topology(self):
+        """-> mesh.MeshEdges: the unique edges in the order of their first half-edge, the triangles on each, how many run it forward"""
+        from .mesh import MeshEdges, edge_topology
+        e = edge_topology(self.vertices, self.triangles)
+        return MeshEdges(*(self._out(x) for x in (e.edges, e.edge_count, e.edge_forward, e.edge_first_triangle, e.edge_of_half)),
+                         e.n_invalid_triangles, e.n_vertices)
+
+    def get_non_manifold_edges(self, allow_boundary_edges: bool = True):
+        """o3d get_non_manifold_edges: int32 [n, 2], the edges with more than two triangles (allow_boundary_edges=False: without exactly two)"""
+        from .mesh import edge_topology
+        return self._out(edge_topology(self.vertices, self.triangles).get_non_manifold_edges(allow_boundary_edges))
+
+    def get_boundary_edges(self):
+        """int32 [n, 2]: the edges with exactly one triangle -- the rims of the holes"""
+        from .mesh import edge_topology
+        return self._out(edge_topology(self.vertices, self.triangles).get_boundary_edges())
+
+    def is_edge_manifold(self, allow_boundary_edges: bool = True) -> bool:
+        from .mesh import edge_topology
+        return edge_topology(self.vertices, self.triangles).is_edge_manifold(allow_boundary_edges)
+
+    def is_consistently_oriented(self) -> bool:
+        """every edge of two triangles is run once in each direction (the test of the winding as it stands; is_orientable is not built)"""
+        from .mesh import edge_topology
+        return edge_topology(self.vertices, self.triangles).is_consistently_oriented()
+
+    def is_closed(self) -> bool:
+        """every edge has exactly two triangles; with is_consistently_oriented() the precondition of a signed distance (is_watertight, which
+        also wants vertex-manifoldness and no self-intersection, is not built)"""
+        from .mesh import edge_topology
+        return edge_topology(self.vertices, self.triangles).is_closed()
+
+    def cluster_connected_triangles(self):
+        """o3d cluster_connected_triangles -> (triangle_clusters int32 [T], cluster_n_triangles int32 [C], cluster_area float64 [C]); triangles
+        that share an edge are connected, clusters are numbered by their first triangle"""
+        from .mesh import cluster_connected_triangles
+        return tuple(self._out(x) for x in cluster_connected_triangles(self.vertices, self.triangles))
+
+    def get_surface_area(self) -> float:
+        from .mesh import get_surface_area
+        return get_surface_area(self.vertices, self.triangles)
+
+    def remove_triangles_by_mask(self, mask) -> "TriangleMesh":
+        """o3d remove_triangles_by_mask, returning a new mesh: the triangles whose mask is True leave, the vertices stay"""
+        from .mesh import remove_triangles_by_mask
+        return remove_triangles_by_mask(self, mask)[0]
+
+    def remove_unreferenced_vertices(self) -> "TriangleMesh":
+        """o3d remove_unreferenced_vertices, returning a new mesh"""
+        from .mesh import remove_unreferenced_vertices
+        return remove_unreferenced_vertices(self)[0]
+
+    def remove_small_components(self, min_triangles: Optional[int] = None, min_area: Optional[float] = None, keep_largest: bool = False):
+        """-> (TriangleMesh without the clusters of fewer than min_triangles triangles or less than min_area area -- keep_largest: without all
+        but the largest --, vertex_map int32 [V], triangle_map int32 [T]: the new row of every old row or -1).  Order-preserving."""
+        from .mesh import remove_small_components
+        return remove_small_components(self, min_triangles=min_triangles, min_area=min_area, keep_largest=keep_largest)
+
+    def compute_triangle_normals(self):
+        """o3d compute_triangle_normals: sets and returns ``triangle_normals``, the unit face normals (zero for a degenerate triangle)"""
+        from .mesh import compute_triangle_normals
+        self.triangle_normals = self._out(compute_triangle_normals(self.vertices, self.triangles))
+        return self.triangle_normals
+
+    def compute_vertex_normals(self):
+        """o3d compute_vertex_normals: sets and returns ``vertex_normals``, area-weighted"""
+        from .mesh import compute_vertex_normals
+        self.vertex_normals = self._out(compute_vertex_normals(self.vertices, self.triangles))
+        return self.vertex_normals
+
+    def _smoothed(self, v, c) -> "TriangleMesh":
+        return TriangleMesh(self._out(v), self.vertex_colors if c is None else self._out(c), self.triangles)
+
+    def filter_smooth_laplacian(self, number_of_iterations: int = 1, lambda_filter: float = 0.5, colors: bool = False) -> "TriangleMesh":
+        """o3d filter_smooth_laplacian -> a new mesh (normals are not carried: they would be stale); colors: smooth the vertex colours too"""
+        from .mesh import filter_smooth_laplacian
+        if not isinstance(colors, bool):
+            raise ValueError(f"colors {colors!r}: expected a bool")
+        return self._smoothed(*filter_smooth_laplacian(self.vertices, self.triangles, number_of_iterations, lambda_filter,
+                                                       vertex_colors=self.vertex_colors if colors else None))
+
+    def filter_smooth_taubin(self, number_of_iterations: int = 1, lambda_filter: float = 0.5, mu: float = -0.53, colors: bool = False) -> "TriangleMesh":
+        """o3d filter_smooth_taubin -> a new mesh: per iteration the lambda step, then the mu step"""
+        from .mesh import filter_smooth_taubin
+        if not isinstance(colors, bool):
+            raise ValueError(f"colors {colors!r}: expected a bool")
+        return self._smoothed(*filter_smooth_taubin(self.vertices, self.triangles, number_of_iterations, lambda_filter, mu,
+                                                    vertex_colors=self.vertex_colors if colors else None))
 
     def sample_points_uniformly(self, number_of_points: int, seed: int = 0, host: Optional[bool] = None):
         """o3d.geometry.TriangleMesh.sample_points_uniformly -> (the PointCloud of number_of_points samples drawn uniformly by area -- points,
@@ -425,12 +532,19 @@ class TSDF:
     def save_pcd(self, saving_path: str) -> None:
         write_ply(saving_path, self.extract_pcd())
 
-    def extract_mesh(self) -> TriangleMesh:
-        """ScalableTSDFVolume.extract_triangle_mesh(): marching cubes over every voxel cube whose eight corners carry weight"""
+    def _empty_mesh(self, host: bool) -> TriangleMesh:
+        if not host:
+            return TriangleMesh(torch.zeros(0, 3, device=self.dev), torch.zeros(0, 3, device=self.dev),
+                                torch.zeros(0, 3, dtype=torch.int32, device=self.dev))
+        return TriangleMesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
+
+    def extract_mesh(self, host: bool = True) -> TriangleMesh:
+        """ScalableTSDFVolume.extract_triangle_mesh(): marching cubes over every voxel cube whose eight corners carry weight.  host=False:
+        the TriangleMesh's fields are device tensors holding the same rows, so the mesh is cleaned where it lies (bodyslam_amd/mesh.py)."""
         from . import marching_cubes as MC
         U = self.n_units
         if U == 0:
-            return TriangleMesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
+            return self._empty_mesh(host)
         if getattr(self, "_mc_tab", None) is None:
             tab = np.concatenate([MC.TRI_TABLE.reshape(-1), np.array(MC.EDGES, dtype=np.int32).reshape(-1)]).astype(np.int32)
             self._mc_tab = torch.from_numpy(tab).to(self.dev)
@@ -443,7 +557,7 @@ class TSDF:
         counts = count.cpu().numpy().astype(np.int64)
         total = int(counts.sum())
         if total == 0:
-            return TriangleMesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
+            return self._empty_mesh(host)
         off = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)).to(self.dev)
         verts = torch.empty(3 * total, 3, device=self.dev)
         cols = torch.empty(3 * total, 3, device=self.dev)
@@ -456,6 +570,8 @@ class TSDF:
         uniq, inverse = torch.unique(keys, sorted=True, return_inverse=True)
         first = torch.full((uniq.shape[0],), keys.shape[0], dtype=torch.int64, device=self.dev)
         first.scatter_reduce_(0, inverse, torch.arange(keys.shape[0], device=self.dev), reduce="amin")      # the first corner of every vertex
+        if not host:
+            return TriangleMesh(verts[first], cols[first], inverse.view(-1, 3).to(torch.int32).contiguous())
         return TriangleMesh(verts[first].cpu().numpy(), cols[first].cpu().numpy(), inverse.view(-1, 3).to(torch.int32).cpu().numpy())
 
     def save_mesh(self, saving_path: str) -> None:
@@ -597,8 +713,8 @@ class MAP:
     def extract_pcd(self, host: bool = True) -> PointCloud:
         return self.model.extract_pcd(host=host)
 
-    def extract_mesh(self) -> TriangleMesh:
-        return self.model.extract_mesh()
+    def extract_mesh(self, host: bool = True) -> TriangleMesh:
+        return self.model.extract_mesh(host=host)
 
     def save_pcd(self, saving_path: str) -> None:
         self.model.save_pcd(saving_path)

@@ -827,6 +827,75 @@ int bs_mesh_sample(const void* records, int64_t n_triangles, const int64_t* cum,
                    int64_t n_vertices, uint64_t seed, uint64_t first, int64_t n, float* points, float* colors, float* normals, int32_t* index,
                    void* stream);
 
+/* ---- mesh topology and clean-up: edges, components, normals, smoothing -----------------------------------------------------------------
+ * These launches replace Open3D's TriangleMesh.cluster_connected_triangles, get_non_manifold_edges / is_edge_manifold,
+ * compute_triangle_normals, compute_vertex_normals, get_surface_area, filter_smooth_laplacian and filter_smooth_taubin: what everyone runs on
+ * a TSDF mesh before reporting a number.  Restated from Open3D's documented meaning; parity with Open3D is UNPINNED.  The statement is
+ * tests/_mesh_ops_ref.py, and every result is bit-equal to it.  All pointers are device pointers.  vertices fp32 [V, 3], triangles int32
+ * [T, 3], T <= BS_MESH_MAX_TRIANGLES.  A triangle is VALID when its three indices lie in [0, V) and are pairwise distinct; an invalid one
+ * takes part in nothing.  A valid triangle is KEPT under bs_mesh_records' rule (finite vertices, a finite non-zero fp32 cross product).
+ * Half-edge h = 3 t + c runs from a = tri[t][c] to b = tri[t][(c + 1) % 3]; its key is min(a, b) << 32 | max(a, b).
+ *   bs_mesh_edge_insert    one thread per half-edge of a valid triangle inserts its key into keys [slots] of 64-bit words (filled with
+ *                          BS_MESH_EDGE_EMPTY_KEY by the caller) by compare-and-swap with linear probing, then, integer atomics on the slot:
+ *                          first_half int32 [slots] (filled with BS_MESH_EDGE_NO_HALF) takes the minimum of h, count int32 [slots] (zeroed)
+ *                          one, forward int32 [slots] (zeroed) one when a < b.  slot_of_half int32 [3 T] (-1: an invalid triangle, or no
+ *                          slot).  slots: a power of two; the default is the smallest above 3 T.  After `slots` probes without a free slot or
+ *                          a match the thread sets BS_MESH_EDGE_TABLE_FULL in status[0] and gives up: no loop is unbounded.  status int32 [2]
+ *                          (zeroed by the caller); status[1] counts the invalid triangles
+ *   bs_mesh_edge_flags     leader int32 [3 T] = first_half[slot_of_half] (-1: none), is_first int32 [3 T] = (leader == h).  The caller scans
+ *                          is_first inclusively: rank int32 [3 T]; the edge led by half-edge j is row rank[j] - 1, E = rank[3 T - 1]: edges in
+ *                          the order of their first half-edge
+ *   bs_mesh_edge_rows      edges int32 [E, 2] (min, max), edge_count, edge_forward, edge_first_triangle int32 [E], edge_of_half int32 [3 T]
+ *                          (-1 for the half-edges of an invalid triangle)
+ *   bs_mesh_cc_hook        components of valid triangles that share an edge.  parent int32 [T] starts as 0 .. T - 1 and only decreases, so
+ *                          parent[x] <= x and a root walk strictly descends (at most T steps).  One thread per half-edge: the roots of its
+ *                          triangle and of its edge's first triangle; when they differ, an integer atomic minimum of the smaller root into
+ *                          the larger root's parent, and changed int32 [1] = 1
+ *   bs_mesh_cc_compress    parent[t] = root(t).  The caller repeats (zero changed, hook, compress) until changed stays 0: every round that
+ *                          reports a change turns a root into a non-root for good, so at most T rounds report one.  Then parent[t] is the
+ *                          smallest triangle index of t's component, whatever the schedule
+ *   bs_mesh_cc_roots       is_root int32 [T] = (t is valid and parent[t] == t); the caller scans it inclusively: rank int32 [T], C = rank[T - 1]
+ *   bs_mesh_cc_clusters    triangle_clusters int32 [T] = rank[parent[t]] - 1 (-1: invalid): clusters in the order of their first triangle;
+ *                          cluster_n_triangles int32 [C] (zeroed) by integer atomics
+ *   bs_mesh_segment_sum    out[s] = the sum of values[start[s] .. start[s + 1]) (fp64; start int64 [n_segments + 1]) by one wave: lane l adds
+ *                          elements l, l + 64, ... in order from +0.0, then lanes are added across by xor 32, 16, 8, 4, 2, 1.  Cluster areas
+ *                          (the areas gathered by a stable sort of the clusters) and the surface area (one segment)
+ *   bs_mesh_triangle_geometry   any of (NULL: not wanted) flags int32 [T] (BS_MESH_TRIANGLE_VALID | BS_MESH_TRIANGLE_KEPT), normals fp32 [T, 3]
+ *                          (bs_mesh_sample's unit normal, zero when not kept), cross fp64 [T, 3] (the fp64 cross product of the fp64 differences
+ *                          of the fp32 vertices, zero when not kept) and area fp64 [T] = 0.5 sqrt((nx nx + ny ny) + nz nz) of it
+ *   bs_mesh_vertex_normals corner_order int64 [3 T]: the corners 3 t + c stably sorted by vertex (those of invalid triangles last);
+ *                          vertex_start int64 [V + 1].  One thread per vertex adds `cross` of its corners' triangles in that order in fp64,
+ *                          scales by the largest |component|, normalises and rounds once: normals fp32 [V, 3], zero when the sum is zero
+ *   bs_mesh_laplacian_step one thread per vertex: mean = (the fp64 sum of in[nbr[nbr_start[v] .. nbr_start[v + 1])] in order) / count,
+ *                          out = fl32(v + lambda (mean - v)) in fp64, clamped to [0, 1] before the rounding when `clamp`; a vertex without
+ *                          neighbours is copied.  in and out fp32 [V, 3], distinct buffers
+ * No floating-point atomics and no retry loops: the same bits in every run, for every table size and every order of the atomics.  Not built:
+ * vertex-manifoldness, self-intersection and hence is_watertight, is_orientable / re-orientation, simplification, subdivision, hole filling. */
+#define BS_MESH_EDGE_EMPTY_KEY 0xffffffffffffffffull
+#define BS_MESH_EDGE_NO_HALF 0x7fffffff
+enum { BS_MESH_EDGE_TABLE_FULL = 1 };
+enum { BS_MESH_TRIANGLE_VALID = 1, BS_MESH_TRIANGLE_KEPT = 2 };
+int bs_mesh_edge_insert(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, void* keys, int32_t* first_half, int32_t* count,
+                        int32_t* forward, int64_t slots, int32_t* slot_of_half, int32_t* status, void* stream);
+int bs_mesh_edge_flags(const int32_t* slot_of_half, const int32_t* first_half, int64_t slots, int64_t n_half, int32_t* leader, int32_t* is_first,
+                       void* stream);
+int bs_mesh_edge_rows(const int32_t* triangles, int64_t n_triangles, const int32_t* slot_of_half, const int32_t* count, const int32_t* forward,
+                      int64_t slots, const int32_t* leader, const int32_t* rank, int64_t n_edges, int32_t* edges, int32_t* edge_count,
+                      int32_t* edge_forward, int32_t* edge_first_triangle, int32_t* edge_of_half, void* stream);
+int bs_mesh_cc_hook(const int32_t* edge_of_half, const int32_t* edge_first_triangle, int64_t n_triangles, int64_t n_edges, int32_t* parent,
+                    int32_t* changed, void* stream);
+int bs_mesh_cc_compress(int32_t* parent, int64_t n_triangles, void* stream);
+int bs_mesh_cc_roots(const int32_t* parent, const int32_t* edge_of_half, int64_t n_triangles, int32_t* is_root, void* stream);
+int bs_mesh_cc_clusters(const int32_t* parent, const int32_t* edge_of_half, const int32_t* rank, int64_t n_triangles, int64_t n_clusters,
+                        int32_t* triangle_clusters, int32_t* cluster_n_triangles, void* stream);
+int bs_mesh_segment_sum(const double* values, int64_t n_values, const int64_t* start, int64_t n_segments, double* out, void* stream);
+int bs_mesh_triangle_geometry(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, int32_t* flags,
+                              float* normals, double* cross, double* area, void* stream);
+int bs_mesh_vertex_normals(const double* cross, int64_t n_triangles, const int64_t* corner_order, const int64_t* vertex_start, int64_t n_vertices,
+                           float* normals, void* stream);
+int bs_mesh_laplacian_step(const float* in, int64_t n_vertices, const int64_t* nbr_start, const int32_t* nbr, int64_t n_nbr, double lambda,
+                           int32_t clamp, float* out, void* stream);
+
 /* ---- rigid ICP registration ------------------------------------------------------------------------------------------------------------
  * bs_icp_step + bs_icp_finish replace Open3D's pipelines.registration.registration_icp with TransformationEstimationPointToPlane or
  * TransformationEstimationPointToPoint (no scale) and ICPConvergenceCriteria, and, in BS_ICP_EVALUATE mode, evaluate_registration: what

@@ -1,0 +1,273 @@
+"""Numpy statement of the mesh clean-up (csrc/mesh_ops.hip, bodyslam_amd/mesh.py) -- TEST INFRASTRUCTURE ONLY.
+
+Restated from the documented meaning of Open3D's TriangleMesh.cluster_connected_triangles, remove_triangles_by_mask,
+remove_unreferenced_vertices, get_non_manifold_edges, is_edge_manifold, compute_triangle_normals, compute_vertex_normals, get_surface_area,
+filter_smooth_laplacian and filter_smooth_taubin; nothing here comes from Open3D's code or from the reference, which only calls some of
+them (3DM/mapping_module.py).  Parity with Open3D is UNPINNED.  numpy does not contract, every operation and every summation order is
+written out: the device must return these bits.
+
+Triangles.  vertices float32 [V, 3], triangles int32 [T, 3].  A triangle is VALID when its three indices lie in [0, V) and are pairwise
+distinct; an invalid one takes part in nothing (cluster -1, zero normal, zero area, no edge).  A valid triangle is KEPT under the rule of
+tests/_mesh_scene_ref.py kept_and_normals: finite coordinates and a finite non-zero float32 cross product.  Topology uses the valid
+triangles, normals and areas the kept ones.
+
+Edges.  Half-edge h = 3 t + c runs from a = tri[t][c] to b = tri[t][(c + 1) % 3]; its undirected key is (min(a, b), max(a, b)).  Unique
+edges are numbered in the order of their first (lowest) half-edge.  Per edge: count = its half-edges, forward = those with a < b,
+first_triangle = (first half-edge) // 3.
+
+Components.  Two valid triangles are connected when they share an edge (a shared vertex alone does not connect).  The label of a
+component is its smallest triangle index, the cluster id the rank of that label among all labels, ascending.
+
+Areas.  n = the float64 cross product of the float64 differences of the float32 vertices; area = 0.5 sqrt((nx nx + ny ny) + nz nz) for a
+kept triangle, 0 otherwise.  A sum of m values x[0 .. m) is wave_sum(x): lane l of 64 starts at +0.0 and adds x[l], x[l + 64], ... in
+that order; then for o = 32, 16, 8, 4, 2, 1 every lane l becomes lane[l] + lane[l ^ o] (all lanes end equal).  cluster_area sums the
+areas of a cluster's triangles in ascending triangle order, surface_area all T areas in triangle order.
+
+Vertex normals.  For every vertex the float64 n of its kept incident triangles is added per component, from +0.0, in ascending corner
+number 3 t + c; then m = max |s_a|, u = s / m, u / sqrt((ux ux + uy uy) + uz uz) in float64, rounded to float32 once; zero when s = 0.
+
+Smoothing.  The neighbours of a vertex are the other ends of the unique edges at it, ascending.  One step: mean = (the float64 sum of
+the neighbours from +0.0 in ascending order) / count, out = float32(v + lambda (mean - v)) in float64; a vertex without neighbours is
+copied.  Colours take the same step and are clamped to [0, 1] in float64 before the rounding.  Taubin: the lambda step, then the mu step.
+"""
+import numpy as np
+
+import _mesh_scene_ref as MS
+
+f32, f64, i32, i64 = np.float32, np.float64, np.int32, np.int64
+
+
+def _vt(vertices, triangles):
+    v = np.asarray(vertices).astype(f32).reshape(-1, 3)
+    t = np.asarray(triangles).astype(i64).reshape(-1, 3)
+    return v, t
+
+
+def valid_triangles(n_vertices, triangles):
+    t = np.asarray(triangles).astype(i64).reshape(-1, 3)
+    inside = ((t >= 0) & (t < n_vertices)).all(1)
+    return inside & (t[:, 0] != t[:, 1]) & (t[:, 1] != t[:, 2]) & (t[:, 2] != t[:, 0])
+
+
+# ---- edges ---------------------------------------------------------------------------------------------------------------------------------
+def edge_table(vertices, triangles):
+    """-> dict: edges int32 [E, 2] (min, max), edge_count, edge_forward, edge_first_triangle int32 [E], edge_of_half int32 [3 T] (-1 for
+    the half-edges of an invalid triangle), n_invalid int"""
+    v, t = _vt(vertices, triangles)
+    T = len(t)
+    valid = valid_triangles(len(v), t)
+    a, b = t.reshape(-1), t[:, [1, 2, 0]].reshape(-1)                      # half-edge h = 3 t + c: a -> b
+    live = np.repeat(valid, 3)
+    h = np.nonzero(live)[0]
+    lo, hi = np.minimum(a[h], b[h]), np.maximum(a[h], b[h])
+    key = (lo << 32) | hi
+    uniq, first, inverse, count = np.unique(key, return_index=True, return_inverse=True, return_counts=True)   # first: the lowest position
+    order = np.argsort(first, kind="stable")                               # edges in order of their first half-edge
+    rank = np.empty(len(uniq), i64)
+    rank[order] = np.arange(len(uniq))
+    edge_of_half = np.full(3 * T, -1, i32)
+    edge_of_half[h] = rank[inverse.reshape(-1)]
+    E = len(uniq)
+    forward = np.zeros(E, i64)
+    np.add.at(forward, rank[inverse.reshape(-1)], (a[h] < b[h]).astype(i64))
+    return dict(edges=np.stack([uniq[order] >> 32, uniq[order] & 0xFFFFFFFF], 1).astype(i32).reshape(-1, 2), edge_count=count[order].astype(i32),
+                edge_forward=forward.astype(i32), edge_first_triangle=(h[first[order]] // 3).astype(i32), edge_of_half=edge_of_half,
+                n_invalid=int(T - valid.sum()))
+
+
+def non_manifold_edges(table, allow_boundary_edges=True):
+    """the edges [n, 2] with count > 2 (allow_boundary_edges) or count != 2, in edge order"""
+    c = table["edge_count"]
+    return table["edges"][(c > 2) if allow_boundary_edges else (c != 2)]
+
+
+def boundary_edges(table):
+    return table["edges"][table["edge_count"] == 1]
+
+
+def is_edge_manifold(table, allow_boundary_edges=True):
+    return len(non_manifold_edges(table, allow_boundary_edges)) == 0
+
+
+def is_consistently_oriented(table):
+    """every edge of count 2 is run once in each direction"""
+    return bool((table["edge_forward"][table["edge_count"] == 2] == 1).all())
+
+
+def is_closed(table):
+    return bool((table["edge_count"] == 2).all())
+
+
+# ---- components ----------------------------------------------------------------------------------------------------------------------------
+def component_labels(table, n_triangles):
+    """label int64 [T]: the smallest triangle index of the triangle's component (its own index for an invalid triangle)"""
+    parent = list(range(n_triangles))
+
+    def root(x):
+        while parent[x] != x:
+            x = parent[x]
+        return x
+    eoh, eft = table["edge_of_half"], table["edge_first_triangle"]
+    for h in np.nonzero(eoh >= 0)[0]:
+        r, s = root(int(h) // 3), root(int(eft[eoh[h]]))
+        if r != s:
+            parent[max(r, s)] = min(r, s)
+    return np.array([root(x) for x in range(n_triangles)], i64).reshape(-1)
+
+
+def wave_sum(x):
+    x = np.asarray(x, f64)
+    lanes = np.zeros(64, f64)
+    for start in range(0, len(x), 64):                                     # lane l: x[l], x[l + 64], ... in order
+        part = x[start:start + 64]
+        lanes[:len(part)] = lanes[:len(part)] + part
+    for o in (32, 16, 8, 4, 2, 1):
+        lanes = lanes + lanes[np.arange(64) ^ o]
+    return lanes[0]
+
+
+def triangle_geometry(vertices, triangles):
+    """-> (valid bool [T], kept bool [T], unit normals float32 [T, 3], n float64 [T, 3], area float64 [T]); zero where not kept"""
+    v, t = _vt(vertices, triangles)
+    valid = valid_triangles(len(v), t)
+    ts = np.where(valid[:, None], t, 0)
+    v0, v1, v2 = (v[ts[:, k]] for k in range(3)) if len(v) else (np.zeros((len(t), 3), f32),) * 3
+    kept, unit = MS.kept_and_normals(v0, v1, v2)
+    kept = kept & valid
+    a, b, c = v0.astype(f64), v1.astype(f64), v2.astype(f64)
+    with np.errstate(all="ignore"):
+        n = MS._cross(b - a, c - a)
+        area = 0.5 * np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+    return (valid, kept, np.where(kept[:, None], unit, f32(0)).astype(f32), np.where(kept[:, None], n, 0.0),
+            np.where(kept, area, 0.0))
+
+
+def cluster_connected_triangles(vertices, triangles):
+    """-> (triangle_clusters int32 [T] (-1: invalid), cluster_n_triangles int32 [C], cluster_area float64 [C])"""
+    v, t = _vt(vertices, triangles)
+    T = len(t)
+    table = edge_table(v, t)
+    valid = valid_triangles(len(v), t)
+    label = component_labels(table, T)
+    roots = np.nonzero(valid & (label == np.arange(T)))[0]                 # ascending: cluster id = rank of the label
+    cluster = np.where(valid, np.searchsorted(roots, label), -1).astype(i32)
+    area = triangle_geometry(v, t)[4]
+    n_tri = np.array([(cluster == c).sum() for c in range(len(roots))], i32).reshape(-1)
+    c_area = np.array([wave_sum(area[cluster == c]) for c in range(len(roots))], f64).reshape(-1)
+    return cluster, n_tri, c_area
+
+
+def surface_area(vertices, triangles):
+    return f64(wave_sum(triangle_geometry(vertices, triangles)[4]))
+
+
+# ---- normals -------------------------------------------------------------------------------------------------------------------------------
+def triangle_normals(vertices, triangles):
+    return triangle_geometry(vertices, triangles)[2]
+
+
+def vertex_normals(vertices, triangles):
+    v, t = _vt(vertices, triangles)
+    valid, kept, _, n, _ = triangle_geometry(v, t)
+    s = np.zeros((len(v), 3), f64)
+    for tri in np.nonzero(kept)[0]:                                        # ascending corner number: ascending triangle, then corner
+        for c in range(3):
+            s[t[tri, c]] = s[t[tri, c]] + n[tri]
+    with np.errstate(all="ignore"):
+        m = np.maximum(np.maximum(np.abs(s[:, 0]), np.abs(s[:, 1])), np.abs(s[:, 2]))
+        u = s / m[:, None]
+        u = u / np.sqrt((u[:, 0] * u[:, 0] + u[:, 1] * u[:, 1]) + u[:, 2] * u[:, 2])[:, None]
+    return np.where((m > 0)[:, None], u, 0.0).astype(f32)
+
+
+# ---- smoothing -----------------------------------------------------------------------------------------------------------------------------
+def adjacency(table, n_vertices):
+    """-> (start int64 [V + 1], neighbours int32 [2 E]): both directions of every unique edge, sorted by (a, b)"""
+    e = table["edges"].astype(i64)
+    a, b = np.concatenate([e[:, 0], e[:, 1]]), np.concatenate([e[:, 1], e[:, 0]])
+    o = np.argsort((a << 32) | b, kind="stable")
+    start = np.concatenate([[0], np.cumsum(np.bincount(a, minlength=n_vertices))]).astype(i64)
+    return start, b[o].astype(i32)
+
+
+def laplacian_step(x, start, nbr, lam, clamp=False):
+    x = np.asarray(x).astype(f32)
+    out = x.copy()
+    for i in range(len(x)):
+        k = int(start[i + 1] - start[i])
+        if k == 0:
+            continue
+        s = np.zeros(3, f64)
+        for j in nbr[start[i]:start[i + 1]]:
+            s = s + x[j].astype(f64)
+        with np.errstate(all="ignore"):
+            mean = s / f64(k)
+            y = x[i].astype(f64) + f64(lam) * (mean - x[i].astype(f64))
+            if clamp:
+                y = np.where(y < 0.0, 0.0, np.where(y > 1.0, 1.0, y))
+            out[i] = y.astype(f32)
+    return out
+
+
+def filter_smooth(vertices, triangles, iterations, steps, vertex_colors=None):
+    """steps: the factors of one iteration -- (lambda,) for Laplacian, (lambda, mu) for Taubin -> (vertices, colours or None)"""
+    v, t = _vt(vertices, triangles)
+    start, nbr = adjacency(edge_table(v, t), len(v))
+    c = None if vertex_colors is None else np.asarray(vertex_colors).astype(f32)
+    for _ in range(iterations):
+        for lam in steps:
+            v = laplacian_step(v, start, nbr, lam)
+            if c is not None:
+                c = laplacian_step(c, start, nbr, lam, clamp=True)
+    return v, c
+
+
+def filter_smooth_laplacian(vertices, triangles, number_of_iterations=1, lambda_filter=0.5, vertex_colors=None):
+    return filter_smooth(vertices, triangles, number_of_iterations, (lambda_filter,), vertex_colors)
+
+
+def filter_smooth_taubin(vertices, triangles, number_of_iterations=1, lambda_filter=0.5, mu=-0.53, vertex_colors=None):
+    return filter_smooth(vertices, triangles, number_of_iterations, (lambda_filter, mu), vertex_colors)
+
+
+# ---- removal -------------------------------------------------------------------------------------------------------------------------------
+def remove_triangles_by_mask(triangles, mask):
+    """the rows whose mask is False, in their order -> (triangles, triangle_map int32 [T]: the new row of every old row or -1)"""
+    t = np.asarray(triangles).reshape(-1, 3)
+    keep = ~np.asarray(mask, bool)
+    tmap = np.where(keep, np.cumsum(keep) - 1, -1).astype(i32)
+    return t[keep], tmap
+
+
+def remove_unreferenced_vertices(n_vertices, triangles):
+    """-> (kept vertex rows int64 ascending, triangles re-indexed, vertex_map int32 [V]); a vertex is referenced when an index of any
+    triangle names it; an index outside [0, V) stays as it is"""
+    t = np.asarray(triangles).astype(i64).reshape(-1, 3)
+    inside = (t >= 0) & (t < n_vertices)
+    used = np.zeros(n_vertices, bool)
+    used[t[inside]] = True
+    vmap = np.where(used, np.cumsum(used) - 1, -1).astype(i32)
+    new_t = np.where(inside, vmap[np.where(inside, t, 0)] if n_vertices else t, t).astype(i32)
+    return np.nonzero(used)[0], new_t, vmap
+
+
+def small_component_mask(clusters, n_tri, area, min_triangles=None, min_area=None, keep_largest=False):
+    """True for the triangles to remove: the invalid ones, and those of a cluster with fewer than min_triangles triangles or less than
+    min_area area; keep_largest: every cluster but the one of most triangles (the lowest id among equals)"""
+    drop = np.zeros(len(n_tri), bool)
+    if min_triangles is not None:
+        drop |= n_tri < min_triangles
+    if min_area is not None:
+        drop |= area < min_area
+    if keep_largest and len(n_tri):
+        drop |= np.arange(len(n_tri)) != int(np.argmax(n_tri))                 # the first maximum
+    return np.where(clusters >= 0, drop[np.maximum(clusters, 0)] if len(n_tri) else True, True)
+
+
+def remove_small_components(vertices, triangles, min_triangles=None, min_area=None, keep_largest=False):
+    """-> (vertices, triangles, vertex_map, triangle_map), order-preserving"""
+    v, t = _vt(vertices, triangles)
+    cl, n_tri, area = cluster_connected_triangles(v, t)
+    t1, tmap = remove_triangles_by_mask(t.astype(i32), small_component_mask(cl, n_tri, area, min_triangles, min_area, keep_largest))
+    rows, t2, vmap = remove_unreferenced_vertices(len(v), t1)
+    return v[rows], t2, vmap, tmap
