@@ -4,10 +4,10 @@
 // Open3D's documented meaning; parity with Open3D is UNPINNED.  The statement is tests/_mesh_ops_ref.py, DESIGN section 3.21 the argument.
 //
 //   edge_insert   one thread per half-edge h = 3 t + c (a = tri[t][c] -> b = tri[t][(c + 1) % 3]) of a valid triangle inserts the key
-//                 min(a, b) << 32 | max(a, b) into an open-addressing table of 64-bit keys -- the probe loop of csrc/voxel.hip, a local copy:
-//                 that one is interleaved with the voxel's own `first` rule --, then three integer atomics on the slot: the minimum of h, the
-//                 count, and the count of half-edges with a < b.  The loop ends after `slots` probes with BS_MESH_EDGE_TABLE_FULL.
-//   edge_flags    leader[h] = first_half[slot_h], is_first[h] = (leader[h] == h); the caller's inclusive scan of is_first is the edge's rank:
+//                 min(a, b) << 32 | max(a, b) into the open-addressing table of 64-bit keys of slot_table.h (slot_insert: the table voxel.hip
+//                 uses too), then three integer atomics on the slot: the minimum of h, the count, and the count of half-edges with a < b.
+//                 A table without room after `slots` probes sets BS_MESH_EDGE_TABLE_FULL.
+//   edge_flags    slot_table.h's flags kernel: leader[h] = first_half[slot_h], is_first[h] = (leader[h] == h); the caller's inclusive scan of is_first is the edge's rank:
 //                 edges are numbered in the order of their first half-edge, whatever slot they got.
 //   edge_rows     one thread per half-edge writes edge_of_half; the first half-edge of an edge writes the edge's row.
 //   cc_hook       one thread per half-edge: the roots of its triangle and of its edge's first triangle; when they differ, atomicMin of the
@@ -19,8 +19,8 @@
 //   cc_roots / cc_clusters   is_root flags for the caller's scan; cluster = rank of the root - 1, the sizes by integer atomics (one per distinct
 //                 cluster of a wave).
 //   segment_sum   one wave per segment of an fp64 array, reduce.h's column_sum order: cluster areas and the surface area.
-//   triangle_geometry   validity, the kept rule and unit normal of csrc/mesh_scene.hip (the same fp32 expressions), the fp64 cross product
-//                 and area.
+//   triangle_geometry   triangle.h, the functions mesh_scene.hip calls too: validity, the fp32 cross product with the kept rule, the unit
+//                 normal, the fp64 cross product and area.
 //   vertex_normals      one thread per vertex adds the fp64 cross products of its corners in ascending corner number (the caller's stable
 //                 sort of the corners by vertex): the store-then-sum-per-destination form, no float atomics.
 //   laplacian_step      one thread per vertex gathers its neighbours (CSR, ascending) in fp64 and writes a second buffer.
@@ -30,26 +30,14 @@
 #include "common.h"
 #include "pc_grid.h"
 #include "reduce.h"
+#include "slot_table.h"
+#include "triangle.h"
 
 namespace bs {
 namespace {
 
 constexpr int MO_THREADS = 256;
-typedef unsigned long long edge_key;
-constexpr edge_key EDGE_EMPTY = BS_MESH_EDGE_EMPTY_KEY;
-
-__device__ __forceinline__ edge_key edge_mix(edge_key x) {             // (which slot a key starts at changes the time only)
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-
-// the three indices of triangle t; true when it is valid
-__device__ __forceinline__ bool mo_triangle(const int32_t* __restrict__ triangles, int64_t t, int64_t n_vertices, int32_t (&v)[3]) {
-    v[0] = triangles[3 * t]; v[1] = triangles[3 * t + 1]; v[2] = triangles[3 * t + 2];
-    return v[0] >= 0 && v[0] < n_vertices && v[1] >= 0 && v[1] < n_vertices && v[2] >= 0 && v[2] < n_vertices && v[0] != v[1] && v[1] != v[2] &&
-           v[2] != v[0];
-}
+typedef slot_key edge_key;
 
 __global__ void __launch_bounds__(MO_THREADS) edge_insert_kernel(const int32_t* __restrict__ triangles, int64_t n_triangles, int64_t n_vertices,
                                                                  edge_key* __restrict__ keys, int32_t* __restrict__ first_half,
@@ -61,17 +49,9 @@ __global__ void __launch_bounds__(MO_THREADS) edge_insert_kernel(const int32_t* 
     const int c = (int)(h - 3 * t);
     int32_t v[3];
     int32_t found = -1;
-    if (mo_triangle(triangles, t, n_vertices, v)) {
+    if (tri_indices(triangles, t, n_vertices, v)) {
         const int32_t a = v[c], b = v[c == 2 ? 0 : c + 1];
-        const edge_key key = ((edge_key)(a < b ? a : b) << 32) | (edge_key)(a < b ? b : a);
-        const edge_key mask = (edge_key)slots - 1;
-        edge_key slot = edge_mix(key) & mask;
-        for (int64_t probe = 0; probe < slots; ++probe) {
-            edge_key cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == EDGE_EMPTY) cur = atomicCAS(&keys[slot], EDGE_EMPTY, key);
-            if (cur == EDGE_EMPTY || cur == key) { found = (int32_t)slot; break; }
-            slot = (slot + 1) & mask;
-        }
+        found = slot_insert(keys, slots, ((edge_key)(a < b ? a : b) << 32) | (edge_key)(a < b ? b : a));
         if (found < 0) {
             atomicOr(&status[0], BS_MESH_EDGE_TABLE_FULL);
         } else {
@@ -83,17 +63,6 @@ __global__ void __launch_bounds__(MO_THREADS) edge_insert_kernel(const int32_t* 
         atomicAdd(&status[1], 1);
     }
     slot_of_half[h] = found;
-}
-
-__global__ void __launch_bounds__(MO_THREADS) edge_flags_kernel(const int32_t* __restrict__ slot_of_half, const int32_t* __restrict__ first_half,
-                                                                int64_t slots, int64_t n_half, int32_t* __restrict__ leader,
-                                                                int32_t* __restrict__ is_first) {
-    const int64_t h = (int64_t)blockIdx.x * MO_THREADS + threadIdx.x;
-    if (h >= n_half) return;
-    const int32_t slot = slot_of_half[h];
-    const int32_t ld = slot >= 0 && slot < slots ? first_half[slot] : -1;
-    leader[h] = ld;
-    is_first[h] = ld == (int32_t)h ? 1 : 0;
 }
 
 __global__ void __launch_bounds__(MO_THREADS) edge_rows_kernel(const int32_t* __restrict__ triangles, int64_t n_triangles,
@@ -228,7 +197,7 @@ __global__ void __launch_bounds__(MO_THREADS) triangle_geometry_kernel(const flo
     const int64_t t = (int64_t)blockIdx.x * MO_THREADS + threadIdx.x;
     if (t >= n_triangles) return;
     int32_t idx[3];
-    const bool valid = mo_triangle(triangles, t, n_vertices, idx);
+    const bool valid = tri_indices(triangles, t, n_vertices, idx);
     float p[3][3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -236,34 +205,19 @@ __global__ void __launch_bounds__(MO_THREADS) triangle_geometry_kernel(const flo
 #pragma unroll
         for (int a = 0; a < 3; ++a) p[k][a] = vertices[3 * j + a];
     }
-    // the kept rule and the unit normal of csrc/mesh_scene.hip (ms_cross, ms_unit_normal), the same fp32 expressions
-    const float e1x = p[1][0] - p[0][0], e1y = p[1][1] - p[0][1], e1z = p[1][2] - p[0][2];
-    const float e2x = p[2][0] - p[0][0], e2y = p[2][1] - p[0][1], e2z = p[2][2] - p[0][2];
-    const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
-    bool kept = valid && pc_finite(nx) && pc_finite(ny) && pc_finite(nz) && (nx != 0.0f || ny != 0.0f || nz != 0.0f);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) kept = kept && pc_finite(p[k][0]) && pc_finite(p[k][1]) && pc_finite(p[k][2]);
+    float n32[3];
+    const bool kept = tri_cross(p[0], p[1], p[2], n32) && valid;
     if (flags) flags[t] = (valid ? BS_MESH_TRIANGLE_VALID : 0) | (kept ? BS_MESH_TRIANGLE_KEPT : 0);
     if (normals) {
         float u[3] = {0.0f, 0.0f, 0.0f};
-        if (kept) {
-            const float m = fmaxf(fmaxf(fabsf(nx), fabsf(ny)), fabsf(nz));
-            const float sx = __fdiv_rn(nx, m), sy = __fdiv_rn(ny, m), sz = __fdiv_rn(nz, m);
-            const float len = sqrtf((sx * sx + sy * sy) + sz * sz);
-            u[0] = __fdiv_rn(sx, len); u[1] = __fdiv_rn(sy, len); u[2] = __fdiv_rn(sz, len);
-        }
+        if (kept) tri_unit(n32, u);
         normals[3 * t] = u[0]; normals[3 * t + 1] = u[1]; normals[3 * t + 2] = u[2];
     }
     if (cross || area) {
         double n[3] = {0.0, 0.0, 0.0}, ar = 0.0;
         if (kept) {
-            const double ax = p[0][0], ay = p[0][1], az = p[0][2];
-            const double d1x = (double)p[1][0] - ax, d1y = (double)p[1][1] - ay, d1z = (double)p[1][2] - az;
-            const double d2x = (double)p[2][0] - ax, d2y = (double)p[2][1] - ay, d2z = (double)p[2][2] - az;
-            n[0] = d1y * d2z - d1z * d2y;
-            n[1] = d1z * d2x - d1x * d2z;
-            n[2] = d1x * d2y - d1y * d2x;
-            ar = 0.5 * sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+            tri_cross64(p[0], p[1], p[2], n);
+            ar = tri_area64(n);
         }
         if (cross) { cross[3 * t] = n[0]; cross[3 * t + 1] = n[1]; cross[3 * t + 2] = n[2]; }
         if (area) area[t] = ar;
@@ -361,7 +315,7 @@ extern "C" int bs_mesh_edge_flags(const int32_t* slot_of_half, const int32_t* fi
     BS_REQUIRE(slot_of_half && first_half && leader && is_first, "bs_mesh_edge_flags: null pointer");
     BS_REQUIRE(n_half >= 1 && n_half < ((int64_t)1 << 31) && slots >= 1, "bs_mesh_edge_flags: n = %lld, slots = %lld", (long long)n_half,
                (long long)slots);
-    hipLaunchKernelGGL(edge_flags_kernel, mo_grid(n_half), dim3(MO_THREADS), 0, st, slot_of_half, first_half, slots, n_half, leader, is_first);
+    slot_flags_launch(slot_of_half, first_half, slots, n_half, leader, is_first, st);
     BS_CHECK_LAUNCH();
     return BS_OK;
 }

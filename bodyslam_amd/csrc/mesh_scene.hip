@@ -6,7 +6,8 @@
 //
 // Arithmetic (fp32, no contraction, every division and square root correctly rounded -- sqrtf, not __fsqrt_rn, which is the native
 // approximation in this toolchain; the whole feature follows from it).
-//   triangle    global index = its row in the concatenation of the scene's geometries.  e1 = v1 - v0, e2 = v2 - v0,
+//   triangle    (triangle.h: tri_cross, tri_unit_normal, tri_cross64, tri_area64 -- the functions mesh_ops.hip's triangle geometry calls too)
+//               global index = its row in the concatenation of the scene's geometries.  e1 = v1 - v0, e2 = v2 - v0,
 //               n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x); KEPT when the nine coordinates and n are finite and n != 0,
 //               the others are in no result.  Unit normal: m = max |n_a|, s = n / m, s / sqrt((sx sx + sy sy) + sz sz)
 //   ray         (Woop, Benthin, Wald, "Watertight Ray/Triangle Intersection", JCGT 2013, restated)  kz = the first axis of largest |d|,
@@ -83,32 +84,12 @@
 
 #include "common.h"
 #include "pc_grid.h"
+#include "triangle.h"
 
 namespace bs {
 namespace {
 
 constexpr int MS_THREADS = 256, MS_RAYS = 64, MS_WAVES = MS_THREADS / 64, MS_TILE = 256;      // tile: 256 triangles = 768 records = 12 KB
-
-__device__ __forceinline__ bool ms_finite3(const f32x4 p) { return pc_finite(p[0]) && pc_finite(p[1]) && pc_finite(p[2]); }
-
-// n = (b - a) x (c - a) as written at the top; true when the triangle is kept
-__device__ __forceinline__ bool ms_cross(const f32x4 a, const f32x4 b, const f32x4 c, float (&n)[3]) {
-    const float e1x = b[0] - a[0], e1y = b[1] - a[1], e1z = b[2] - a[2], e2x = c[0] - a[0], e2y = c[1] - a[1], e2z = c[2] - a[2];
-    n[0] = e1y * e2z - e1z * e2y;
-    n[1] = e1z * e2x - e1x * e2z;
-    n[2] = e1x * e2y - e1y * e2x;
-    return ms_finite3(a) && ms_finite3(b) && ms_finite3(c) && pc_finite(n[0]) && pc_finite(n[1]) && pc_finite(n[2]) &&
-           (n[0] != 0.0f || n[1] != 0.0f || n[2] != 0.0f);
-}
-
-__device__ __forceinline__ void ms_unit_normal(const f32x4 a, const f32x4 b, const f32x4 c, float (&u)[3]) {
-    float n[3];
-    ms_cross(a, b, c, n);
-    const float m = fmaxf(fmaxf(fabsf(n[0]), fabsf(n[1])), fabsf(n[2]));
-    const float sx = __fdiv_rn(n[0], m), sy = __fdiv_rn(n[1], m), sz = __fdiv_rn(n[2], m);
-    const float len = sqrtf((sx * sx + sy * sy) + sz * sz);
-    u[0] = __fdiv_rn(sx, len); u[1] = __fdiv_rn(sy, len); u[2] = __fdiv_rn(sz, len);
-}
 
 // ---- rays ----------------------------------------------------------------------------------------------------------------------------------
 struct MsRay {
@@ -247,7 +228,7 @@ __global__ void __launch_bounds__(MS_THREADS) ms_records_kernel(const float* __r
         p[k] = f32x4{vertices[3 * jj], vertices[3 * jj + 1], vertices[3 * jj + 2], 0.0f};
     }
     float n[3];
-    keep = ms_cross(p[0], p[1], p[2], n) && keep;
+    keep = tri_cross(p[0], p[1], p[2], n) && keep;
     p[0][3] = __int_as_float(keep ? (int32_t)i : -1);
     records[3 * i] = p[0];
     records[3 * i + 1] = p[1];
@@ -336,7 +317,7 @@ __device__ __forceinline__ void ms_cast_write(const f32x4* __restrict__ records,
         if (ray.ok && ms_ray_tri(ray, a, b, c, t, u, v)) {
             geom = ms_geometry(geom_start, n_geom, (int32_t)gi);
             prim = (int32_t)gi - geom_start[geom];
-            ms_unit_normal(a, b, c, n);
+            tri_unit_normal(a, b, c, n);
         } else {
             t = INFINITY; u = 0.0f; v = 0.0f;
         }
@@ -534,19 +515,17 @@ __global__ void __launch_bounds__(MS_THREADS) ms_closest_grid_kernel(const f32x4
 }
 
 // ---- sampling ------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double ms_area(const f32x4 a, const f32x4 b, const f32x4 c) {
-    const double e1x = (double)b[0] - (double)a[0], e1y = (double)b[1] - (double)a[1], e1z = (double)b[2] - (double)a[2];
-    const double e2x = (double)c[0] - (double)a[0], e2y = (double)c[1] - (double)a[1], e2z = (double)c[2] - (double)a[2];
-    const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
-    return 0.5 * sqrt((nx * nx + ny * ny) + nz * nz);
-}
-
 __global__ void __launch_bounds__(MS_THREADS) ms_area_kernel(const f32x4* __restrict__ records, int64_t n_triangles, double* __restrict__ area,
                                                              unsigned long long* __restrict__ top) {
     const int64_t i = (int64_t)blockIdx.x * MS_THREADS + threadIdx.x;
     if (i >= n_triangles) return;
     const f32x4 a = records[3 * i];
-    const double s = __float_as_int(a[3]) >= 0 ? ms_area(a, records[3 * i + 1], records[3 * i + 2]) : 0.0;
+    double s = 0.0;
+    if (__float_as_int(a[3]) >= 0) {
+        double n[3];
+        tri_cross64(a, records[3 * i + 1], records[3 * i + 2], n);
+        s = tri_area64(n);
+    }
     area[i] = s;
     if (s > 0.0) atomicMax(top, (unsigned long long)__double_as_longlong(s));       // (a kept triangle's area is finite)
 }
@@ -590,7 +569,7 @@ __global__ void __launch_bounds__(MS_THREADS) ms_sample_kernel(const f32x4* __re
 #pragma unroll
     for (int d = 0; d < 3; ++d) points[3 * k + d] = (wa * a[d] + wb * b[d]) + wc * c[d];
     float nrm[3];
-    ms_unit_normal(a, b, c, nrm);
+    tri_unit_normal(a, b, c, nrm);
 #pragma unroll
     for (int d = 0; d < 3; ++d) normals[3 * k + d] = nrm[d];
     index[k] = (int32_t)lo;

@@ -4,14 +4,14 @@
 // The statement is tests/_voxel_ref.py.
 //
 // Four launches, nothing but stream order between them:
-//   assign      one thread per point: v = floor(((double) p - o) / h) per axis, key = vz << 42 | vy << 21 | vx, inserted into an open-addressing
-//               table of 64-bit keys (linear probing from a mixed hash; atomicCAS on the key, atomicMin of the point index on the slot's
-//               `first`).  A slot goes from EMPTY to its key once and never changes again, so a relaxed load that shows a key other than
+//   assign      one thread per point: v = floor(((double) p - o) / h) per axis, key = vz << 42 | vy << 21 | vx, inserted into the open-addressing
+//               table of 64-bit keys of slot_table.h (slot_insert, shared with mesh_ops.hip: linear probing from a mixed hash, atomicCAS on
+//               the key), then atomicMin of the point index on the slot's `first`.  A slot goes from EMPTY to its key once and never changes again, so a relaxed load that shows a key other than
 //               EMPTY is final: only an EMPTY slot needs the CAS.  `first` only decreases, so a relaxed load at or below the point's index
 //               saves the atomicMin: at h = 0.05 m a voxel of the 1 mm map holds thousands of points and nearly all of them skip it.
 //               The probe loop ends after `slots` probes with the status bit BS_PC_VOXEL_TABLE_FULL: a full table costs an error, never
 //               a spinning wave.
-//   flags       leader[i] = first[slot_i], is_first[i] = (leader[i] == i).  The caller's inclusive scan of is_first (integer, exact) is the
+//   flags       slot_table.h's flags kernel: leader[i] = first[slot_i], is_first[i] = (leader[i] == i).  The caller's inclusive scan of is_first (integer, exact) is the
 //               rank: the voxel led by point j has row rank[j] - 1 -- first appearance order, whatever slot the voxel got.
 //   accumulate  one thread per point adds its 3, 6 or 9 int64 terms Q and a count to its row with 64-bit integer atomics.  Integer addition
 //               is associative, so any pre-summing is exact: a run of adjacent lanes with the same row (clouds from depth images and from
@@ -24,22 +24,16 @@
 
 #include "common.h"
 #include "pc_grid.h"
+#include "slot_table.h"
 
 namespace bs {
 namespace {
 
 constexpr int VOXEL_THREADS = 256;
 constexpr int VOXEL_ATTR_SHIFT = 30;
-typedef unsigned long long voxel_key;
-constexpr voxel_key VOXEL_EMPTY = BS_PC_VOXEL_EMPTY_KEY;
+typedef slot_key voxel_key;
 
 struct VoxelOrigin { double o[3]; };
-
-__device__ __forceinline__ voxel_key voxel_mix(voxel_key x) {          // (which slot a key starts at changes the time only)
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
 
 __global__ void __launch_bounds__(VOXEL_THREADS) voxel_assign_kernel(const float* __restrict__ pts, int64_t n, VoxelOrigin org, double h,
                                                                      voxel_key* __restrict__ keys, int32_t* __restrict__ first, int64_t slots,
@@ -52,15 +46,7 @@ __global__ void __launch_bounds__(VOXEL_THREADS) voxel_assign_kernel(const float
         const double limit = (double)(1 << BS_PC_VOXEL_AXIS_BITS);
         const double vx = floor(((double)x - org.o[0]) / h), vy = floor(((double)y - org.o[1]) / h), vz = floor(((double)z - org.o[2]) / h);
         if (vx >= 0.0 && vx < limit && vy >= 0.0 && vy < limit && vz >= 0.0 && vz < limit) {
-            const voxel_key key = ((voxel_key)vz << 42) | ((voxel_key)vy << 21) | (voxel_key)vx;
-            const voxel_key mask = (voxel_key)slots - 1;
-            voxel_key slot = voxel_mix(key) & mask;
-            for (int64_t probe = 0; probe < slots; ++probe) {
-                voxel_key cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == VOXEL_EMPTY) cur = atomicCAS(&keys[slot], VOXEL_EMPTY, key);
-                if (cur == VOXEL_EMPTY || cur == key) { found = (int32_t)slot; break; }
-                slot = (slot + 1) & mask;
-            }
+            found = slot_insert(keys, slots, ((voxel_key)vz << 42) | ((voxel_key)vy << 21) | (voxel_key)vx);
             if (found < 0) {
                 atomicOr(status, BS_PC_VOXEL_TABLE_FULL);
             } else if (__hip_atomic_load(&first[found], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (int32_t)i) {
@@ -72,17 +58,6 @@ __global__ void __launch_bounds__(VOXEL_THREADS) voxel_assign_kernel(const float
         }
     }
     slot_of_point[i] = found;
-}
-
-__global__ void __launch_bounds__(VOXEL_THREADS) voxel_flags_kernel(const int32_t* __restrict__ slot_of_point, const int32_t* __restrict__ first,
-                                                                    int64_t slots, int64_t n, int32_t* __restrict__ leader,
-                                                                    int32_t* __restrict__ is_first) {
-    const int64_t i = (int64_t)blockIdx.x * VOXEL_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const int32_t slot = slot_of_point[i];
-    const int32_t ld = slot >= 0 && slot < slots ? first[slot] : -1;
-    leader[i] = ld;
-    is_first[i] = ld == (int32_t)i ? 1 : 0;
 }
 
 // Q of an attribute component; false when it is not finite with |a| <= 2
@@ -230,8 +205,7 @@ extern "C" int bs_pc_voxel_flags(const int32_t* slot_of_point, const int32_t* fi
     BS_REQUIRE(slot_of_point && first && leader && is_first, "bs_pc_voxel_flags: null pointer");
     BS_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && slots >= 1, "bs_pc_voxel_flags: n = %lld, slots = %lld", (long long)n, (long long)slots);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(voxel_flags_kernel, dim3((unsigned)cdiv64(n, VOXEL_THREADS)), dim3(VOXEL_THREADS), 0, st, slot_of_point, first, slots, n, leader,
-                       is_first);
+    slot_flags_launch(slot_of_point, first, slots, n, leader, is_first, st);
     BS_CHECK_LAUNCH();
     return BS_OK;
 }

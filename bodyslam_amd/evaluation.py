@@ -31,6 +31,7 @@ from typing import TYPE_CHECKING, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _args as AR
 from . import _lib as L
 
 if TYPE_CHECKING:
@@ -142,13 +143,9 @@ def evaluate_depth(pred, gt, protocol: str = "hamlyn", gt_range: Optional[Sequen
     g = _as_u16_frames(gt, "gt")
     if tuple(p.shape) != tuple(g.shape):
         raise ValueError(f"pred shape {tuple(p.shape)} and gt shape {tuple(g.shape)} differ")
-    cuda = [t.device for t in (p, g) if t.is_cuda]
-    if not torch.cuda.is_available():
-        L.init(0)                              # raises BodySlamHipError: no CPU fallback
-    dev = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = AR.device_for(p, g)
     B, H, W = p.shape
     with torch.cuda.device(dev):
-        L.init(dev.index)
         p = p.to(dev, non_blocking=False).contiguous()
         g = g.to(dev, non_blocking=False).contiguous()
         nb = min(B, _MAX_FRAMES_PER_LAUNCH)
@@ -284,8 +281,7 @@ def _as_poses(x, what: str) -> torch.Tensor:
 def _check_trajectory_args(protocol, delta):
     if protocol not in TRAJECTORY_PROTOCOLS:
         raise ValueError(f"unknown protocol {protocol!r}: one of {sorted(TRAJECTORY_PROTOCOLS)}")
-    if isinstance(delta, bool) or not isinstance(delta, (int, np.integer)) or delta < 1:
-        raise ValueError(f"delta {delta!r}: expected an integer >= 1")
+    AR.integer(delta, "delta", 1)
 
 
 def evaluate_trajectory(pred, gt, protocol: str = "evo", delta: int = 1, all_pairs: bool = False, align_origin: bool = True,
@@ -322,14 +318,10 @@ def evaluate_trajectory(pred, gt, protocol: str = "evo", delta: int = 1, all_pai
     lengths = [int(a.shape[0]) for a in P]
     if sum(lengths) >= 2 ** 31:
         raise ValueError(f"{sum(lengths)} poses in all: the offsets are int32")
-    cuda = [t.device for t in P + G if t.is_cuda]
-    if not torch.cuda.is_available():
-        L.init(0)                              # raises BodySlamHipError: no CPU fallback
-    dev = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = AR.device_for(*P, *G)
     flags = ((L.TRAJ_ALIGN_ORIGIN if align_origin else 0) | (L.TRAJ_ALIGN if align else 0) | (L.TRAJ_CORRECT_SCALE if correct_scale else 0) |
              (L.TRAJ_ALL_PAIRS if all_pairs else 0))
     with torch.cuda.device(dev):
-        L.init(dev.index)
         P = [t.to(dev) for t in P]
         G = [t.to(dev) for t in G]
         p_all = P[0] if len(P) == 1 else torch.cat(P)
@@ -398,19 +390,7 @@ def evaluate_trajectory_files(pred_paths, gt_paths, protocol: str = "evo", delta
 
 
 def _as_points(x, what: str) -> torch.Tensor:
-    if isinstance(x, np.ndarray):
-        if x.dtype not in (np.float32, np.float64):
-            raise ValueError(f"{what}: dtype {x.dtype}, expected float32 or float64")
-        t = torch.from_numpy(np.ascontiguousarray(x))
-    elif isinstance(x, torch.Tensor):
-        if x.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"{what}: dtype {x.dtype}, expected torch.float32 or torch.float64")
-        t = x.detach()
-    else:
-        raise ValueError(f"{what}: expected a numpy array or a torch tensor, got {type(x).__name__}")
-    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
-        raise ValueError(f"{what}: shape {tuple(t.shape)}, expected a non-empty [n, 3]")
-    return t
+    return AR.points(x, what, unwrap=False)
 
 
 def similarity_fit_record(source, target) -> np.ndarray:
@@ -420,12 +400,8 @@ def similarity_fit_record(source, target) -> np.ndarray:
         raise ValueError(f"source shape {tuple(a.shape)} and target shape {tuple(b.shape)} differ")
     if a.dtype != b.dtype:
         raise ValueError(f"source dtype {a.dtype} and target dtype {b.dtype} differ")
-    cuda = [t.device for t in (a, b) if t.is_cuda]
-    if not torch.cuda.is_available():
-        L.init(0)                              # raises BodySlamHipError: no CPU fallback
-    dev = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = AR.device_for(a, b)
     with torch.cuda.device(dev):
-        L.init(dev.index)
         a, b = a.to(dev).contiguous(), b.to(dev).contiguous()
         ws = torch.empty(L.SIMILARITY_FIT_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
         out = torch.empty(16, dtype=torch.float64, device=dev)
@@ -515,11 +491,8 @@ def distance_stats_record(dist: torch.Tensor, thresholds: Sequence[float] = ()) 
     taus = _check_thresholds(thresholds)
     if not isinstance(dist, torch.Tensor) or dist.dtype != torch.float32 or dist.dim() != 1 or dist.numel() < 1:
         raise ValueError("dist: expected a non-empty fp32 torch tensor [n]")
-    if not torch.cuda.is_available():
-        L.init(0)                              # raises BodySlamHipError: no CPU fallback
-    dev = dist.device if dist.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = AR.device_for(dist)
     with torch.cuda.device(dev):
-        L.init(dev.index)
         ws = torch.empty(L.PC_STATS_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
         out = torch.empty(L.PC_STATS_FIELDS, dtype=torch.float64, device=dev)
         L.pc_stats(dist.to(dev).contiguous(), taus, ws, out)
@@ -659,9 +632,8 @@ def _check_gt_mesh(gt_mesh, gt, n_gt_samples) -> bool:
     from .tsdf import TriangleMesh
     if gt_mesh not in GT_MESH:
         raise ValueError(f"unknown gt_mesh {gt_mesh!r}: one of {GT_MESH}")
-    if n_gt_samples is not None and (isinstance(n_gt_samples, bool) or not isinstance(n_gt_samples, (int, np.integer)) or
-                                     not 1 <= n_gt_samples < 2 ** 31):
-        raise ValueError(f"n_gt_samples {n_gt_samples!r}: expected None or an integer in [1, 2^31)")
+    if n_gt_samples is not None:
+        AR.integer(n_gt_samples, "n_gt_samples", 1, 2 ** 31 - 1, "None or an integer in [1, 2^31)")
     if gt_mesh == "vertices":
         if n_gt_samples is not None:
             raise ValueError('n_gt_samples given without gt_mesh="surface"')
@@ -694,8 +666,7 @@ def _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, alig
     if not isinstance(pred, (TSDF, MAP)):
         p = PC.as_points(pred, "pred")
     g = PC.as_points(gt, "gt")
-    if not torch.cuda.is_available():
-        L.init(0)                              # raises BodySlamHipError: no CPU fallback
+    AR.device_for()                            # (no GPU: the error comes before a map is asked for its points)
     if isinstance(pred, (TSDF, MAP)):
         cloud = pred.extract_pcd(host=False)
         pts = cloud.points
@@ -704,11 +675,9 @@ def _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, alig
         p = PC.as_points(pts, "pred")
         if kw is not None:
             p_normals = cloud.normals
-    cuda = [t.device for t in (p, g) if t.is_cuda]
-    dev = cuda[0] if cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = AR.device_for(p, g)
     alignment = None
     with torch.cuda.device(dev):
-        L.init(dev.index)
         p, g = p.to(dev).contiguous(), g.to(dev).to(torch.float32).contiguous()
         if A is not None:
             moved = torch.empty(p.shape[0], 3, dtype=torch.float32, device=dev)

@@ -18,13 +18,13 @@ Not built: Open3D's vertex-manifold and self-intersection tests and hence is_wat
 subdivision, hole filling, signed distance."""
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
+from . import _args as AR
 from . import _lib as L
 
 last_rounds = 0          # the (hook, compress) rounds of the latest cluster_connected_triangles, the final unchanged one included
@@ -65,44 +65,11 @@ class MeshEdges:
 # ---- arguments -----------------------------------------------------------------------------------------------------------------------------
 def _as_mesh(vertices, triangles=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """-> (vertices fp32 / fp64 torch [V, 3], triangles integer torch [T, 3]) where they lie; V and T may be 0, indices are not checked"""
-    from .tsdf import TriangleMesh
-    if isinstance(vertices, TriangleMesh):
-        if triangles is not None:
-            raise ValueError("a TriangleMesh brings its own triangles")
-        vertices, triangles = vertices.vertices, vertices.triangles
-    out = []
-    for x, what, floating in ((vertices, "vertices", True), (triangles, "triangles", False)):
-        if isinstance(x, np.ndarray):
-            ok = x.dtype in (np.float32, np.float64) if floating else x.dtype.kind in "iu"
-            if ok and not floating:
-                if x.dtype == np.uint64 and x.size and int(x.max()) >= 2 ** 63:
-                    raise ValueError("triangles: an index of 2^63 or more")
-                x = x.astype(np.int64) if x.dtype != np.int32 else x
-            t = torch.from_numpy(np.ascontiguousarray(x)) if ok else None
-        elif isinstance(x, torch.Tensor):
-            ok = x.dtype in (torch.float32, torch.float64) if floating else x.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
-            t = x.detach()
-        else:
-            raise ValueError(f"{what}: expected a numpy array or a torch tensor, got {type(x).__name__}")
-        if not ok:
-            raise ValueError(f"{what}: dtype {x.dtype}, expected {'float32 or float64' if floating else 'integers'}")
-        if t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError(f"{what}: shape {tuple(t.shape)}, expected [n, 3]")
-        out.append(t)
-    v, t = out
-    if v.shape[0] >= 2 ** 31:
-        raise ValueError(f"vertices: {v.shape[0]} rows: the indices are int32")
-    if t.shape[0] > L.MESH_MAX_TRIANGLES:
-        raise ValueError(f"triangles: {t.shape[0]} rows, at most 2^29")
-    return v, t
+    return AR.triangles(vertices, triangles, allow_empty_vertices=True)
 
 
 def _device(v: torch.Tensor, t: torch.Tensor, device: int) -> torch.device:
-    if not torch.cuda.is_available():
-        L.init(0)                              # raises BodySlamHipError: no CPU fallback
-    dev = v.device if v.is_cuda else (t.device if t.is_cuda else torch.device("cuda", int(device)))
-    L.init(dev.index)
-    return dev
+    return AR.device_for(v, t, device=device)
 
 
 def _on_device(v, t, dev) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -114,23 +81,20 @@ def _on_device(v, t, dev) -> Tuple[torch.Tensor, torch.Tensor]:
 
 
 def _check_iterations(n) -> int:
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n < 2 ** 31:
-        raise ValueError(f"number_of_iterations {n!r}: expected an integer >= 0")
-    return int(n)
+    return AR.integer(n, "number_of_iterations", 0, 2 ** 31 - 1, "an integer >= 0")
 
 
 def _check_factor(x, what: str) -> float:
-    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(float(x)):
-        raise ValueError(f"{what} {x!r}: expected a finite number")
-    return float(x)
+    return AR.number(x, what, "a finite number")
 
 
 def _check_slots(slots, n_half: int) -> int:
     if slots is None:
         return edge_table_slots(n_half // 3)
-    if isinstance(slots, bool) or not isinstance(slots, (int, np.integer)) or not 1 <= slots <= 2 ** 31 or slots & (slots - 1):
+    n = AR.integer(slots, "slots", 1, 2 ** 31, "a power of two, at most 2^31")
+    if n & (n - 1):
         raise ValueError(f"slots {slots!r}: expected a power of two, at most 2^31")
-    return int(slots)
+    return n
 
 
 def edge_table_slots(n_triangles: int) -> int:
@@ -160,12 +124,10 @@ def _edge_rows(t: torch.Tensor, n_vertices: int, slots: int) -> MeshEdges:
     keys = torch.full((slots,), L.MESH_EDGE_EMPTY_KEY, dtype=torch.int64, device=dev)            # (the fills and the scan are plumbing)
     first_half = torch.full((slots,), L.MESH_EDGE_NO_HALF, **i32)
     count, forward = torch.zeros(slots, **i32), torch.zeros(slots, **i32)
-    slot_of_half, leader, is_first, edge_of_half = (torch.empty(3 * T, **i32) for _ in range(4))
+    slot_of_half, edge_of_half = torch.empty(3 * T, **i32), torch.empty(3 * T, **i32)
     status = torch.zeros(2, **i32)
     L.mesh_edge_insert(t, n_vertices, keys, first_half, count, forward, slot_of_half, status)
-    L.mesh_edge_flags(slot_of_half, first_half, leader, is_first)
-    rank = torch.cumsum(is_first, 0).to(torch.int32)                                             # integer, exact
-    word, n_invalid, E = (int(x) for x in torch.cat([status, rank[-1:]]).cpu())
+    leader, rank, (word, n_invalid, E) = AR.first_ranks(L.mesh_edge_flags, slot_of_half, first_half, status)
     if word & L.MESH_EDGE_TABLE_FULL:
         raise L.BodySlamHipError(f"edge_topology: the edge table of {slots} slots is full")
     if word:
@@ -409,8 +371,8 @@ def remove_small_components(mesh, min_triangles: Optional[int] = None, min_area:
     triangles or less than min_area area; keep_largest: every cluster but the one of most triangles (ties go to the lower cluster id).
     -> (TriangleMesh, vertex_map int32 [V], triangle_map int32 [T]).  Order-preserving: the remaining triangles and vertices keep their
     order; colours and any normals are carried along."""
-    if min_triangles is not None and (isinstance(min_triangles, bool) or not isinstance(min_triangles, (int, np.integer)) or min_triangles < 0):
-        raise ValueError(f"min_triangles {min_triangles!r}: expected None or an integer >= 0")
+    if min_triangles is not None:
+        AR.integer(min_triangles, "min_triangles", 0, None, "None or an integer >= 0")
     if min_area is not None:
         min_area = _check_factor(min_area, "min_area")
     if not isinstance(keep_largest, (bool, np.bool_)):

@@ -36,76 +36,37 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from . import _args as AR
 from . import _lib as L
 
 SHELL_CAP = 8               # a source still searching after this shell goes to the brute-force kernel (a starting point, not tuned)
 METHODS = ("grid", "brute")
 
 
-def as_points(x, what: str) -> torch.Tensor:
-    """-> fp32 or fp64 torch tensor [n, 3] on whatever device x is on.  x: a numpy array or torch tensor [n, 3], fp32 or fp64; a
-    tsdf.PointCloud (its points); a tsdf.TriangleMesh (its vertices).  ValueError on anything else."""
-    from .tsdf import PointCloud, TriangleMesh
-    if isinstance(x, PointCloud):
-        x = x.points
-    elif isinstance(x, TriangleMesh):
-        x = x.vertices
-    if isinstance(x, np.ndarray):
-        if x.dtype not in (np.float32, np.float64):
-            raise ValueError(f"{what}: dtype {x.dtype}, expected float32 or float64")
-        t = torch.from_numpy(np.ascontiguousarray(x))
-    elif isinstance(x, torch.Tensor):
-        if x.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"{what}: dtype {x.dtype}, expected torch.float32 or torch.float64")
-        t = x.detach()
-    else:
-        raise ValueError(f"{what}: expected a numpy array, a torch tensor, a PointCloud or a TriangleMesh, got {type(x).__name__}")
-    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
-        raise ValueError(f"{what}: shape {tuple(t.shape)}, expected a non-empty [n, 3]")
-    if t.shape[0] >= 2 ** 31:
-        raise ValueError(f"{what}: {t.shape[0]} points: the indices are int32")
-    return t
+as_points = AR.points
 
 
 def _check_cell_size(cell_size) -> Optional[float]:
     if cell_size is None:
         return None
-    if isinstance(cell_size, bool) or not isinstance(cell_size, (int, float, np.integer, np.floating)):
-        raise ValueError(f"cell_size {cell_size!r}: expected None or a positive number")
-    h = float(np.float32(cell_size))
-    if not (h > 0.0 and math.isfinite(h)):
-        raise ValueError(f"cell_size {cell_size!r}: expected None or a positive number (finite and non-zero in fp32)")
-    return h
+    return AR.number(cell_size, "cell_size", "None or a positive number (finite and non-zero in fp32)", AR.positive, fp32=True)
 
 
 def _check_max_distance(max_distance) -> float:
     if max_distance is None:
         return math.inf
-    if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float, np.integer, np.floating)):
-        raise ValueError(f"max_distance {max_distance!r}: expected None or a number >= 0")
-    v = float(np.float32(max_distance))
-    if not v >= 0.0:
-        raise ValueError(f"max_distance {max_distance!r}: expected None or a number >= 0")
-    return v
+    return AR.number(max_distance, "max_distance", "None or a number >= 0", lambda v: v >= 0.0, fp32=True)
 
 
 def _check_k(k, what: str = "k") -> int:
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= L.PC_KNN_MAX:
-        raise ValueError(f"{what} {k!r}: expected an integer in 1 .. {L.PC_KNN_MAX}")
-    return int(k)
+    return AR.integer(k, what, 1, L.PC_KNN_MAX)
 
 
 def _check_radius(radius) -> float:
     """None -> inf (no radius); otherwise a positive number, finite and non-zero in fp32"""
     if radius is None:
         return math.inf
-    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
-        raise ValueError(f"radius {radius!r}: expected None or a positive number")
-    with np.errstate(over="ignore"):
-        v = float(np.float32(radius))
-    if not (v > 0.0 and math.isfinite(v)):
-        raise ValueError(f"radius {radius!r}: expected None or a positive number (finite and non-zero in fp32)")
-    return v
+    return AR.number(radius, "radius", "None or a positive number (finite and non-zero in fp32)", AR.positive, fp32=True)
 
 
 def _check_orientation(direction, camera_location) -> Tuple[int, Optional[np.ndarray]]:
@@ -171,11 +132,8 @@ class NearestNeighbours:
     def __init__(self, target, cell_size: Optional[float] = None, device: int = 0):
         t = as_points(target, "target")
         h = _check_cell_size(cell_size)
-        if not torch.cuda.is_available():
-            L.init(0)                              # raises BodySlamHipError: no CPU fallback
-        self.dev = t.device if t.is_cuda else torch.device("cuda", int(device))
+        self.dev = AR.device_for(t, device=device)
         with torch.cuda.device(self.dev):
-            L.init(self.dev.index)
             self.target = t.to(self.dev).to(torch.float32).contiguous()
             raw = torch.empty(8, dtype=torch.int32, device=self.dev)
             L.pc_bounds(self.target, raw)
@@ -306,8 +264,7 @@ def remove_statistical_outlier(points, nb_neighbors: int = 20, std_ratio: float 
     avg = ``knn_mean_distance``; over its finite entries bs_pc_stats gives n, sum and sum of squares in its fixed order; in fp64
     mean = sum / n, std = sqrt(max(sumsq - n mean^2, 0) / (n - 1)) (0 for n < 2); a point is kept when (double) avg < mean + std_ratio std.
     A non-finite point is never kept.  1 <= nb_neighbors <= 32.  Raises ValueError on bad arguments before the GPU is touched."""
-    if isinstance(std_ratio, bool) or not isinstance(std_ratio, (int, float, np.integer, np.floating)) or not math.isfinite(float(std_ratio)):
-        raise ValueError(f"std_ratio {std_ratio!r}: expected a finite number")
+    AR.number(std_ratio, "std_ratio", "a finite number")
     avg = knn_mean_distance(points, nb_neighbors, cell_size=cell_size, device=device)
     with torch.cuda.device(avg.device):
         ws = torch.empty(L.PC_STATS_WORKSPACE_BYTES, dtype=torch.uint8, device=avg.device)
@@ -337,12 +294,7 @@ class VoxelDownSample:
 
 
 def _check_voxel_size(voxel_size) -> float:
-    if isinstance(voxel_size, bool) or not isinstance(voxel_size, (int, float, np.integer, np.floating)):
-        raise ValueError(f"voxel_size {voxel_size!r}: expected a positive finite number")
-    h = float(voxel_size)
-    if not (h > 0.0 and math.isfinite(h)):
-        raise ValueError(f"voxel_size {voxel_size!r}: expected a positive finite number")
-    return h
+    return AR.number(voxel_size, "voxel_size", "a positive finite number", AR.positive)
 
 
 def _as_attribute(a, what: str, n: int) -> Optional[torch.Tensor]:
@@ -394,11 +346,8 @@ def voxel_down_sample(points, voxel_size, colors=None, normals=None, unit_normal
     t = as_points(points, "points")
     n = int(t.shape[0])
     c, nr = _as_attribute(colors, "colors", n), _as_attribute(normals, "normals", n)
-    if not torch.cuda.is_available():
-        L.init(0)                              # raises BodySlamHipError: no CPU fallback
-    dev = t.device if t.is_cuda else torch.device("cuda", int(device))
+    dev = AR.device_for(t, device=device)
     with torch.cuda.device(dev):
-        L.init(dev.index)
         pts = t.to(dev).to(torch.float32).contiguous()
         c, nr = (None if a is None else a.to(dev).to(torch.float32).contiguous() for a in (c, nr))
         raw = torch.empty(8, dtype=torch.int32, device=dev)
@@ -420,12 +369,10 @@ def _voxel_rows(pts, colors, normals, origin, h, shift, unit_normals, slots) -> 
     i32 = dict(dtype=torch.int32, device=dev)
     keys = torch.full((slots,), L.PC_VOXEL_EMPTY_KEY, dtype=torch.int64, device=dev)           # (the fills and the scan are plumbing)
     first = torch.full((slots,), L.PC_VOXEL_NO_POINT, **i32)
-    slot_of_point, leader, is_first, row_of_point = (torch.empty(n, **i32) for _ in range(4))
+    slot_of_point, row_of_point = torch.empty(n, **i32), torch.empty(n, **i32)
     status = torch.zeros(1, **i32)
     L.pc_voxel_assign(pts, origin, h, keys, first, slot_of_point, status)
-    L.pc_voxel_flags(slot_of_point, first, leader, is_first)
-    rank = torch.cumsum(is_first, 0).to(torch.int32)                                            # integer, exact
-    m = int(rank[-1].cpu())
+    leader, rank, (m,) = AR.first_ranks(L.pc_voxel_flags, slot_of_point, first)
     if m == 0:                                                                                   # (only with a status bit set)
         _voxel_status(int(status.cpu()), h)
         raise L.BodySlamHipError("voxel_down_sample: no voxel for the finite points")
@@ -452,9 +399,7 @@ def _voxel_status(word: int, h: float) -> None:
 
 
 def _check_count(n, what: str, lo: int, hi: int) -> int:
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not lo <= n < hi:
-        raise ValueError(f"{what} {n!r}: expected an integer in [{lo}, {hi})")
-    return int(n)
+    return AR.integer(n, what, lo, hi - 1)
 
 
 def sample_mesh(vertices, triangles, number_of_points, vertex_colors=None, seed: int = 0, first: int = 0, device: int = 0):
@@ -478,11 +423,8 @@ def sample_mesh(vertices, triangles, number_of_points, vertex_colors=None, seed:
     if t.shape[0] > L.MESH_MAX_SAMPLED_TRIANGLES:
         raise ValueError(f"triangles: {t.shape[0]} rows, at most 2^22 can be sampled")
     c = _as_attribute(vertex_colors, "vertex_colors", int(v.shape[0]))
-    if not torch.cuda.is_available():
-        L.init(0)                              # raises BodySlamHipError: no CPU fallback
-    dev = v.device if v.is_cuda else torch.device("cuda", int(device))
+    dev = AR.device_for(v, device=device)
     with torch.cuda.device(dev):
-        L.init(dev.index)
         v, t = v.to(dev), t.to(dev)
         check_indices(t, int(v.shape[0]))
         v, t = v.to(torch.float32).contiguous(), t.to(torch.int32).contiguous()
@@ -525,11 +467,8 @@ def transform_points(points, transform) -> torch.Tensor:
     applied) or (R [3, 3], s, t [3]) as evaluation.similarity_transform returns it."""
     A = affine_rows(transform)
     p = as_points(points, "points")
-    if not torch.cuda.is_available():
-        L.init(0)                              # raises BodySlamHipError: no CPU fallback
-    dev = p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = AR.device_for(p)
     with torch.cuda.device(dev):
-        L.init(dev.index)
         p = p.to(dev).contiguous()
         out = torch.empty(p.shape[0], 3, dtype=torch.float32, device=dev)
         L.pc_transform(p, A, out)

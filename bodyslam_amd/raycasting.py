@@ -25,6 +25,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import _args as AR
 from . import _lib as L
 from . import pointcloud as PC
 
@@ -50,29 +51,7 @@ def grid_padding(lo: np.ndarray, hi: np.ndarray):
 def as_triangles(vertices, triangles=None):
     """-> (vertices fp32 or fp64 torch [V, 3], triangles torch integer [T, 3]) where they lie.  (vertices, triangles): numpy arrays or torch
     tensors, or a tsdf.TriangleMesh alone.  ValueError on anything else; the index range is checked where the data is (check_indices)."""
-    from .tsdf import TriangleMesh
-    if isinstance(vertices, TriangleMesh):
-        if triangles is not None:
-            raise ValueError("add_triangles: a TriangleMesh brings its own triangles")
-        vertices, triangles = vertices.vertices, vertices.triangles
-    v = PC.as_points(vertices, "vertices")
-    if isinstance(triangles, np.ndarray):
-        if triangles.dtype.kind not in "iu":
-            raise ValueError(f"triangles: dtype {triangles.dtype}, expected integers")
-        if triangles.dtype == np.uint64 and triangles.size and int(triangles.max()) >= 2 ** 63:
-            raise ValueError("triangles: an index outside [0, V)")
-        t = torch.from_numpy(np.ascontiguousarray(triangles.astype(np.int64)))
-    elif isinstance(triangles, torch.Tensor):
-        if triangles.dtype.is_floating_point or triangles.dtype in (torch.bool, torch.complex64, torch.complex128):
-            raise ValueError(f"triangles: dtype {triangles.dtype}, expected integers")
-        t = triangles.detach()
-    else:
-        raise ValueError(f"triangles: expected a numpy array or a torch tensor, got {type(triangles).__name__}")
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f"triangles: shape {tuple(t.shape)}, expected [T, 3]")
-    if t.shape[0] > L.MESH_MAX_TRIANGLES:
-        raise ValueError(f"triangles: {t.shape[0]} rows, at most 2^29")
-    return v, t
+    return AR.triangles(vertices, triangles)
 
 
 def check_indices(t: torch.Tensor, n_vertices: int) -> None:
@@ -82,16 +61,7 @@ def check_indices(t: torch.Tensor, n_vertices: int) -> None:
 
 
 def _as_rows(x, width: int, what: str) -> torch.Tensor:
-    if isinstance(x, np.ndarray):
-        if x.dtype not in (np.float32, np.float64):
-            raise ValueError(f"{what}: dtype {x.dtype}, expected float32 or float64")
-        x = torch.from_numpy(np.ascontiguousarray(x))
-    elif isinstance(x, torch.Tensor):
-        if x.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"{what}: dtype {x.dtype}, expected torch.float32 or torch.float64")
-        x = x.detach()
-    else:
-        raise ValueError(f"{what}: expected a numpy array or a torch tensor, got {type(x).__name__}")
+    x = AR.floating(x, what)
     if x.dim() < 1 or x.shape[-1] != width:
         raise ValueError(f"{what}: shape {tuple(x.shape)}, expected [..., {width}]")
     if x.numel() // width >= 2 ** 31:
@@ -114,11 +84,7 @@ class RaycastingScene:
     def __init__(self, device: int = 0, cell_size: Optional[float] = None):
         self._cell_size = PC._check_cell_size(cell_size)
         self.last_fallback = 0
-        if isinstance(device, bool) or not isinstance(device, (int, np.integer)) or device < 0:
-            raise ValueError(f"device {device!r}: expected a GPU index")
-        if not torch.cuda.is_available():
-            L.init(0)                              # raises BodySlamHipError: no CPU fallback
-        self.dev = torch.device("cuda", int(device))
+        self.dev = AR.device_for(device=AR.integer(device, "device", 0, None, "a GPU index"))
         self._geometries = []                      # (vertices fp32 [V, 3], triangles int32 [T, 3]) on the device
         self._dirty = True
         self.n_triangles = self.n_kept = 0
@@ -129,8 +95,7 @@ class RaycastingScene:
         tsdf.TriangleMesh -> the geometry's id 0, 1, ...  ValueError for an index outside [0, V).  A triangle with a non-finite vertex, or
         whose fp32 cross product (v1 - v0) x (v2 - v0) is exactly zero or not finite, is in no result; primitive ids still count it."""
         v, t = as_triangles(vertices, triangles)
-        with torch.cuda.device(self.dev):
-            L.init(self.dev.index)
+        with torch.cuda.device(AR.device_for(device=self.dev.index)):
             v, t = v.to(self.dev), t.to(self.dev)
             check_indices(t, int(v.shape[0]))
             total = sum(int(g[1].shape[0]) for g in self._geometries) + int(t.shape[0])
@@ -200,12 +165,10 @@ class RaycastingScene:
         if K.shape != (3, 3) or E.shape != (4, 4) or not (np.isfinite(K).all() and np.isfinite(E).all()):
             raise ValueError(f"create_rays_pinhole: a finite 3 x 3 intrinsic and 4 x 4 extrinsic matrix, got {K.shape} and {E.shape}")
         for name, n in (("width_px", width_px), ("height_px", height_px)):
-            if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
-                raise ValueError(f"create_rays_pinhole: {name} {n!r}, expected a positive integer")
+            AR.integer(n, f"create_rays_pinhole: {name}", 1, None, "a positive integer")
         if K[0, 0] == 0.0 or K[1, 1] == 0.0:
             raise ValueError("create_rays_pinhole: a zero focal length")
-        if isinstance(pixel_center, bool) or not isinstance(pixel_center, (int, float, np.integer, np.floating)) or not np.isfinite(pixel_center):
-            raise ValueError(f"create_rays_pinhole: pixel_center {pixel_center!r}, expected a finite number")
+        AR.number(pixel_center, "create_rays_pinhole: pixel_center", "a finite number")
         R, t = E[:3, :3], E[:3, 3]
         v, u = np.meshgrid(np.arange(int(height_px), dtype=np.float64), np.arange(int(width_px), dtype=np.float64), indexing="ij")
         x = ((u + np.float64(pixel_center)) - K[0, 2]) / K[0, 0]

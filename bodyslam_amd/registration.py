@@ -26,6 +26,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import _args as AR
 from . import _lib as L
 from . import pointcloud as PC
 
@@ -49,13 +50,7 @@ class RegistrationResult:
 
 
 def _check_radius(r) -> float:
-    if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)):
-        raise ValueError(f"max_correspondence_distance {r!r}: expected a positive number")
-    with np.errstate(over="ignore"):
-        v = float(np.float32(r))
-    if not (v > 0.0 and math.isfinite(v)):
-        raise ValueError(f"max_correspondence_distance {r!r}: expected a positive number (finite and non-zero in fp32)")
-    return v
+    return AR.number(r, "max_correspondence_distance", "a positive number (finite and non-zero in fp32)", AR.positive, fp32=True)
 
 
 def _check_init(init, what: str = "init") -> np.ndarray:
@@ -71,14 +66,10 @@ def _check_init(init, what: str = "init") -> np.ndarray:
 
 
 def _check_criteria(max_iteration, relative_fitness, relative_rmse) -> Tuple[int, float, float]:
-    if isinstance(max_iteration, bool) or not isinstance(max_iteration, (int, np.integer)) or not 1 <= max_iteration <= L.ICP_MAX_ITERATIONS:
-        raise ValueError(f"max_iteration {max_iteration!r}: expected an integer in 1 .. {L.ICP_MAX_ITERATIONS}")
-    out = []
-    for name, v in (("relative_fitness", relative_fitness), ("relative_rmse", relative_rmse)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or math.isnan(float(v)):
-            raise ValueError(f"{name} {v!r}: expected a number")
-        out.append(float(v))
-    return int(max_iteration), out[0], out[1]
+    n = AR.integer(max_iteration, "max_iteration", 1, L.ICP_MAX_ITERATIONS)
+    fitness, rmse = (AR.number(v, name, "a number", lambda v: not math.isnan(v))
+                     for name, v in (("relative_fitness", relative_fitness), ("relative_rmse", relative_rmse)))
+    return n, fitness, rmse
 
 
 def _as_normals(normals, n: int) -> torch.Tensor:
@@ -116,13 +107,10 @@ class _Run:
     """the device side of one registration: the index, the buffers and the two launches"""
 
     def __init__(self, s, t, target, nt, radius, est, cell_size, device, T0, max_iteration, relative_fitness, relative_rmse):
-        if not torch.cuda.is_available():
-            L.init(0)                              # raises BodySlamHipError: no CPU fallback
         self.nn = target if t is None else PC.NearestNeighbours(t, cell_size=cell_size, device=device)
-        self.dev = self.nn.dev
+        self.dev = AR.device_for(device=self.nn.dev.index)
         self.radius, self.est, self.crit = radius, est, (max_iteration, relative_fitness, relative_rmse)
         with torch.cuda.device(self.dev):
-            L.init(self.dev.index)
             self.src = s.to(self.dev).contiguous()
             self.normals = None if nt is None else nt.to(self.dev).to(torch.float32).contiguous()
             self.m = int(self.src.shape[0])

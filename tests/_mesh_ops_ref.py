@@ -127,17 +127,15 @@ def wave_sum(x):
 
 
 def triangle_geometry(vertices, triangles):
-    """-> (valid bool [T], kept bool [T], unit normals float32 [T, 3], n float64 [T, 3], area float64 [T]); zero where not kept"""
+    """-> (valid bool [T], kept bool [T], unit normals float32 [T, 3], n float64 [T, 3], area float64 [T]); zero where not kept.  The kept
+    rule, the unit normal, the cross product and the area are _mesh_scene_ref's: a TriangleMesh and a RaycastingScene keep the same triangles"""
     v, t = _vt(vertices, triangles)
     valid = valid_triangles(len(v), t)
     ts = np.where(valid[:, None], t, 0)
     v0, v1, v2 = (v[ts[:, k]] for k in range(3)) if len(v) else (np.zeros((len(t), 3), f32),) * 3
     kept, unit = MS.kept_and_normals(v0, v1, v2)
     kept = kept & valid
-    a, b, c = v0.astype(f64), v1.astype(f64), v2.astype(f64)
-    with np.errstate(all="ignore"):
-        n = MS._cross(b - a, c - a)
-        area = 0.5 * np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+    n, area = MS.cross_and_area(v0, v1, v2)
     return (valid, kept, np.where(kept[:, None], unit, f32(0)).astype(f32), np.where(kept[:, None], n, 0.0),
             np.where(kept, area, 0.0))
 

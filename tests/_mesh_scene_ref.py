@@ -264,14 +264,18 @@ def mulhi64(a, b):
     return np.array([(int(x) * int(b)) >> 64 for x in np.asarray(a).ravel()], u64).reshape(np.shape(a))
 
 
-def sample_weights(v0, v1, v2, kept):
-    """uint64 [T]: floor(area / max area 2^40), area = 0.5 sqrt((cx cx + cy cy) + cz cz) of the float64 cross product of the float64
-    differences of the float32 vertices; 0 for a triangle that is not kept"""
+def cross_and_area(v0, v1, v2):
+    """-> (n float64 [T, 3], area float64 [T]): the float64 cross product of the float64 differences of the float32 vertices, and
+    area = 0.5 sqrt((nx nx + ny ny) + nz nz)"""
     a, b, c = v0.astype(f64), v1.astype(f64), v2.astype(f64)
     with np.errstate(all="ignore"):
         n = _cross(b - a, c - a)
-        area = 0.5 * np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
-    area = np.where(kept, area, 0.0)
+        return n, 0.5 * np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+
+
+def sample_weights(v0, v1, v2, kept):
+    """uint64 [T]: floor(area / max area 2^40) with cross_and_area's area; 0 for a triangle that is not kept"""
+    area = np.where(kept, cross_and_area(v0, v1, v2)[1], 0.0)
     top = area.max() if len(area) else 0.0
     if not (top > 0.0 and np.isfinite(top)):
         return np.zeros(len(area), u64)

@@ -189,6 +189,62 @@ def test_bindings_directly(M):
     assert same_bits(host(out), np.array([0.0, R.wave_sum(a64[:70]), R.wave_sum(a64[70:])]))
 
 
+def promise_mesh():
+    """32 vertices, 39 triangles: a 5 x 5 height field (32 ordinary triangles) and one triangle of every kind that is not kept"""
+    g = np.arange(5, dtype=f32) * f32(0.25)
+    grid = np.array([[x, y, f32(((7 * i + 13 * j) % 5) * 0.05)] for j, y in enumerate(g) for i, x in enumerate(g)], f32)
+    extra = np.array([[0.5, 0.5, 0.5], [1, 1, 1], [2, 2, 2],            # 25, 26, 27: exactly collinear
+                      [np.nan, 0, 0], [0, np.inf, 0],                   # 28, 29
+                      [1e30, 0, 0], [0, 1e30, 0]], f32)                 # 30, 31: with vertex 0 a cross product of 1e60, inf in fp32
+    quad = [(5 * j + i, 5 * j + i + 1, 5 * j + i + 5, 5 * j + i + 6) for j in range(4) for i in range(4)]
+    ordinary = [tri for a, b, c, d in quad for tri in ((a, b, d), (a, d, c))]
+    special = [(3, 3, 9), (7, 12, 12), (25, 26, 27), (0, 1, 28), (5, 29, 6), (0, 30, 31), (26, 25, 27)]
+    return np.concatenate([grid, extra]), np.array(ordinary + special, i32)
+
+
+def test_scene_and_mesh_keep_the_same_triangles(M):
+    """the promise of csrc/triangle.h: RaycastingScene and mesh.py keep the same triangles and give the same normal bits"""
+    from bodyslam_amd import _lib as L
+    from bodyslam_amd import pointcloud as PC
+    from bodyslam_amd.raycasting import RaycastingScene
+    v, t = promise_mesh()
+    T = len(t)
+    # the two numpy statements first: the reference alone agrees with itself on this mesh
+    valid, kept, unit, _, area = R.triangle_geometry(v, t)
+    scene_kept, scene_unit = MS.kept_and_normals(*MS.corners(v, t))
+    assert np.array_equal(kept, scene_kept) and same_bits(unit, scene_unit)
+    assert kept[:32].all() and not kept[32:].any() and valid[32:].tolist() == [False, False, True, True, True, True, True]
+    assert (area[:32] > 0).all() and (np.abs(np.linalg.norm(unit[:32].astype(f64), axis=1) - 1) < 1e-6).all()
+    L.init(0)
+    vd, td = torch.from_numpy(v).cuda(), torch.from_numpy(t).cuda()
+    # (a) the kept set of the scene's records is the KEPT flag of the mesh's geometry, triangle for triangle
+    records, n_kept = torch.empty(T, 3, 4, device="cuda"), torch.empty(1, dtype=torch.int32, device="cuda")
+    L.mesh_records(vd, td, records, n_kept)
+    flags, nrm = torch.empty(T, dtype=torch.int32, device="cuda"), torch.empty(T, 3, device="cuda")
+    L.mesh_triangle_geometry(vd, td, flags=flags, normals=nrm)
+    rec_kept = host(records[:, 0, 3].contiguous().view(torch.int32) >= 0)
+    flag_kept = (host(flags) & L.MESH_TRIANGLE_KEPT) != 0
+    assert np.array_equal(rec_kept, flag_kept) and np.array_equal(flag_kept, kept) and int(n_kept) == 32
+    nrm = host(nrm)
+    assert same_bits(nrm, unit)
+    # (b) a sample's normal is its triangle's row
+    _, _, s_normals, s_index = PC.sample_mesh(v, t, 400, seed=3)
+    s_index = host(s_index)
+    assert len(s_index) == 400 and kept[s_index].all() and len(set(s_index.tolist())) >= 24
+    assert same_bits(host(s_normals), nrm[s_index])
+    # (c) a hit's primitive normal is that row too: one ray down onto the centroid of every triangle of the height field, and two misses
+    centroid = v[t[:32]].astype(f64).mean(1)
+    rays = np.concatenate([np.concatenate([centroid + [0, 0, 2], np.tile([0.0, 0, -1], (32, 1))], 1),
+                           [[5, 5, 2, 0, 0, -1], [0.4, 0.4, 2, 0, 0, 1]]]).astype(f32)
+    scene = RaycastingScene()
+    scene.add_triangles(v, t)
+    for method in ("grid", "brute"):
+        out = scene.cast_rays(rays, method=method)
+        prim, got = host(out["primitive_ids"]), host(out["primitive_normals"])
+        assert prim[:32].tolist() == list(range(32)) and prim[32:].tolist() == [-1, -1], method
+        assert same_bits(got[:32], nrm[prim[:32]]) and not got[32:].any(), method
+
+
 # ---- 4: permuted triangle rows --------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["cube", "height_field"])
 def test_permuted_rows(M, name):
