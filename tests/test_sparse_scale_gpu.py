@@ -10,6 +10,7 @@ import pytest
 
 import _corner_scene as S
 import _orb_ref as R
+from _orb_cases import level_view
 from oracle.ukf_ref import LinearKF
 
 pytestmark = pytest.mark.gpu
@@ -35,11 +36,6 @@ def plane():
     out = eng(rgbd(curr), rgbd(prev))
     st = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in eng.last_stages.items()}
     return dict(prev=prev, curr=curr, motion=motion, f=f, m=m, ref=ref, out=out, counts=eng.last_counts.copy(), st=st)
-
-
-def level_view(st, name, frame, l):
-    w, h, off = st["levels"][l]
-    return st[name][frame, off:off + w * h].reshape(h, w)
 
 
 # ---- stage outputs, bit for bit ---------------------------------------------------------------------------------------------------------
