@@ -248,7 +248,12 @@ class TSDFRef:
                             if np.dot(nrm, mid.mean(0) - ins.mean(0)) < 0:
                                 loop = loop[::-1]
                             # fan from a vertex whose diagonals all run through the cube's interior (a diagonal inside a cube face
-                            # could coincide with an edge of the neighbouring cube: four triangles on one edge)
+                            # could coincide with an edge of the neighbouring cube: four triangles on one edge).  Which of the
+                            # admissible vertices is a free choice (Open3D's comes with the classic table); it is made explicit so that
+                            # triangles, not only surfaces, can be compared: the first admissible one in the oriented loop, counted from
+                            # the cube edge with the lowest (corner, corner) pair -- not from wherever the dict happened to start.
+                            k0 = min(range(len(loop)), key=lambda i: tuple(sorted(loop[i])))
+                            loop = loop[k0:] + loop[:k0]
                             in_face = lambda e0, e1: any(set(e0) <= set(cyc) and set(e1) <= set(cyc) for cyc in faces)
                             for rot in range(len(loop)):
                                 cand = loop[rot:] + loop[:rot]
