@@ -22,13 +22,15 @@ Everything runs in the kernels of csrc/odometry.hip.  Three ways to call it:
     (the reference starts every pair from the identity, visual_odometry.py:100), so n frames are n simultaneous pairs: every stage is
     ONE launch over the whole block (~100 launches per block instead of 81 per frame) and the work is HBM streaming instead of a
     chain of 10-microsecond launches.  Pair for pair the same sums in the same order as the other two: bit-equal results.
+All three go through one pyramid build and one step loop: a pair is a batch of one.
 
 ``PointToPlaneOdometry`` (below) is the other registration of the reference's Open3D models: a depth frame against the map's
 ray-cast depth, point-to-plane, what ``MAP.track_frame_to_model`` runs."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence
+import functools
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -55,8 +57,70 @@ def se3_exp(delta: np.ndarray) -> np.ndarray:
     return T
 
 
+# ---- what both odometries share: level shapes, the schedule, scratch, the host-walked loop ----------------------------------------
+def _level_shapes(H: int, W: int, K: Sequence[float], n_levels: int) -> List[Tuple[int, int, np.ndarray]]:
+    """(h, w, intrinsics as 4 host doubles) of every pyramid level, fine to coarse: sizes halve rounding up, intrinsics halve"""
+    shapes, k = [], tuple(K)
+    for _ in range(n_levels):
+        shapes.append((H, W, np.array(k, dtype=np.float64)))
+        H, W, k = (H + 1) // 2, (W + 1) // 2, tuple(v / 2.0 for v in k)
+    return shapes
+
+
+def _schedule(iterations: Sequence[int]) -> List[Tuple[int, int]]:
+    """(level, iterations) coarse to fine"""
+    return list(zip(range(len(iterations) - 1, -1, -1), iterations))
+
+
+@functools.lru_cache(maxsize=None)
+def _identity12(dev: torch.device) -> torch.Tensor:
+    """rows 0..2 of the identity on the device: uploaded once, only ever read"""
+    return torch.tensor([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], dtype=torch.float64, device=dev)
+
+
+def _scratch(n: int, H: int, W: int, dev: torch.device) -> dict:
+    """for n simultaneous pairs: the identity pose T0 [12], the poses T [n, 12], the Gauss-Newton step's block partials and sums"""
+    blocks = min((H * W + 255) // 256, 256)          # the grid of the accumulate kernels (csrc/odometry.hip odo_grid)
+    return dict(T0=_identity12(dev),
+                T=torch.empty(n, 12, dtype=torch.float64, device=dev),
+                partial=torch.empty(n, blocks, 29, dtype=torch.float64, device=dev),
+                out=torch.zeros(n, 29, dtype=torch.float64, device=dev))
+
+
+def _pyrdown(src: int, n: int, H: int, W: int, dst: int, depth_threshold: Optional[float], st: int) -> None:
+    """n images at address src -> their next level at dst, on stream st; depth_threshold None: an intensity image"""
+    is_depth = depth_threshold is not None
+    L.check(L.load_library().bs_odo_pyrdown(src, n, H, W, dst, int(is_depth), depth_threshold if is_depth else 0.0, st), "bs_odo_pyrdown")
+
+
+def _host_walk(T: np.ndarray, schedule: Sequence[Tuple[int, int]], sums: Callable[[int, np.ndarray], np.ndarray], starved_leaves_level: bool):
+    """The Gauss-Newton loop walked from the host (trace=True: tests, diagnostics).  sums(level, T12) returns the 29 sums of that level
+    at the host pose T12 (12 doubles).  Every step is logged as (level, A, b, cost, inliers); a step with fewer than 6 inliers leaves
+    the pose alone and, with starved_leaves_level, ends its level's iterations.  Returns (T, log)."""
+    iu = np.triu_indices(6)
+    log = []
+    for level, iters in schedule:
+        for _ in range(iters):
+            r = sums(level, np.ascontiguousarray(T[:3].reshape(12)))
+            A = np.zeros((6, 6))
+            A[iu] = r[:21]
+            A = A + np.triu(A, 1).T
+            b, cost, n = r[21:27], float(r[27]), int(round(r[28]))
+            log.append((level, A.copy(), b.copy(), cost, n))
+            if n >= 6:
+                T = se3_exp(np.linalg.solve(A + 1e-12 * np.eye(6), -b)) @ T
+            elif starved_leaves_level:
+                break
+    return T, log
+
+
 class _Level:
-    __slots__ = ("H", "W", "K", "Kc", "I", "D", "gIx", "gIy", "gDx", "gDy")     # maps: [H, W], or [slots, H, W] in track_block
+    __slots__ = ("H", "W", "Kc", "I", "D", "gIx", "gIy", "gDx", "gDy")     # maps: [slots, H, W]
+
+    def at(self, slot: int) -> List[int]:
+        """the addresses of image `slot` of the six maps (I, D, gIx, gIy, gDx, gDy)"""
+        o = 4 * slot * self.H * self.W
+        return [m.data_ptr() + o for m in (self.I, self.D, self.gIx, self.gIy, self.gDx, self.gDy)]
 
 
 class RGBDOdometry:
@@ -78,89 +142,77 @@ class RGBDOdometry:
         self._blk = None
 
     # ---- device-side image preparation ---------------------------------------------------------------
-    def _alloc_levels(self, H: int, W: int) -> List[_Level]:
-        """the six maps of every pyramid level as views of ONE flat buffer (a frame's whole state moves with one copy)"""
-        shapes = []
-        h, w, k = H, W, self.K
-        for _ in range(len(self.iterations)):
-            shapes.append((h, w, k))
-            h, w, k = (h + 1) // 2, (w + 1) // 2, tuple(v / 2.0 for v in k)
-        flat = torch.empty(sum(6 * a * b for a, b, _ in shapes), device=self.dev, dtype=torch.float32)
+    def _alloc_levels(self, H: int, W: int, slots: int = 1):
+        """(levels, flat): the six [slots, h, w] maps of every pyramid level as views of ONE flat buffer (with one slot, a frame's
+        whole state moves with one copy)"""
+        shapes = _level_shapes(H, W, self.K, len(self.iterations))
+        flat = torch.empty(sum(6 * slots * h * w for h, w, _ in shapes), device=self.dev, dtype=torch.float32)
         levels, off = [], 0
-        for (h, w, k) in shapes:
+        for (h, w, kc) in shapes:
             lv = _Level()
-            lv.H, lv.W, lv.K, lv.Kc = h, w, k, np.array(k, dtype=np.float64)
+            lv.H, lv.W, lv.Kc = h, w, kc
             maps = []
             for _ in range(6):
-                maps.append(flat[off:off + h * w].view(h, w))
-                off += h * w
+                maps.append(flat[off:off + slots * h * w].view(slots, h, w))
+                off += slots * h * w
             lv.I, lv.D, lv.gIx, lv.gIy, lv.gDx, lv.gDy = maps
             levels.append(lv)
-        self._last_flat = flat
-        return levels
+        return levels, flat
 
-    def _build(self, levels: List[_Level], color: torch.Tensor, depth: torch.Tensor, depth_max: float, gradients: bool = True):
+    def _build(self, levels: List[_Level], color: torch.Tensor, depth: torch.Tensor, depth_max: float, n: int = 1, slot: int = 0,
+               gradients: bool = True):
+        """the pyramids (and gradients) of n frames into slots slot .. slot + n - 1: one launch per stage, 1 + 4 + 6 on three levels"""
         lib, st = L.load_library(), L.stream_ptr()
+        at = [lv.at(slot) for lv in levels]
         l0 = levels[0]
-        L.check(lib.bs_odo_prepare(L.p(color), L.p(depth), 1, l0.H, l0.W, float(depth_max), L.p(l0.I), L.p(l0.D), st), "bs_odo_prepare")
-        for p, n in zip(levels[:-1], levels[1:]):
-            L.check(lib.bs_odo_pyrdown(L.p(p.I), 1, p.H, p.W, L.p(n.I), 0, 0.0, st), "bs_odo_pyrdown")
-            L.check(lib.bs_odo_pyrdown(L.p(p.D), 1, p.H, p.W, L.p(n.D), 1, 2.0 * DEPTH_OUTLIER_TRUNC, st), "bs_odo_pyrdown")
+        L.check(lib.bs_odo_prepare(L.p(color), L.p(depth), n, l0.H, l0.W, float(depth_max), at[0][0], at[0][1], st), "bs_odo_prepare")
+        for p, a, b in zip(levels[:-1], at[:-1], at[1:]):
+            _pyrdown(a[0], n, p.H, p.W, b[0], None, st)
+            _pyrdown(a[1], n, p.H, p.W, b[1], 2.0 * DEPTH_OUTLIER_TRUNC, st)
         if gradients:
-            for lv in levels:
-                L.check(lib.bs_odo_sobel(L.p(lv.I), 1, lv.H, lv.W, L.p(lv.gIx), L.p(lv.gIy), st), "bs_odo_sobel")
-                L.check(lib.bs_odo_sobel(L.p(lv.D), 1, lv.H, lv.W, L.p(lv.gDx), L.p(lv.gDy), st), "bs_odo_sobel")
+            for lv, (I, D, gIx, gIy, gDx, gDy) in zip(levels, at):
+                for img, gx, gy in ((I, gIx, gIy), (D, gDx, gDy)):
+                    L.check(lib.bs_odo_sobel(img, n, lv.H, lv.W, gx, gy, st), "bs_odo_sobel")
 
     def _pyramid(self, color_u8, depth_m, depth_max: float, gradients: bool):
         color, depth = self._dev(color_u8, torch.uint8), self._dev(depth_m, torch.float32)      # numpy, host or device tensors
-        levels = self._alloc_levels(*depth.shape)
-        self._build(levels, color, depth, depth_max, gradients)
+        levels, _ = self._alloc_levels(*depth.shape)
+        self._build(levels, color, depth, depth_max, gradients=gradients)
         return levels
 
-    def _steps(self, ps: List[_Level], pt: List[_Level], T_dev: torch.Tensor, partial: torch.Tensor, out: torch.Tensor):
-        """the coarse-to-fine loop on the device: sum(iterations) x (sums kernel, fixed-order reduction + 6x6 solve + pose update)"""
+    def _steps(self, src: List[_Level], s: int, tgt: List[_Level], t: int, pairs: int, T: torch.Tensor, partial: torch.Tensor, out: torch.Tensor):
+        """the coarse-to-fine loop on the device, sum(iterations) x (sums kernel, fixed-order reduction + 6x6 solve + pose update):
+        pair p = image s + p of the source levels against image t + p of the target levels, at pose T[p]"""
         lib, st = L.load_library(), L.stream_ptr()
-        for level, iters in zip(range(len(ps) - 1, -1, -1), self.iterations):
-            s, t = ps[level], pt[level]
-            L.check(lib.bs_odo_step(L.p(s.I), L.p(s.D), L.p(t.I), L.p(t.D), L.p(t.gIx), L.p(t.gIy), L.p(t.gDx), L.p(t.gDy), 1, s.H, s.W,
-                                    s.Kc.ctypes.data_as(C.c_void_p), L.p(T_dev), iters, DEPTH_OUTLIER_TRUNC, DEPTH_HUBER, INTENSITY_HUBER,
-                                    L.p(partial), L.p(out), self.flags, st), "bs_odo_step")
+        for level, iters in _schedule(self.iterations):
+            lv = src[level]
+            L.check(lib.bs_odo_step(*lv.at(s)[:2], *tgt[level].at(t), pairs, lv.H, lv.W, lv.Kc.ctypes.data_as(C.c_void_p), L.p(T), iters,
+                                    DEPTH_OUTLIER_TRUNC, DEPTH_HUBER, INTENSITY_HUBER, L.p(partial), L.p(out), self.flags, st), "bs_odo_step")
 
     # ---- the estimate ----------------------------------------------------------------------------------
     def estimate(self, src_color, src_depth, tgt_color, tgt_depth, depth_max: float, init: Optional[np.ndarray] = None, trace: bool = False):
         """T (4x4 float64): source points -> target frame"""
-        lib, st = L.load_library(), L.stream_ptr()
         ps = self._pyramid(src_color, src_depth, depth_max, gradients=False)
         pt = self._pyramid(tgt_color, tgt_depth, depth_max, gradients=True)
         T = np.eye(4) if init is None else np.array(init, dtype=np.float64)
-        out = torch.zeros(29, dtype=torch.float64, device=self.dev)
-        partial = torch.empty((ps[0].H * ps[0].W + 255) // 256, 29, dtype=torch.float64, device=self.dev)
+        k = _scratch(1, ps[0].H, ps[0].W, self.dev)
         if not trace:
             # no host round trip until the pose is read back; trace=True below walks the same steps from the host (tests, diagnostics)
-            T_dev = torch.from_numpy(np.ascontiguousarray(T[:3].reshape(12))).to(self.dev)
-            self._steps(ps, pt, T_dev, partial, out)
-            T[:3] = T_dev.cpu().numpy().reshape(3, 4)
+            k["T"].copy_(k["T0"] if init is None else torch.from_numpy(np.ascontiguousarray(T[:3].reshape(1, 12))))
+            self._steps(ps, 0, pt, 0, 1, k["T"], k["partial"], k["out"])
+            T[:3] = k["T"].cpu().numpy().reshape(3, 4)
             self.last_trace = None
             return T
-        iu = np.triu_indices(6)
-        log = []
-        for level, iters in zip(range(len(ps) - 1, -1, -1), self.iterations):
-            s, t = ps[level], pt[level]
-            for _ in range(iters):
-                T12 = np.ascontiguousarray(T[:3].reshape(12))
-                L.check(lib.bs_odo_accumulate(L.p(s.I), L.p(s.D), L.p(t.I), L.p(t.D), L.p(t.gIx), L.p(t.gIy), L.p(t.gDx), L.p(t.gDy), s.H, s.W,
-                                              s.Kc.ctypes.data_as(C.c_void_p), T12.ctypes.data_as(C.c_void_p), DEPTH_OUTLIER_TRUNC, DEPTH_HUBER,
-                                              INTENSITY_HUBER, L.p(partial), L.p(out), self.flags, st), "bs_odo_accumulate")
-                r = out.cpu().numpy()                    # (synchronises: T12 / Kc outlive the launch)
-                A = np.zeros((6, 6))
-                A[iu] = r[:21]
-                A = A + np.triu(A, 1).T
-                b, res, n = r[21:27], float(r[27]), int(round(r[28]))
-                log.append((level, A.copy(), b.copy(), res, n))
-                if n < 6:
-                    break
-                T = se3_exp(np.linalg.solve(A + 1e-12 * np.eye(6), -b)) @ T
-        self.last_trace = log
+        lib, st = L.load_library(), L.stream_ptr()
+
+        def sums(level, T12):
+            s = ps[level]
+            L.check(lib.bs_odo_accumulate(*s.at(0)[:2], *pt[level].at(0), s.H, s.W, s.Kc.ctypes.data_as(C.c_void_p), T12.ctypes.data_as(C.c_void_p),
+                                          DEPTH_OUTLIER_TRUNC, DEPTH_HUBER, INTENSITY_HUBER, L.p(k["partial"]), L.p(k["out"]), self.flags, st),
+                    "bs_odo_accumulate")
+            return k["out"][0].cpu().numpy()                    # (synchronises: T12 / Kc outlive the launch)
+
+        T, self.last_trace = _host_walk(T, _schedule(self.iterations), sums, starved_leaves_level=True)
         return T
 
     def __call__(self, curr_rgbd, prev_rgbd) -> np.ndarray:
@@ -187,16 +239,11 @@ class RGBDOdometry:
         H, W = depth_m.shape
         k = self._trk
         if k is None or k["hw"] != (H, W):
-            prev = self._alloc_levels(H, W)
-            prev_flat = self._last_flat
-            cur = self._alloc_levels(H, W)
-            cur_flat = self._last_flat
+            prev, prev_flat = self._alloc_levels(H, W)
+            cur, cur_flat = self._alloc_levels(H, W)
             k = self._trk = dict(hw=(H, W), prev=prev, cur=cur, prev_flat=prev_flat, cur_flat=cur_flat, have_prev=False, graph=None, warm=False,
                                  color=torch.empty(H, W, 3, dtype=torch.uint8, device=self.dev), depth=torch.empty(H, W, device=self.dev),
-                                 T=torch.zeros(12, dtype=torch.float64, device=self.dev),
-                                 T0=torch.tensor([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], dtype=torch.float64, device=self.dev),
-                                 partial=torch.empty((H * W + 255) // 256, 29, dtype=torch.float64, device=self.dev),
-                                 out=torch.zeros(29, dtype=torch.float64, device=self.dev))
+                                 **_scratch(1, H, W, self.dev))
         k["color"].copy_(color_u8)
         k["depth"].copy_(depth_m)
         if not k["have_prev"]:
@@ -207,7 +254,7 @@ class RGBDOdometry:
         def pair():
             k["T"].copy_(k["T0"])
             self._build(k["cur"], k["color"], k["depth"], 3.0e38)
-            self._steps(k["cur"], k["prev"], k["T"], k["partial"], k["out"])
+            self._steps(k["cur"], 0, k["prev"], 0, 1, k["T"], k["partial"], k["out"])
             k["prev_flat"].copy_(k["cur_flat"])                 # the current frame becomes the next pair's target
 
         if not graph:
@@ -228,7 +275,7 @@ class RGBDOdometry:
             g.replay()
         else:
             k["graph"].replay()
-        return k["T"].clone()
+        return k["T"][0].clone()
 
     # ---- a block of consecutive frames at once ---------------------------------------------------------
     def track_block(self, colors_u8: torch.Tensor, depths_m: torch.Tensor, max_block: int = 64) -> torch.Tensor:
@@ -244,19 +291,8 @@ class RGBDOdometry:
         if k is None or k["hw"] != (H, W) or k["slots"] < n + 1:
             old = k if (k is not None and k["hw"] == (H, W) and k["have_prev"]) else None      # a larger block than before: keep the previous frame
             slots = max(n, max_block if n > 1 else 1) + 1
-            levels, (h, w, kk) = [], (H, W, self.K)
-            for _ in range(len(self.iterations)):
-                lv = _Level()
-                lv.H, lv.W, lv.K, lv.Kc = h, w, kk, np.array(kk, dtype=np.float64)
-                lv.I, lv.D, lv.gIx, lv.gIy, lv.gDx, lv.gDy = (torch.empty(slots, h, w, device=self.dev, dtype=torch.float32) for _ in range(6))
-                levels.append(lv)
-                h, w, kk = (h + 1) // 2, (w + 1) // 2, tuple(v / 2.0 for v in kk)
-            nblk = min((H * W + 255) // 256, 256)
-            k = self._blk = dict(hw=(H, W), slots=slots, levels=levels, have_prev=False,
-                                 T=torch.empty(slots - 1, 12, dtype=torch.float64, device=self.dev),
-                                 T0=torch.tensor([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], dtype=torch.float64, device=self.dev),
-                                 partial=torch.empty(slots - 1, nblk, 29, dtype=torch.float64, device=self.dev),
-                                 out=torch.zeros(slots - 1, 29, dtype=torch.float64, device=self.dev))
+            levels, _ = self._alloc_levels(H, W, slots)
+            k = self._blk = dict(hw=(H, W), slots=slots, levels=levels, have_prev=False, **_scratch(slots - 1, H, W, self.dev))
             if old is not None:      # (a first call with one frame allocates two slots; the next, larger block must still pair with that frame)
                 for l_new, l_old in zip(levels, old["levels"]):
                     for name in ("I", "D", "gIx", "gIy", "gDx", "gDy"):
@@ -264,28 +300,16 @@ class RGBDOdometry:
                 k["have_prev"] = True
         if n == 0:
             return torch.empty(0, 12, dtype=torch.float64, device=self.dev)
-        lib, st = L.load_library(), L.stream_ptr()
-        colors_u8, depths_m = colors_u8.contiguous(), depths_m.contiguous()
         lv = k["levels"]
-        # slot 0 holds the previous block's last frame; the n new frames go to slots 1..n
-        L.check(lib.bs_odo_prepare(L.p(colors_u8), L.p(depths_m), n, H, W, 3.0e38, L.p(lv[0].I[1]), L.p(lv[0].D[1]), st), "bs_odo_prepare")
-        for p_, n_ in zip(lv[:-1], lv[1:]):
-            L.check(lib.bs_odo_pyrdown(L.p(p_.I[1]), n, p_.H, p_.W, L.p(n_.I[1]), 0, 0.0, st), "bs_odo_pyrdown")
-            L.check(lib.bs_odo_pyrdown(L.p(p_.D[1]), n, p_.H, p_.W, L.p(n_.D[1]), 1, 2.0 * DEPTH_OUTLIER_TRUNC, st), "bs_odo_pyrdown")
-        for l_ in lv:                           # every new frame is a target, in this block or (the last one) in the next
-            L.check(lib.bs_odo_sobel(L.p(l_.I[1]), n, l_.H, l_.W, L.p(l_.gIx[1]), L.p(l_.gIy[1]), st), "bs_odo_sobel")
-            L.check(lib.bs_odo_sobel(L.p(l_.D[1]), n, l_.H, l_.W, L.p(l_.gDx[1]), L.p(l_.gDy[1]), st), "bs_odo_sobel")
+        # slot 0 holds the previous block's last frame; the n new frames go to slots 1..n.  Every new frame gets its gradients: it is a
+        # target, in this block or (the last one) in the next
+        self._build(lv, colors_u8.contiguous(), depths_m.contiguous(), 3.0e38, n, 1)
         first = 0 if k["have_prev"] else 1       # the first pair's target slot
         pairs = n - first
         T = k["T"][:max(pairs, 0)]
         if pairs > 0:
             T.copy_(k["T0"].expand(pairs, 12))
-            for level, iters in zip(range(len(lv) - 1, -1, -1), self.iterations):
-                l_ = lv[level]
-                s, t = first + 1, first
-                L.check(lib.bs_odo_step(L.p(l_.I[s]), L.p(l_.D[s]), L.p(l_.I[t]), L.p(l_.D[t]), L.p(l_.gIx[t]), L.p(l_.gIy[t]), L.p(l_.gDx[t]),
-                                        L.p(l_.gDy[t]), pairs, l_.H, l_.W, l_.Kc.ctypes.data_as(C.c_void_p), L.p(T), iters, DEPTH_OUTLIER_TRUNC,
-                                        DEPTH_HUBER, INTENSITY_HUBER, L.p(k["partial"]), L.p(k["out"]), self.flags, st), "bs_odo_step")
+            self._steps(lv, first + 1, lv, first, pairs, T, k["partial"], k["out"])
         for l_ in lv:                           # the block's last frame is the next block's first target
             for m in (l_.I, l_.D, l_.gIx, l_.gIy, l_.gDx, l_.gDy):
                 m[0].copy_(m[n])
@@ -336,16 +360,10 @@ class PointToPlaneOdometry:
         k = self._buf
         if k is not None and k["hw"] == (H, W) and k["n"] >= n:
             return k
-        levels, (h, w, kk) = [], (H, W, self.K)
-        for _ in range(len(self.iterations)):
-            levels.append(dict(H=h, W=w, Kc=np.array(kk, dtype=np.float64), D=torch.empty(2, n, h, w, device=self.dev, dtype=torch.float32),
-                               rec=torch.empty(n, h, w, 4, device=self.dev, dtype=torch.float32)))
-            h, w, kk = (h + 1) // 2, (w + 1) // 2, tuple(v / 2.0 for v in kk)
-        nblk = min((H * W + 255) // 256, 256)
-        k = self._buf = dict(hw=(H, W), n=n, levels=levels, T=torch.empty(n, 12, dtype=torch.float64, device=self.dev),
-                             T0=torch.tensor([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], dtype=torch.float64, device=self.dev),
-                             partial=torch.empty(n, nblk, 29, dtype=torch.float64, device=self.dev),
-                             out=torch.zeros(n, 29, dtype=torch.float64, device=self.dev))
+        levels = [dict(H=h, W=w, Kc=kc, D=torch.empty(2, n, h, w, device=self.dev, dtype=torch.float32),
+                       rec=torch.empty(n, h, w, 4, device=self.dev, dtype=torch.float32))
+                  for h, w, kc in _level_shapes(H, W, self.K, len(self.iterations))]
+        k = self._buf = dict(hw=(H, W), n=n, levels=levels, **_scratch(n, H, W, self.dev))
         return k
 
     def _build(self, k: dict, src: torch.Tensor, tgt: torch.Tensor, depth_max: float) -> None:
@@ -354,14 +372,14 @@ class PointToPlaneOdometry:
         n, m = src.shape[0], k["n"]
         lv = k["levels"]
         l0 = lv[0]
-        L.check(lib.bs_odo_p2p_prepare(L.p(src), n, l0["H"], l0["W"], float(depth_max), L.p(l0["D"][0]), st), "bs_odo_p2p_prepare")
-        L.check(lib.bs_odo_p2p_prepare(L.p(tgt), n, l0["H"], l0["W"], 3.0e38, L.p(l0["D"][1]), st), "bs_odo_p2p_prepare")
+        for side, (depth, dmax) in enumerate(((src, float(depth_max)), (tgt, 3.0e38))):
+            L.check(lib.bs_odo_p2p_prepare(L.p(depth), n, l0["H"], l0["W"], dmax, L.p(l0["D"][side]), st), "bs_odo_p2p_prepare")
         for p_, n_ in zip(lv[:-1], lv[1:]):
             if n == m:           # the stack is full: source and target images are contiguous, one launch
-                L.check(lib.bs_odo_pyrdown(L.p(p_["D"]), 2 * n, p_["H"], p_["W"], L.p(n_["D"]), 1, 2.0 * self.depth_diff, st), "bs_odo_pyrdown")
+                _pyrdown(L.p(p_["D"]), 2 * n, p_["H"], p_["W"], L.p(n_["D"]), 2.0 * self.depth_diff, st)
             else:
                 for side in (0, 1):
-                    L.check(lib.bs_odo_pyrdown(L.p(p_["D"][side]), n, p_["H"], p_["W"], L.p(n_["D"][side]), 1, 2.0 * self.depth_diff, st), "bs_odo_pyrdown")
+                    _pyrdown(L.p(p_["D"][side]), n, p_["H"], p_["W"], L.p(n_["D"][side]), 2.0 * self.depth_diff, st)
         for l_ in lv:
             L.check(lib.bs_odo_p2p_target(L.p(l_["D"][1]), n, l_["H"], l_["W"], l_["Kc"].ctypes.data_as(C.c_void_p), L.p(l_["rec"]), st), "bs_odo_p2p_target")
 
@@ -390,9 +408,8 @@ class PointToPlaneOdometry:
         i12 = self._init12(init, n)
         T.copy_(k["T0"].expand(n, 12) if i12 is None else torch.from_numpy(i12).to(self.dev))
         lib, st = L.load_library(), L.stream_ptr()
-        lv = k["levels"]
-        for level, iters in zip(range(len(lv) - 1, -1, -1), self.iterations):
-            l_ = lv[level]
+        for level, iters in _schedule(self.iterations):
+            l_ = k["levels"][level]
             L.check(lib.bs_odo_p2p_step(L.p(l_["D"][0]), L.p(l_["rec"]), n, l_["H"], l_["W"], l_["Kc"].ctypes.data_as(C.c_void_p), L.p(T), iters,
                                         self.depth_diff, self.depth_huber, L.p(k["partial"]), L.p(k["out"]), st), "bs_odo_p2p_step")
         self.last_sums = k["out"][:n].clone()
@@ -410,26 +427,17 @@ class PointToPlaneOdometry:
         lib, st = L.load_library(), L.stream_ptr()
         k = self._buffers(1, *src.shape[1:])
         self._build(k, src, tgt, depth_max)
-        iu = np.triu_indices(6)
-        log = []
-        lv = k["levels"]
-        for level, iters in zip(range(len(lv) - 1, -1, -1), self.iterations):
-            l_ = lv[level]
-            for _ in range(iters):
-                T12 = np.ascontiguousarray(T[:3].reshape(12))
-                L.check(lib.bs_odo_p2p_accumulate(L.p(l_["D"][0]), L.p(l_["rec"]), l_["H"], l_["W"], l_["Kc"].ctypes.data_as(C.c_void_p),
-                                                  T12.ctypes.data_as(C.c_void_p), self.depth_diff, self.depth_huber, L.p(k["partial"]), L.p(k["out"]),
-                                                  st), "bs_odo_p2p_accumulate")
-                r = k["out"][0].cpu().numpy()
-                A = np.zeros((6, 6))
-                A[iu] = r[:21]
-                A = A + np.triu(A, 1).T
-                b, cost, cnt = r[21:27], float(r[27]), int(round(r[28]))
-                log.append((level, A.copy(), b.copy(), cost, cnt))
-                if cnt >= 6:         # (fewer: the pose stays, the schedule goes on -- as the device loop does)
-                    T = se3_exp(np.linalg.solve(A + 1e-12 * np.eye(6), -b)) @ T
+
+        def sums(level, T12):
+            l_ = k["levels"][level]
+            L.check(lib.bs_odo_p2p_accumulate(L.p(l_["D"][0]), L.p(l_["rec"]), l_["H"], l_["W"], l_["Kc"].ctypes.data_as(C.c_void_p),
+                                              T12.ctypes.data_as(C.c_void_p), self.depth_diff, self.depth_huber, L.p(k["partial"]), L.p(k["out"]),
+                                              st), "bs_odo_p2p_accumulate")
+            return k["out"][0].cpu().numpy()
+
+        # (fewer than 6 inliers: the pose stays, the schedule goes on -- as the device loop does)
+        T, self.last_trace = _host_walk(T, _schedule(self.iterations), sums, starved_leaves_level=False)
         self.last_sums = k["out"][:1].clone()
-        self.last_trace = log
         return T
 
     def _dev(self, x) -> torch.Tensor:

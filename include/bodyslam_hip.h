@@ -487,7 +487,7 @@ int bs_tsdf_raycast(const double* K, const double* extrinsics, int32_t n_views, 
  *   bs_odo_sobel       3x3 Sobel / 8 in x and y, replicate borders, NaN propagates
  *   bs_odo_accumulate  the sums of one Gauss-Newton step at pose T: out29 = [21 upper-triangle terms of sum w J^T J (row-major),
  *                      6 terms of sum w J^T r, the weighted cost, the inlier count]; hybrid residuals (intensity + depth), Huber
- *                      weights, target sampled bilinearly; partial = scratch double [ceil(H*W/256), 29]; deterministic.
+ *                      weights, target sampled bilinearly; partial = scratch double [min(ceil(H*W/256), 256), 29]; deterministic.
  *                      flags bit 0: the target images are read at the NEAREST pixel of the projected point (round half away from zero),
  *                      Open3D's association; bit 1: Open3D's robust step -- sum J^T J unweighted, sum J^T huber'(r) with
  *                      huber'(r) = r clipped to +-delta, cost = sum huber(r)
@@ -534,8 +534,8 @@ int bs_odo_accumulate(const float* src_intensity, const float* src_depth, const 
  *                          J = [p x n, n] for the left twist (omega, nu); out29 = [sum J J^T (21, unweighted), sum J clip(r, +-depth_huber)
  *                          (6), sum huber(r), the inlier count]; partial = scratch double [min(ceil(H*W/256), 256), 29]; deterministic
  *   bs_odo_p2p_step        `iterations` such steps of one level on the device, as bs_odo_step: pair p of `batch` reads source image p,
- *                          target record image p, pose T_dev[12 p ..], scratch partial[p][.][29], sums out29[29 p ..]; the same finish,
- *                          6x6 solve and pose update kernels as bs_odo_step; fewer than 6 inliers leave the pose alone */
+ *                          target record image p, pose T_dev[12 p ..], scratch partial[p][.][29], sums out29[29 p ..]; the same kernel
+ *                          (fixed-order finish, 6x6 solve, pose update) as bs_odo_step; fewer than 6 inliers leave the pose alone */
 int bs_odo_p2p_prepare(const float* depth, int32_t batch, int32_t H, int32_t W, double depth_max, float* depth_out, void* stream);
 int bs_odo_p2p_target(const float* depth, int32_t batch, int32_t H, int32_t W, const double* K, float* target, void* stream);
 int bs_odo_p2p_accumulate(const float* src_depth, const float* target, int32_t H, int32_t W, const double* K, const double* T,

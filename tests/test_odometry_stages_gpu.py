@@ -405,6 +405,10 @@ def test_device_loop_equals_host_loop(flags):
         assert out_dev[i][28] == s[28]
     T_again, out_again = device_loop(dev, starts)
     assert np.array_equal(T_again, T_dev) and np.array_equal(out_again, out_dev)
+    # one step's sums are the accumulate entry's at the same pose, bit for bit: both entries reduce the partials with one kernel
+    out_one = device_loop(dev, starts, iters=1)[1]
+    for i in range(LOOP_BATCH):
+        assert np.array_equal(out_one[i], dev_accumulate(dev, i, hw, K, starts[i], flags)), i
     # a source with 5 valid pixels: no solve, the pose comes back bit for bit; its neighbour in the batch is untouched by that
     two = {k: torch.cat([dev[k][:1], dev[k][:1]]).contiguous() for k in names}
     two["Ds"] = sparse_stack(dev, "Ds", hw)
@@ -446,6 +450,9 @@ def test_p2p_device_loop_equals_host_loop():
         assert out_dev[i][28] == s[28]
     T_again, out_again = device_loop(dev["p2p_src"], dev["rec"], starts)
     assert np.array_equal(T_again, T_dev) and np.array_equal(out_again, out_dev)
+    out_one = device_loop(dev["p2p_src"], dev["rec"], starts, iters=1)[1]          # as in the hybrid test: one step's sums, bit for bit
+    for i in range(LOOP_BATCH):
+        assert np.array_equal(out_one[i], dev_p2p_accumulate(dev, i, hw, K, starts[i])), i
     src2 = sparse_stack(dev, "p2p_src", hw)
     rec2 = torch.cat([dev["rec"][:1], dev["rec"][:1]]).contiguous()
     T2, out2 = device_loop(src2, rec2, [starts[0], starts[0]])
