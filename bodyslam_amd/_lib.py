@@ -170,6 +170,19 @@ _SIGS = {
                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pc_normals": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pc_knn_mean_distance": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p],
+    # radius search and DBSCAN (csrc/radius.hip); the index arguments as for bs_pc_query_knn
+    "bs_pc_radius_count": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
+                           C.c_void_p, C.c_void_p],
+    "bs_pc_radius_fill": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
+                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_radius_sort": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_pc_radius_unpack": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_dbscan_hook": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
+                          C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_dbscan_compress": [C.c_void_p, C.c_int64, C.c_void_p],
+    "bs_pc_dbscan_roots": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_pc_dbscan_labels": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
+                            C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     # voxel down-sampling (csrc/voxel.hip); the origin is a pointer to 3 host doubles
     "bs_pc_voxel_assign": [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pc_voxel_flags": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -1020,7 +1033,88 @@ def pc_knn_mean_distance(d2, count, k, avg):
     check(load_library().bs_pc_knn_mean_distance(p(d2), p(count), m, k, p(avg), stream_ptr()), "bs_pc_knn_mean_distance")
 
 
-PC_VOXEL_AXIS_BITS, PC_VOXEL_EMPTY_KEY, PC_VOXEL_NO_POINT = 21, -1, 0x7fffffff             # (the empty key as the int64 a torch fill_ takes)
+PC_RADIUS_OVERRUN = 1
+
+
+def _pc_index(index):
+    """index: (records, n_records, cell_start, lo, hi, cell_size, dims) as for pc_query_knn -> (the leading arguments of a bs_pc_radius_* /
+    bs_pc_dbscan_* call, the host arrays that must stay alive over it)"""
+    records, n_records, cell_start, lo, hi, cell_size, dims = index
+    _i32(cell_start)
+    (lo_, lo_p), (hi_, hi_p), (d_, d_p) = _host(lo, "float32", 3), _host(hi, "float32", 3), _host(dims, "int32", 3)
+    assert records.dtype == torch.float32 and records.is_cuda and records.is_contiguous() and records.dim() == 2 and records.shape[1] == 4
+    assert cell_start.numel() == int(d_[0]) * int(d_[1]) * int(d_[2]) + 1 and 0 <= n_records <= records.shape[0]
+    return (p(records), p(cell_start), int(n_records), lo_p, hi_p, float(cell_size), d_p), (lo_, hi_, d_)
+
+
+def pc_radius_count(index, source, radius, count):
+    """index: see _pc_index; source fp32 [m, 3], count int32 [m]: on the device (include/bodyslam_hip.h)"""
+    _pts(source)
+    _i32(count)
+    assert count.numel() == source.shape[0]
+    head, alive = _pc_index(index)
+    check(load_library().bs_pc_radius_count(*head, p(source), source.shape[0], float(radius), p(count), stream_ptr()), "bs_pc_radius_count")
+
+
+def pc_radius_fill(index, source, radius, row_start, total, keys, status):
+    """row_start int64 [m + 1] (the exclusive scan of the counts, total = its last entry), keys int64 [total], status int32 [1] (zeroed)"""
+    _pts(source)
+    _i64(row_start, keys)
+    _i32(status)
+    assert row_start.numel() == source.shape[0] + 1 and keys.numel() == total >= 1 and status.numel() >= 1
+    head, alive = _pc_index(index)
+    check(load_library().bs_pc_radius_fill(*head, p(source), source.shape[0], float(radius), p(row_start), int(total), p(keys), p(status),
+                                           stream_ptr()), "bs_pc_radius_fill")
+
+
+def pc_radius_sort(keys, row_start, keys_out):
+    _i64(keys, row_start, keys_out)
+    assert keys.numel() == keys_out.numel() >= 1 and row_start.numel() >= 2 and keys.data_ptr() != keys_out.data_ptr()
+    check(load_library().bs_pc_radius_sort(p(keys), p(row_start), row_start.numel() - 1, keys.numel(), p(keys_out), stream_ptr()),
+          "bs_pc_radius_sort")
+
+
+def pc_radius_unpack(keys, index, d2):
+    _i64(keys)
+    _i32(index)
+    assert d2.dtype == torch.float32 and d2.is_cuda and d2.is_contiguous() and keys.numel() == index.numel() == d2.numel() >= 1
+    check(load_library().bs_pc_radius_unpack(p(keys), keys.numel(), p(index), p(d2), stream_ptr()), "bs_pc_radius_unpack")
+
+
+def pc_dbscan_hook(index, points, eps, count, min_points, parent, changed):
+    """points fp32 [n, 3] (the cloud the index was built over), count int32 [n] (pc_radius_count of the cloud on itself), parent int32 [n],
+    changed int32 [1]"""
+    _pts(points)
+    _i32(count, parent, changed)
+    n = points.shape[0]
+    assert count.numel() == n and parent.numel() == n and changed.numel() >= 1
+    head, alive = _pc_index(index)
+    check(load_library().bs_pc_dbscan_hook(*head, p(points), n, float(eps), p(count), int(min_points), p(parent), p(changed), stream_ptr()),
+          "bs_pc_dbscan_hook")
+
+
+def pc_dbscan_compress(parent):
+    _i32(parent)
+    check(load_library().bs_pc_dbscan_compress(p(parent), parent.numel(), stream_ptr()), "bs_pc_dbscan_compress")
+
+
+def pc_dbscan_roots(parent, count, min_points, is_root):
+    _i32(parent, count, is_root)
+    assert parent.numel() == count.numel() == is_root.numel()
+    check(load_library().bs_pc_dbscan_roots(p(parent), p(count), int(min_points), parent.numel(), p(is_root), stream_ptr()), "bs_pc_dbscan_roots")
+
+
+def pc_dbscan_labels(index, points, eps, count, min_points, parent, rank, n_clusters, labels):
+    _pts(points)
+    _i32(count, parent, rank, labels)
+    n = points.shape[0]
+    assert count.numel() == n and parent.numel() == n and rank.numel() == n and labels.numel() == n and 0 <= n_clusters <= n
+    head, alive = _pc_index(index)
+    check(load_library().bs_pc_dbscan_labels(*head, p(points), n, float(eps), p(count), int(min_points), p(parent), p(rank), int(n_clusters),
+                                             p(labels), stream_ptr()), "bs_pc_dbscan_labels")
+
+
+PC_VOXEL_AXIS_BITS, PC_VOXEL_EMPTY_KEY, PC_VOXEL_NO_POINT = 21, -1, 0x7fffffff            # (the empty key as the int64 a torch fill_ takes)
 PC_VOXEL_TABLE_FULL, PC_VOXEL_OUT_OF_RANGE, PC_VOXEL_BAD_ATTRIBUTE = 1, 2, 4
 
 

@@ -175,20 +175,6 @@ __global__ void __launch_bounds__(KNN_THREADS) pc_knn_mean_kernel(const float* _
     avg[i] = cnt ? (float)(s / (double)cnt) : __builtin_nanf("");
 }
 
-// the largest fp32 d2 with sqrtf(d2) <= radius (host arithmetic: sqrtf is correctly rounded and monotone)
-float knn_d2_cutoff(float radius) {
-    if (!(radius < INFINITY)) return INFINITY;
-    float c = radius * radius;
-    if (!(c < INFINITY)) c = 3.402823466e+38f;
-    while (c > 0.0f && sqrtf(c) > radius) c = nextafterf(c, 0.0f);
-    for (;;) {
-        const float up = nextafterf(c, INFINITY);
-        if (!(up < INFINITY) || sqrtf(up) > radius) break;
-        c = up;
-    }
-    return c;
-}
-
 }  // namespace
 }  // namespace bs
 

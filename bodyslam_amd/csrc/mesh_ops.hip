@@ -32,6 +32,7 @@
 #include "reduce.h"
 #include "slot_table.h"
 #include "triangle.h"
+#include "union_min.h"
 
 namespace bs {
 namespace {
@@ -94,17 +95,7 @@ __global__ void __launch_bounds__(MO_THREADS) edge_rows_kernel(const int32_t* __
     }
 }
 
-// ---- components ----------------------------------------------------------------------------------------------------------------------------
-// the root of x: parent[p] <= p, so every step strictly descends and there are at most n of them
-__device__ __forceinline__ int32_t cc_root(const int32_t* parent, int32_t x, int64_t n) {
-    for (int64_t step = 0; step < n; ++step) {
-        const int32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p >= x || p < 0) break;
-        x = p;
-    }
-    return x;
-}
-
+// ---- components (the root walk, the hook and the compression: union_min.h, shared with radius.hip) --------------------------------------------
 __global__ void __launch_bounds__(MO_THREADS) cc_hook_kernel(const int32_t* __restrict__ edge_of_half,
                                                              const int32_t* __restrict__ edge_first_triangle, int64_t n_triangles,
                                                              int64_t n_edges, int32_t* parent, int32_t* __restrict__ changed) {
@@ -114,17 +105,13 @@ __global__ void __launch_bounds__(MO_THREADS) cc_hook_kernel(const int32_t* __re
     if (e < 0 || e >= n_edges) return;
     const int32_t u = edge_first_triangle[e], t = (int32_t)(h / 3);
     if (u < 0 || u >= n_triangles || u == t) return;
-    const int32_t rt = cc_root(parent, t, n_triangles), ru = cc_root(parent, u, n_triangles);
-    if (rt == ru) return;
-    atomicMin(&parent[rt > ru ? rt : ru], rt > ru ? ru : rt);
-    *changed = 1;                                                    // (every writer stores the same value)
+    cc_union(parent, t, u, n_triangles, changed);
 }
 
 __global__ void __launch_bounds__(MO_THREADS) cc_compress_kernel(int32_t* parent, int64_t n_triangles) {
     const int64_t t = (int64_t)blockIdx.x * MO_THREADS + threadIdx.x;
     if (t >= n_triangles) return;
-    // a root stays a root during this launch, and every value a walk can meet lies on the path to it
-    __hip_atomic_store(&parent[t], cc_root(parent, (int32_t)t, n_triangles), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    cc_compress(parent, (int32_t)t, n_triangles);
 }
 
 __global__ void __launch_bounds__(MO_THREADS) cc_roots_kernel(const int32_t* __restrict__ parent, const int32_t* __restrict__ edge_of_half,

@@ -1,6 +1,7 @@
 // The uniform grid of the cloud-to-cloud distances and the walk over it, shared by the query (pointcloud.hip, bs_pc_query_grid), the
-// ICP step (icp.hip, bs_icp_step) and the k-nearest-neighbour query (knn.hip, bs_pc_query_knn): one copy of the cell function, the
-// candidate test, the 16-byte record load and the conservative bound, so the kernels cannot drift apart.  The arithmetic and the derivation of the bound are at the top of pointcloud.hip.
+// ICP step (icp.hip, bs_icp_step), the k-nearest-neighbour query (knn.hip, bs_pc_query_knn) and the radius search (radius.hip,
+// bs_pc_radius_*, bs_pc_dbscan_*): one copy of the cell function, the candidate test, the 16-byte record load, the conservative bound
+// and the radius cut-off, so the kernels cannot drift apart.  The arithmetic and the derivation of the bound are at the top of pointcloud.hip.
 #pragma once
 #include <math.h>
 
@@ -90,6 +91,22 @@ __device__ __forceinline__ bool pc_walk_shells(const f32x4* __restrict__ records
     best = sink.best;
     bi = sink.bi;
     return done;
+}
+
+// The radius of the hybrid search (knn.hip) and of the radius search (radius.hip) as a cut-off on d2: the largest fp32 d2 with
+// sqrtf(d2) <= radius (host arithmetic: sqrtf is correctly rounded and monotone), so d2 <= cut-off is the same predicate without a
+// square root per candidate.
+inline float knn_d2_cutoff(float radius) {
+    if (!(radius < INFINITY)) return INFINITY;
+    float c = radius * radius;
+    if (!(c < INFINITY)) c = 3.402823466e+38f;
+    while (c > 0.0f && sqrtf(c) > radius) c = nextafterf(c, 0.0f);
+    for (;;) {
+        const float up = nextafterf(c, INFINITY);
+        if (!(up < INFINITY) || sqrtf(up) > radius) break;
+        c = up;
+    }
+    return c;
 }
 
 inline bool pc_grid_ok(const PcGrid& g) {

@@ -24,7 +24,11 @@ mapping_module.py:72,156,187).  Restated, parity with Open3D unpinned; the state
 (csrc/mesh_scene.hip: integer weights, an integer scan, a counter-based hash -- a sample depends on (seed, its number) alone).  Restated,
 parity with Open3D unpinned; the statement is tests/_mesh_scene_ref.py.  Distances to the surface itself: bodyslam_amd/raycasting.py.
 
-Not built: pure radius search with an unbounded list, orientation propagation, k > 32, Open3D's cubic-id trace format, Poisson-disk
+``query_radius`` / ``count_radius`` drop the cap on the list: every target point within a radius, however many (csrc/radius.hip; Open3D's
+search_radius_vector_3d), and on them stand ``remove_radius_outlier`` (PointCloud.remove_radius_outlier) and ``cluster_dbscan``
+(PointCloud.cluster_dbscan, made deterministic).  Restated, parity with Open3D unpinned; the statement is tests/_radius_ref.py.
+
+Not built: orientation propagation, k > 32, Open3D's cubic-id trace format, Poisson-disk
 sampling of a mesh.
 """
 from __future__ import annotations
@@ -67,6 +71,11 @@ def _check_radius(radius) -> float:
     if radius is None:
         return math.inf
     return AR.number(radius, "radius", "None or a positive number (finite and non-zero in fp32)", AR.positive, fp32=True)
+
+
+def _check_search_radius(radius, what: str = "radius") -> float:
+    """a radius search needs its radius: a positive number, finite and non-zero in fp32"""
+    return AR.number(radius, what, "a positive number (finite and non-zero in fp32)", AR.positive, fp32=True)
 
 
 def _check_orientation(direction, camera_location) -> Tuple[int, Optional[np.ndarray]]:
@@ -112,6 +121,15 @@ def default_cell_size(lo: np.ndarray, hi: np.ndarray, n: int) -> float:
     return h
 
 
+def radius_cell_size(lo: np.ndarray, hi: np.ndarray, radius: float) -> float:
+    """The default edge of an index that is searched with one radius: the radius itself (one shell of cells then covers the search), rounded
+    to fp32, then grown by factors of 1.25 until the grid holds at most 2^24 cells."""
+    h = float(np.float32(radius))
+    while n_cells(grid_dims(lo, hi, h)) > L.PC_MAX_CELLS:
+        h = float(np.float32(h * 1.25))
+    return h
+
+
 def _decode_bounds(raw: np.ndarray) -> Tuple[np.ndarray, np.ndarray, int]:
     """bs_pc_bounds' 8 words -> (lo fp32 [3], hi fp32 [3], finite points)"""
     o = raw.astype(np.uint32).copy()
@@ -127,9 +145,21 @@ class NearestNeighbours:
     target: numpy array or torch tensor [n, 3], fp32 or fp64 (fp64 is rounded to fp32 once, before anything else: the neighbours are
     those of the rounded points), host or device; a tsdf.PointCloud; a tsdf.TriangleMesh (its vertices).  Non-finite target points are
     left out; indices always refer to `target` as given.  cell_size: the grid's edge, None = default_cell_size; a ValueError if the grid
-    would exceed 2^24 cells.  The cell size changes the time, never the result."""
+    would exceed 2^24 cells.  The cell size changes the time, never the result.  ``for_radius`` builds the index with the default cell of a
+    radius search."""
 
     def __init__(self, target, cell_size: Optional[float] = None, device: int = 0):
+        self._build(target, cell_size, device, None)
+
+    @classmethod
+    def for_radius(cls, target, radius: float, cell_size: Optional[float] = None, device: int = 0) -> "NearestNeighbours":
+        """The index for searches with one radius: as the constructor, but cell_size None means radius_cell_size -- the radius itself, as far
+        as the grid allows, so that one shell of cells covers a search -- instead of default_cell_size."""
+        nn = object.__new__(cls)
+        nn._build(target, cell_size, device, _check_search_radius(radius))
+        return nn
+
+    def _build(self, target, cell_size, device, r):
         t = as_points(target, "target")
         h = _check_cell_size(cell_size)
         self.dev = AR.device_for(t, device=device)
@@ -141,7 +171,7 @@ class NearestNeighbours:
             if n_finite == 0:
                 lo, hi = np.zeros(3, np.float32), np.zeros(3, np.float32)
             self.lo, self.hi, self.n_finite = lo, hi, n_finite
-            self.cell_size = default_cell_size(lo, hi, n_finite) if h is None else h
+            self.cell_size = h if h is not None else default_cell_size(lo, hi, n_finite) if r is None else radius_cell_size(lo, hi, r)
             dims = grid_dims(lo, hi, self.cell_size)
             if n_cells(dims) > L.PC_MAX_CELLS:
                 raise ValueError(f"cell_size {self.cell_size}: a grid of {dims[0]} x {dims[1]} x {dims[2]} cells, at most 2^24")
@@ -200,7 +230,7 @@ class NearestNeighbours:
         the radius is in).  Rows are padded with index -1 and d2 +inf; a source point with a non-finite coordinate gets count 0, index
         -1 and d2 NaN.  A source that is a point of the target finds itself first (d2 = 0).  1 <= k <= 32; for k = 1 the result is
         ``query``'s.  The walk has no shell cap and no brute-force fallback: a source far from every target, or a k above the number of
-        targets in reach, costs time and never changes the result.  Pure radius search with an unbounded list is not built."""
+        targets in reach, costs time and never changes the result.  Every neighbour within a radius, however many: ``query_radius``."""
         k = _check_k(k)
         r = _check_radius(radius)
         s = as_points(source, "source")
@@ -212,6 +242,132 @@ class NearestNeighbours:
             count = torch.empty(m, dtype=torch.int32, device=self.dev)
             L.pc_query_knn(self.records, self.n_finite, self.cell_start, self.lo, self.hi, self.cell_size, self.dims, s, k, r, index, d2, count)
         return index, d2, count
+
+    def _index(self):
+        return self.records, self.n_finite, self.cell_start, self.lo, self.hi, self.cell_size, self.dims
+
+    def count_radius(self, source, radius: float) -> torch.Tensor:
+        """-> count int32 [m], a device tensor: for every source point the number of finite target points within `radius` -- sqrtf(d2) <=
+        radius in ``query``'s fp32 arithmetic, a target at exactly the radius is in; 0 for a source with a non-finite coordinate.  One
+        launch (csrc/radius.hip, bs_pc_radius_count); the walk ends when its shells cover the radius."""
+        r = _check_search_radius(radius)
+        s = as_points(source, "source")
+        with torch.cuda.device(self.dev):
+            s = s.to(self.dev).to(torch.float32).contiguous()
+            count = torch.empty(int(s.shape[0]), dtype=torch.int32, device=self.dev)
+            L.pc_radius_count(self._index(), s, r, count)
+        return count
+
+    def query_radius(self, source, radius: float, max_nn: Optional[int] = None, sort: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """-> (row_start int64 [m + 1], index int32 [total], d2 fp32 [total]), device tensors: for every source point ALL the target points
+        within `radius`, however many -- Open3D's KDTreeFlann.search_radius_vector_3d (restated, parity unpinned; the statement is
+        tests/_radius_ref.py).  Source i owns the entries row_start[i] .. row_start[i + 1] - 1.
+
+        The rule is ``count_radius``'s; indices refer to the target as given.  Rows are in ascending (d2, index) order, ``query_knn``'s
+        order: a source that is a point of the target finds itself first (d2 = 0).  sort=False skips the sort: the rows are then the same
+        sets in an unspecified order.  max_nn keeps the first max_nn of every sorted row (it implies the sort).  A count launch, a scan,
+        a fill launch, the sort and an unpack launch; total must stay below 2^31 (ValueError naming it, before anything is filled)."""
+        r = _check_search_radius(radius)
+        k = None if max_nn is None else AR.integer(max_nn, "max_nn", 1)
+        s = as_points(source, "source")
+        with torch.cuda.device(self.dev):
+            s = s.to(self.dev).to(torch.float32).contiguous()
+            m = int(s.shape[0])
+            count = torch.empty(m, dtype=torch.int32, device=self.dev)
+            L.pc_radius_count(self._index(), s, r, count)
+            row_start = torch.zeros(m + 1, dtype=torch.int64, device=self.dev)
+            row_start[1:] = torch.cumsum(count, 0, dtype=torch.int64)                          # the scan is plumbing: integer, exact
+            total = int(row_start[-1].cpu())
+            if total >= 2 ** 31:
+                raise ValueError(f"radius {radius!r}: {total} neighbours in all, the lists hold fewer than 2^31; query fewer sources at a time")
+            index = torch.empty(total, dtype=torch.int32, device=self.dev)
+            d2 = torch.empty(total, dtype=torch.float32, device=self.dev)
+            if total == 0:
+                return row_start, index, d2
+            keys = torch.empty(total, dtype=torch.int64, device=self.dev)
+            status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            L.pc_radius_fill(self._index(), s, r, row_start, total, keys, status)
+            if sort or k is not None:
+                ordered = torch.empty_like(keys)
+                L.pc_radius_sort(keys, row_start, ordered)
+                keys = ordered
+            if int(status.cpu()):
+                raise L.BodySlamHipError(f"query_radius: a row found more neighbours than were counted (status {int(status.cpu())})")
+            if k is not None:                                                                   # a second scan and a gather: plumbing
+                kept = count.clamp(max=k).to(torch.int64)
+                start = torch.zeros(m + 1, dtype=torch.int64, device=self.dev)
+                start[1:] = torch.cumsum(kept, 0)
+                rows = torch.repeat_interleave(torch.arange(m, device=self.dev), kept)
+                keys = keys[torch.arange(rows.numel(), device=self.dev) - start[rows] + row_start[rows]].contiguous()
+                row_start = start
+                index, d2 = index[:keys.numel()].contiguous(), d2[:keys.numel()].contiguous()
+            L.pc_radius_unpack(keys, index, d2)
+        return row_start, index, d2
+
+
+last_rounds = 0                 # cluster_dbscan: the (hook, compress) rounds of the last call, the confirming one included
+last_clusters = 0               # cluster_dbscan: the clusters of the last call
+
+
+def remove_radius_outlier(points, nb_points: int, radius: float, cell_size: Optional[float] = None,
+                          device: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (the kept indices int64 ascending, the mask bool [n]), device tensors: Open3D's PointCloud.remove_radius_outlier (restated, parity
+    unpinned; tests/_radius_ref.py).  A point is kept when the number of points of the cloud within `radius` of it, itself included
+    (``count_radius`` of the cloud on itself), is > nb_points; a non-finite point is never kept.  nb_points >= 0, with no upper limit.
+    cell_size None: radius_cell_size.  One count launch.  Raises ValueError on bad arguments before the GPU is touched."""
+    nb = AR.integer(nb_points, "nb_points", 0)
+    r = _check_search_radius(radius)
+    _check_cell_size(cell_size)
+    as_points(points, "points")
+    nn = NearestNeighbours.for_radius(points, r, cell_size=cell_size, device=device)
+    with torch.cuda.device(nn.dev):
+        mask = nn.count_radius(nn.target, r) > nb                         # (the compaction is plumbing: a comparison and torch.nonzero)
+        return torch.nonzero(mask).reshape(-1), mask
+
+
+def cluster_dbscan(points, eps: float, min_points: int, cell_size: Optional[float] = None, device: int = 0) -> torch.Tensor:
+    """-> labels int32 [n], a device tensor, -1 for noise: Open3D's PointCloud.cluster_dbscan, made deterministic (restated, parity
+    unpinned; tests/_radius_ref.py).  ``last_clusters`` and ``last_rounds`` hold the number of clusters and the rounds the labelling took.
+
+    With ``count_radius``'s rule for "within eps": a finite point is CORE when it has at least min_points points within eps, itself
+    included.  The clusters are the connected components of the core points under "within eps", numbered 0, 1, ... in ascending order of
+    their smallest core index.  A finite non-core point with a core point within eps is a BORDER: it takes the smallest cluster number
+    among those core points (not the nearest one's).  Everything else, and every non-finite point, is noise.  This is what the textbook
+    scan gives when it visits the points in ascending index order; the result does not depend on any schedule.
+
+    csrc/radius.hip: a count launch, then rounds of (hook the core neighbours by minimum, compress) until nothing changes -- the
+    neighbourhood is walked again every round, memory stays O(n) -- then the roots, a scan and the labels.  cell_size None:
+    radius_cell_size.  Raises ValueError on bad arguments before the GPU is touched."""
+    global last_rounds, last_clusters
+    r = _check_search_radius(eps, "eps")
+    mp = AR.integer(min_points, "min_points", 1, 2 ** 31 - 1)
+    _check_cell_size(cell_size)
+    as_points(points, "points")
+    nn = NearestNeighbours.for_radius(points, r, cell_size=cell_size, device=device)
+    n, idx = len(nn), nn._index()
+    with torch.cuda.device(nn.dev):
+        i32 = dict(dtype=torch.int32, device=nn.dev)
+        count = nn.count_radius(nn.target, r)
+        parent = torch.arange(n, **i32)
+        changed = torch.zeros(1, **i32)
+        rounds = 0
+        for _ in range(n + 1):                       # every round that reports a change removes a root for good: at most n do
+            changed.zero_()
+            L.pc_dbscan_hook(idx, nn.target, r, count, mp, parent, changed)
+            L.pc_dbscan_compress(parent)
+            rounds += 1
+            if int(changed.cpu()) == 0:
+                break
+        else:
+            raise L.BodySlamHipError(f"cluster_dbscan: no fixed point after {n + 1} rounds")
+        is_root = torch.empty(n, **i32)
+        L.pc_dbscan_roots(parent, count, mp, is_root)
+        rank = torch.cumsum(is_root, 0).to(torch.int32)                   # the scan is plumbing: integer, exact
+        clusters = int(rank[-1].cpu())
+        labels = torch.empty(n, **i32)
+        L.pc_dbscan_labels(idx, nn.target, r, count, mp, parent, rank, clusters, labels)
+    last_rounds, last_clusters = rounds, clusters
+    return labels
 
 
 def estimate_normals(points, k: int = 30, radius: Optional[float] = None, direction=None, camera_location=None,

@@ -92,13 +92,32 @@ class PointCloud:
         rule; restated, parity with Open3D unpinned."""
         from .pointcloud import remove_statistical_outlier
         ind, _ = remove_statistical_outlier(self.points, nb_neighbors=nb_neighbors, std_ratio=std_ratio)
+        return self._kept(ind)
 
+    def _kept(self, ind):
+        """(the PointCloud of the rows `ind` (a device tensor), `ind`): numpy for a numpy cloud, device tensors otherwise"""
         def rows(a):
             if a is None:
                 return None
             return a[ind.cpu().numpy()] if isinstance(a, np.ndarray) else a[ind.to(a.device)]
         ind_out = ind.cpu().numpy() if isinstance(self.points, np.ndarray) else ind
         return PointCloud(rows(self.points), rows(self.colors), rows(self.normals)), ind_out
+
+    def remove_radius_outlier(self, nb_points: int, radius: float):
+        """o3d.geometry.PointCloud.remove_radius_outlier -> (the PointCloud of the kept rows, their indices int64 ascending), as
+        remove_statistical_outlier returns them: a point stays when more than nb_points points of the cloud, itself included, lie within
+        `radius` of it.  pointcloud.remove_radius_outlier states the rule; restated, parity with Open3D unpinned."""
+        from .pointcloud import remove_radius_outlier
+        ind, _ = remove_radius_outlier(self.points, nb_points=nb_points, radius=radius)
+        return self._kept(ind)
+
+    def cluster_dbscan(self, eps: float, min_points: int):
+        """o3d.geometry.PointCloud.cluster_dbscan -> labels int32 [M], -1 for noise: numpy for a numpy cloud, a device tensor otherwise.
+        Deterministic: clusters are numbered by their smallest core point, a border point takes the smallest cluster number among its core
+        neighbours.  pointcloud.cluster_dbscan states the rule; restated, parity with Open3D unpinned."""
+        from .pointcloud import cluster_dbscan
+        labels = cluster_dbscan(self.points, eps=eps, min_points=min_points)
+        return labels.cpu().numpy() if isinstance(self.points, np.ndarray) else labels
 
     def voxel_down_sample(self, voxel_size: float) -> "PointCloud":
         """o3d.geometry.PointCloud.voxel_down_sample: one point per occupied cube of edge voxel_size, with the mean position, colour and

@@ -679,8 +679,8 @@ int bs_pc_stats(const float* dist, int64_t n, const float* thresholds, int32_t n
  *                   the k lexicographically smallest (d2, original target index) among the finite target points, ascending.  With a radius
  *                   (hybrid search; +inf: none) a candidate counts only when sqrtf(d2) <= radius, compared in fp32 -- the comparison
  *                   max_distance uses; a target at exactly the radius is in.  A source that is the target's own point finds itself first
- *                   (d2 = 0), as in Open3D.  1 <= k <= BS_PC_KNN_MAX.  For k = 1 the result is bs_pc_query_grid's.  Pure radius search
- *                   with an unbounded list is not built
+ *                   (d2 = 0), as in Open3D.  1 <= k <= BS_PC_KNN_MAX.  For k = 1 the result is bs_pc_query_grid's.  Every neighbour
+ *                   within a radius, however many: bs_pc_radius_* below
  *   bs_pc_query_knn one thread per source [m, 3] fp32 (device) over the index of bs_pc_grid_scatter: the Chebyshev shells of
  *                   bs_pc_query_grid (the same device function) keeping the k best in registers, until the list is full and its worst d2
  *                   is strictly below the square of the bound on everything unvisited, every cell has been seen, or the shell covers
@@ -712,6 +712,60 @@ int bs_pc_query_knn(const void* records, const int32_t* cell_start, int64_t n_re
 int bs_pc_normals(const float* points, int64_t n, const int32_t* index, const int32_t* count, int32_t k, int32_t orientation,
                   const double* vector, float* normals, double* eigenvalues, void* stream);
 int bs_pc_knn_mean_distance(const float* d2, const int32_t* count, int64_t m, int32_t k, float* avg, void* stream);
+
+/* ---- radius search: neighbour lists, radius outliers, DBSCAN ----------------------------------------------------------------------------
+ * bs_pc_radius_* replace Open3D's KDTreeFlann.search_radius_vector_3d and, with the caller's comparison, PointCloud.remove_radius_outlier;
+ * bs_pc_dbscan_* replace PointCloud.cluster_dbscan.  Restated from Open3D's documented meaning; parity with Open3D is UNPINNED.  The
+ * statement is tests/_radius_ref.py, DESIGN section 3.22 the argument.
+ *   neighbours      the arithmetic of the blocks above: d2 = (dx dx + dy dy) + dz dz in fp32, no contraction; a finite target point is a
+ *                   neighbour of a finite source when sqrtf(d2) <= radius in fp32 (a target at exactly the radius is in), decided as
+ *                   d2 <= cut-off with the largest such d2 found on the host, as bs_pc_query_knn does.  A source with a non-finite
+ *                   coordinate has no neighbours.  Indices refer to the target as given.  Every kernel here runs one thread per source
+ *                   over the index of bs_pc_grid_scatter with the walk of bs_pc_query_grid (the same device function), no shell cap: it
+ *                   ends when the shell covers the radius or every cell has been seen, so a source far from every target costs a few
+ *                   shells and the cell size changes the time only
+ *   bs_pc_radius_count    count int32 [m]: the neighbours of every source
+ *   bs_pc_radius_fill     row_start int64 [m + 1] is the caller's exclusive scan of the counts, total = row_start[m] < 2^31; every source
+ *                   writes the keys (d2 bits << 32 | index) of its neighbours to keys [row_start[i], row_start[i + 1]) in walk order.
+ *                   A row whose bounds are not 0 <= row_start[i] <= row_start[i + 1] <= total, or that finds more neighbours than its
+ *                   segment holds, writes nothing beyond it and sets BS_PC_RADIUS_OVERRUN in status int32 [1] (the caller zeroes it);
+ *                   with counts from the same index and radius this does not happen
+ *   bs_pc_radius_sort     one wave per row: keys_out [row] = the row's keys ascending -- ascending (d2, index), d2 >= 0, the order of
+ *                   bs_pc_query_knn.  The keys of a row are distinct (the index half), so the order is total and does not depend on the
+ *                   walk.  Rows of at most 64 keys go through a compare-exchange network over the wave, longer ones by rank counting
+ *                   (keys_out[number of keys below mine] = mine).  keys_out must not alias keys
+ *   bs_pc_radius_unpack   index int32 [total], d2 fp32 [total] from the keys
+ *   DBSCAN          over a cloud queried on itself with count = bs_pc_radius_count(points, eps): a point is CORE when
+ *                   count >= min_points (itself included; a non-finite point has count 0).  Clusters are the connected components of
+ *                   the core points under "d2 <= cut-off", numbered 0, 1, ... in ascending order of their smallest core index.  A finite
+ *                   non-core point with a core neighbour is a BORDER and takes the smallest cluster number among its core neighbours;
+ *                   everything else is noise, label -1.  Deterministic: it is what the sequential scan in ascending index order gives
+ *   bs_pc_dbscan_hook     parent int32 [n] starts as 0 .. n - 1; one thread per core point walks its neighbourhood and, for every core
+ *                   neighbour of lower index, hooks the two roots by minimum as bs_mesh_cc_hook does (the same device function) and sets
+ *                   changed int32 [1]
+ *   bs_pc_dbscan_compress parent[i] = root(i).  The caller repeats (zero changed, hook, compress) until changed stays 0: at most n rounds
+ *                   report a change.  Then parent[i] of a core point is the smallest core index of its component
+ *   bs_pc_dbscan_roots    is_root int32 [n] = (i is core and parent[i] == i); the caller scans it inclusively: rank int32 [n], C = rank[n - 1]
+ *   bs_pc_dbscan_labels   labels int32 [n]: a core point rank[parent[i]] - 1; any other finite point walks its neighbourhood and takes the
+ *                   minimum of rank[parent[j]] - 1 over its core neighbours j, -1 without one; a non-finite point -1
+ * No floating-point atomics and no LDS; every index read from memory is checked before it is used: the same bits in every run, for every
+ * cell size. */
+#define BS_PC_RADIUS_OVERRUN 1
+int bs_pc_radius_count(const void* records, const int32_t* cell_start, int64_t n_records, const float* lo, const float* hi, float cell_size,
+                       const int32_t* dims, const float* source, int64_t m, float radius, int32_t* count, void* stream);
+int bs_pc_radius_fill(const void* records, const int32_t* cell_start, int64_t n_records, const float* lo, const float* hi, float cell_size,
+                      const int32_t* dims, const float* source, int64_t m, float radius, const int64_t* row_start, int64_t total, void* keys,
+                      int32_t* status, void* stream);
+int bs_pc_radius_sort(const void* keys, const int64_t* row_start, int64_t m, int64_t total, void* keys_out, void* stream);
+int bs_pc_radius_unpack(const void* keys, int64_t total, int32_t* index, float* d2, void* stream);
+int bs_pc_dbscan_hook(const void* records, const int32_t* cell_start, int64_t n_records, const float* lo, const float* hi, float cell_size,
+                      const int32_t* dims, const float* points, int64_t n, float eps, const int32_t* count, int32_t min_points, int32_t* parent,
+                      int32_t* changed, void* stream);
+int bs_pc_dbscan_compress(int32_t* parent, int64_t n, void* stream);
+int bs_pc_dbscan_roots(const int32_t* parent, const int32_t* count, int32_t min_points, int64_t n, int32_t* is_root, void* stream);
+int bs_pc_dbscan_labels(const void* records, const int32_t* cell_start, int64_t n_records, const float* lo, const float* hi, float cell_size,
+                        const int32_t* dims, const float* points, int64_t n, float eps, const int32_t* count, int32_t min_points,
+                        const int32_t* parent, const int32_t* rank, int64_t n_clusters, int32_t* labels, void* stream);
 
 /* ---- voxel down-sampling -----------------------------------------------------------------------------------------------------------------
  * The four bs_pc_voxel_* launches replace Open3D's PointCloud.voxel_down_sample, which the reference calls at
