@@ -219,6 +219,16 @@ _SIGS = {
     "bs_icp_step": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                     C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_icp_finish": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p],
+    # global registration (csrc/global_registration.hip); every pointer is a device pointer
+    "bs_fpfh_spfh": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_fpfh_features": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_feature_match": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p],
+    "bs_gr_hypotheses": [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_gr_score": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p],
+    "bs_gr_winner": [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p],
+    "bs_gr_winner_fit": [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32, C.c_double, C.c_double, C.c_void_p, C.c_void_p],
+    "bs_gr_refit_step": [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_gr_refit_finish": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
 }
 EXPORTS = sorted(list(_SIGS) + ["bs_last_error"])
 
@@ -1215,6 +1225,102 @@ def icp_finish(partial, m, lo, hi, estimation, mode, max_iteration, relative_fit
     assert partial.numel() >= -(-m // ICP_BLOCK) * ICP_PARTIAL_FIELDS and state.numel() >= ICP_STATE_FIELDS + ICP_LOG_FIELDS * int(max_iteration)
     check(load_library().bs_icp_finish(p(partial), int(m), lo_p, hi_p, int(estimation), int(mode), int(max_iteration), float(relative_fitness),
                                        float(relative_rmse), p(state), stream_ptr()), "bs_icp_finish")
+
+
+# ---- global registration (csrc/global_registration.hip) ---------------------------------------------------------------------------------
+FPFH_DIM, FPFH_ROW, GR_STATE_FIELDS, GR_PARTIAL_FIELDS, GR_BLOCK = 33, 36, 16, 17, 256
+
+
+def _lists(n, row_start, index, d2, first):
+    _i64(row_start)
+    _i32(index)
+    m = row_start.numel() - 1
+    assert d2.dtype == torch.float32 and d2.is_cuda and d2.is_contiguous() and d2.numel() == index.numel()
+    assert m >= 1 and 0 <= first and first + m <= n
+    return m
+
+
+def fpfh_spfh(table, row_start, index, d2, first, spfh):
+    """table fp32 [n, 8] = (x, y, z, ., nx, ny, nz, .); row_start int64 [m + 1], index int32 [total], d2 fp32 [total]: the sorted radius lists of
+    the points first .. first + m - 1; spfh int32 [n, FPFH_ROW]: on the device (include/bodyslam_hip.h)"""
+    n = table.shape[0]
+    _f32(table, n, 8)
+    assert spfh.dtype == torch.int32 and spfh.is_cuda and spfh.is_contiguous() and tuple(spfh.shape) == (n, FPFH_ROW)
+    m = _lists(n, row_start, index, d2, first)
+    check(load_library().bs_fpfh_spfh(p(table), n, p(row_start), p(index), p(d2), m, int(first), index.numel(), p(spfh), stream_ptr()), "bs_fpfh_spfh")
+
+
+def fpfh_features(spfh, row_start, index, d2, first, features):
+    """spfh int32 [n, FPFH_ROW] (complete: every neighbour's row is read), the lists as for fpfh_spfh, features fp32 [n, FPFH_DIM]"""
+    n = spfh.shape[0]
+    assert spfh.dtype == torch.int32 and spfh.is_cuda and spfh.is_contiguous() and tuple(spfh.shape) == (n, FPFH_ROW)
+    _f32(features, n, FPFH_DIM)
+    m = _lists(n, row_start, index, d2, first)
+    check(load_library().bs_fpfh_features(p(spfh), n, p(row_start), p(index), p(d2), m, int(first), index.numel(), p(features), stream_ptr()),
+          "bs_fpfh_features")
+
+
+def feature_match(source, target, splits, best):
+    """source fp32 [m, FPFH_DIM], target fp32 [n, FPFH_DIM], best int64 [m] filled with -1 (all bits set)"""
+    m, n = source.shape[0], target.shape[0]
+    _f32(source, m, FPFH_DIM)
+    _f32(target, n, FPFH_DIM)
+    _i64(best)
+    assert best.numel() == m
+    check(load_library().bs_feature_match(p(source), m, p(target), n, int(splits), p(best), stream_ptr()), "bs_feature_match")
+
+
+def _corr(corr):
+    _f64(corr)
+    assert corr.dim() == 2 and corr.shape[1] == 6
+    return corr.shape[0]
+
+
+def gr_hypotheses(corr, seed, h0, count, edge_length_threshold, tau, fits, valid):
+    c = _corr(corr)
+    _f64(fits)
+    _i32(valid)
+    assert fits.numel() >= 12 * count and valid.numel() >= count
+    check(load_library().bs_gr_hypotheses(p(corr), c, int(seed), int(h0), int(count), float(edge_length_threshold), float(tau), p(fits), p(valid),
+                                          stream_ptr()), "bs_gr_hypotheses")
+
+
+def gr_score(corr, fits, valid_list, count, splits, tau, score):
+    c = _corr(corr)
+    _f64(fits)
+    _i32(valid_list, score)
+    assert fits.numel() >= 12 * count and score.numel() >= count and 1 <= valid_list.numel() <= count
+    check(load_library().bs_gr_score(p(corr), c, p(fits), p(valid_list), valid_list.numel(), int(count), int(splits), float(tau), p(score),
+                                     stream_ptr()), "bs_gr_score")
+
+
+def gr_winner(score, count, h0, best):
+    _i32(score)
+    _i64(best)
+    assert score.numel() >= count and best.numel() == 1
+    check(load_library().bs_gr_winner(p(score), int(count), int(h0), p(best), stream_ptr()), "bs_gr_winner")
+
+
+def gr_winner_fit(corr, seed, h, edge_length_threshold, tau, state):
+    c = _corr(corr)
+    _f64(state)
+    assert state.numel() >= GR_STATE_FIELDS
+    check(load_library().bs_gr_winner_fit(p(corr), c, int(seed), int(h), float(edge_length_threshold), float(tau), p(state), stream_ptr()),
+          "bs_gr_winner_fit")
+
+
+def gr_refit_step(corr, state, tau, mask, partial):
+    c = _corr(corr)
+    _f64(state, partial)
+    _i32(mask)
+    assert mask.numel() == c and partial.numel() >= -(-c // GR_BLOCK) * GR_PARTIAL_FIELDS and state.numel() >= GR_STATE_FIELDS
+    check(load_library().bs_gr_refit_step(p(corr), c, p(state), float(tau), p(mask), p(partial), stream_ptr()), "bs_gr_refit_step")
+
+
+def gr_refit_finish(partial, c, final_round, state):
+    _f64(state, partial)
+    assert partial.numel() >= -(-c // GR_BLOCK) * GR_PARTIAL_FIELDS and state.numel() >= GR_STATE_FIELDS
+    check(load_library().bs_gr_refit_finish(p(partial), int(c), 1 if final_round else 0, p(state), stream_ptr()), "bs_gr_refit_finish")
 
 
 # ---- triangle-mesh scene (csrc/mesh_scene.hip) ------------------------------------------------------------------------------------------

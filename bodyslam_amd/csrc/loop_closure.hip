@@ -15,7 +15,7 @@
 //   bs_loop_register      register_kernel, one block per pair:
 //     1 correspondences   the matches with distance <= max_hamming whose two points are valid, compacted in match order (block scan)
 //     2 hypotheses        one thread per hypothesis h (strided): three distinct indices from a counter-based integer hash of
-//                         (seed, pair, h, draw) -- loop_draw below, no RNG state --, Kabsch, score = #(|R p + t - q| < tau)
+//                         (seed, pair, h, draw) -- loop_draw in ransac3.h, no RNG state --, Kabsch, score = #(|R p + t - q| < tau)
 //     3 winner            the highest score, the lowest h among equals; a best score below 3 rejects the pair
 //     4 refit             n_refit rounds of Kabsch (rigid3.h) over the current inliers + recount.  Centroids and covariance are block sums
 //                         in a fixed order (thread-strided partial sums, then reduce.h's block_sum): no atomics, same bits in every run
@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "orb_match.h"
+#include "ransac3.h"
 #include "reduce.h"
 #include "rigid3.h"
 
@@ -39,7 +40,7 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 constexpr int LC_THREADS = ORB_THREADS;
 constexpr int LC_WAVES = LC_THREADS / 64;
-constexpr double LC_RANK_EPS = 1e-12;       // m^2: a sample / inlier set whose (summed) cross-covariance has a second singular value below this is collinear
+constexpr double LC_RANK_EPS = RANSAC3_RANK_EPS;
 
 // ---- bs_orb_lift ------------------------------------------------------------------------------------------------------------------------
 // xyz [batch, ORB_KP, 4] fp64 = (x, y, z, valid 0.0 / 1.0); rows at and behind a frame's count are zero
@@ -77,59 +78,22 @@ __global__ void __launch_bounds__(ORB_THREADS) match_pairs_kernel(const uint32_t
 }
 
 // ---- bs_loop_register -------------------------------------------------------------------------------------------------------------------
-// splitmix64's finaliser over a counter: draw `draw` (0, 1, 2) of hypothesis h of pair `pair`; the high 32 bits are the draw
-__device__ __forceinline__ uint32_t loop_draw(uint64_t seed, uint32_t pair, uint32_t h, uint32_t draw) {
-    uint64_t z = (seed ^ ((uint64_t)pair * 0xD6E8FEB86659FD93ull)) + 0x9E3779B97F4A7C15ull * ((uint64_t)h * 3ull + draw + 1ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (uint32_t)(z >> 32);
-}
-// three distinct indices below C (C >= 3): i0 = r0 % C, i1 = r1 % (C - 1), i2 = r2 % (C - 2), each shifted past the earlier picks
-__device__ __forceinline__ void loop_sample(uint64_t seed, uint32_t pair, uint32_t h, int C, int (&idx)[3]) {
-    const int i0 = (int)(loop_draw(seed, pair, h, 0) % (uint32_t)C);
-    int i1 = (int)(loop_draw(seed, pair, h, 1) % (uint32_t)(C - 1));
-    int i2 = (int)(loop_draw(seed, pair, h, 2) % (uint32_t)(C - 2));
-    if (i1 >= i0) ++i1;
-    const int lo = min(i0, i1), hi = max(i0, i1);
-    if (i2 >= lo) ++i2;
-    if (i2 >= hi) ++i2;
-    idx[0] = i0; idx[1] = i1; idx[2] = i2;
-}
-
-// |R p + t - q|^2
-__device__ __forceinline__ double residual2(const Rigid3& g, double px, double py, double pz, double qx, double qy, double qz) {
-    const double ex = (((g.r[0] * px + g.r[1] * py) + g.r[2] * pz) + g.t[0]) - qx;
-    const double ey = (((g.r[3] * px + g.r[4] * py) + g.r[5] * pz) + g.t[1]) - qy;
-    const double ez = (((g.r[6] * px + g.r[7] * py) + g.r[8] * pz) + g.t[2]) - qz;
-    return (ex * ex + ey * ey) + ez * ez;
-}
-
+// loop_draw, loop_sample, residual2, sample_fit3: ransac3.h, shared with global_registration.hip (the same draw, the same fit, moved there as
+// they stood).
 // Kabsch (rigid3.h) over the three-point sample of hypothesis h, from the correspondences in LDS.  false: the second singular value of the
 // sample's cross-covariance is below LC_RANK_EPS (collinear or coincident points); g is then left alone.
 __device__ __forceinline__ bool lc_sample_fit(uint64_t seed, uint32_t pair, uint32_t h, int C, const f64x2* s_xy, const f64x2* s_zm, const f64x2* d_xy,
                                               const f64x2* d_zw, Rigid3& g) {
     int id[3];
     loop_sample(seed, pair, h, C, id);
-    double s[15];
-#pragma unroll
-    for (int k = 0; k < 15; ++k) s[k] = 0.0;
+    double pp[3][3], qq[3][3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const f64x2 a0 = s_xy[id[k]], a1 = s_zm[id[k]], b0 = d_xy[id[k]], b1 = d_zw[id[k]];
-        const double pp[3] = {a0[0], a0[1], a1[0]}, qq[3] = {b0[0], b0[1], b1[0]};
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            s[i] += pp[i];
-            s[3 + i] += qq[i];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) s[6 + 3 * i + j] += qq[i] * pp[j];
-        }
+        pp[k][0] = a0[0]; pp[k][1] = a0[1]; pp[k][2] = a1[0];
+        qq[k][0] = b0[0]; qq[k][1] = b0[1]; qq[k][2] = b1[0];
     }
-    const KabschFit f = kabsch_from_sums(s, 3.0);
-    if (!(fmin(f.da, f.db) >= LC_RANK_EPS)) return false;
-    g = f.g;
-    return true;
+    return sample_fit3(pp, qq, g);
 }
 
 // rec [P, BS_LOOP_FIELDS] fp64: 0-15 T (row-major 4 x 4, X_train = T X_query), 16 inliers, 17 C, 18 the winning h (-1: rejected), 19 RMSE over

@@ -508,6 +508,7 @@ def _distance_stats(rec: np.ndarray) -> DistanceStats:
 
 _ICP_KEYS = ("max_correspondence_distance", "init", "estimation", "target_normals", "max_iteration", "relative_fitness", "relative_rmse", "cell_size",
              "device", "voxel_size")       # (voxel_size is the evaluation's own: _align_icp takes it out before registration_icp is called)
+_ALIGNS = ("icp", "global")
 
 
 def _check_align(align, icp) -> Optional[dict]:
@@ -515,15 +516,32 @@ def _check_align(align, icp) -> Optional[dict]:
         if icp is not None:
             raise ValueError('icp given without align="icp"')
         return None
-    if align != "icp":
-        raise ValueError(f'unknown align {align!r}: None or "icp"')
+    if align not in _ALIGNS:
+        raise ValueError(f'unknown align {align!r}: None, "icp" or "global"')
     if not isinstance(icp, dict) or "max_correspondence_distance" not in icp:
-        raise ValueError('align="icp" needs icp, a dict of registration_icp keywords with max_correspondence_distance')
-    unknown = sorted(set(icp) - set(_ICP_KEYS))
-    if unknown:
-        raise ValueError(f"icp: unknown keys {unknown}; registration_icp takes {_ICP_KEYS}")
+        raise ValueError(f'align="{align}" needs icp, a dict of registration_icp keywords with max_correspondence_distance')
     from . import registration as REG
     kw = dict(icp)
+    ransac = kw.pop("ransac", None) if align == "global" else None                      # (the one key align="global" adds)
+    unknown = sorted(set(kw) - set(_ICP_KEYS))
+    if unknown:
+        raise ValueError(f"icp: unknown keys {unknown}; registration_icp takes {_ICP_KEYS}")
+    if align == "global":
+        if kw.get("voxel_size") is None:
+            raise ValueError('align="global" needs icp["voxel_size"]: registration_global thins both clouds by it')
+        if "init" in kw:
+            raise ValueError('align="global" takes no icp["init"]: the global registration supplies it')
+        if ransac is not None and not isinstance(ransac, dict):
+            raise ValueError('icp["ransac"]: expected a dict of registration_global keywords')
+        ransac = dict(ransac or {})
+        REG._check_ransac_keys(ransac, REG.GLOBAL_KEYS, 'icp["ransac"]')
+        if ransac.get("normal_sign", "either") not in REG.NORMAL_SIGNS:
+            raise ValueError(f"unknown normal_sign {ransac['normal_sign']!r}: one of {REG.NORMAL_SIGNS}")
+        from .pointcloud import _check_search_radius
+        if ransac.get("feature_radius") is not None:
+            _check_search_radius(ransac["feature_radius"], "feature_radius")
+        if ransac.get("max_correspondence_distance") is not None:
+            REG._check_radius(ransac["max_correspondence_distance"])
     REG._check_radius(kw["max_correspondence_distance"])
     kw["init"] = REG._check_init(kw.get("init"))
     kw.setdefault("estimation", "auto")
@@ -533,6 +551,8 @@ def _check_align(align, icp) -> Optional[dict]:
     if kw.get("voxel_size") is not None:
         from .pointcloud import _check_voxel_size
         kw["voxel_size"] = _check_voxel_size(kw["voxel_size"])
+    if align == "global":
+        kw["ransac"] = ransac
     return kw
 
 
@@ -548,6 +568,11 @@ def _align_icp(p, g, p_normals, g_normals, A, kw, dev):
     normals = kw.pop("target_normals", None)
     if normals is None:
         normals = g_normals
+    ransac = kw.pop("ransac", None)
+    if ransac is not None:
+        # align="global": registration_global of pred -> gt gives the init; the ICP below runs exactly as with align="icp".  pred's own
+        # normals are used only when no `transform` turned the points (otherwise they are estimated on the thinned cloud)
+        init = REG.registration_global(p, g, h, source_normals=p_normals if A is None else None, target_normals=normals, **ransac).transformation
 
     def thinned(cloud, n):
         """the registration's (cloud, normals): as they are, or with voxel_size one point and one unit normal per voxel"""
@@ -606,8 +631,11 @@ def evaluate_reconstruction_aligned(pred, gt, thresholds: Sequence[float] = (0.0
     rmse are then those of that direction).  icp["voxel_size"] = h: the usual recipe -- both clouds are thinned by
     pointcloud.voxel_down_sample(h, unit_normals=True), the target's normals averaged along (they must then be finite with |a| <= 2), the
     registration runs on the thinned clouds in the same direction, and its transform is applied to the full pred: the two distance queries
-    see the full clouds as before; fitness and rmse are those of the thinned pair.  align=None: evaluate_reconstruction itself.  (A function of its own: evaluate_reconstruction's
-    parameter list is pinned by tests/test_pointcloud_cpu.py.)"""
+    see the full clouds as before; fitness and rmse are those of the thinned pair.  align="global": for clouds that share no frame --
+    registration.registration_global(pred, gt, icp["voxel_size"], **icp.get("ransac", {})) (FPFH features, matching, RANSAC) gives the init
+    of the same ICP; icp must carry voxel_size, must not carry init, and may carry "ransac", a dict of registration_global's keywords; the
+    global result stays in registration.last_global, `alignment` is the ICP's as before.  align=None: evaluate_reconstruction itself.
+    (A function of its own: evaluate_reconstruction's parameter list is pinned by tests/test_pointcloud_cpu.py.)"""
     return _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, align, icp)
 
 

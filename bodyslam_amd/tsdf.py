@@ -119,6 +119,16 @@ class PointCloud:
         labels = cluster_dbscan(self.points, eps=eps, min_points=min_points)
         return labels.cpu().numpy() if isinstance(self.points, np.ndarray) else labels
 
+    def compute_fpfh_feature(self, radius: float, max_nn: Optional[int] = 100):
+        """o3d.pipelines.registration.compute_fpfh_feature(cloud, KDTreeSearchParamHybrid(radius, max_nn)) from the cloud's own normals
+        (ValueError without them) -> fp32 [M, 33], one row per point: numpy for a numpy cloud, a device tensor otherwise.
+        registration.compute_fpfh_feature states the arithmetic; restated, parity with Open3D unpinned."""
+        from .registration import compute_fpfh_feature
+        if self.normals is None:
+            raise ValueError("compute_fpfh_feature needs the cloud's normals: estimate_normals first")
+        f = compute_fpfh_feature(self.points, self.normals, radius, max_nn=max_nn)
+        return f.cpu().numpy() if isinstance(self.points, np.ndarray) else f
+
     def voxel_down_sample(self, voxel_size: float) -> "PointCloud":
         """o3d.geometry.PointCloud.voxel_down_sample: one point per occupied cube of edge voxel_size, with the mean position, colour and
         normal of the cube's points (the plain mean: a normal is not re-normalised), rows in order of first appearance -- numpy for a

@@ -997,6 +997,62 @@ int bs_icp_step(const void* records, const int32_t* cell_start, int64_t n_record
 int bs_icp_finish(const double* partial, int64_t m, const float* lo, const float* hi, int32_t estimation, int32_t mode, int32_t max_iteration,
                   double relative_fitness, double relative_rmse, double* state, void* stream);
 
+/* ---- global registration: FPFH features, feature matching, RANSAC over correspondences --------------------------------------------------
+ * The roles of Open3D's compute_fpfh_feature and registration_ransac_based_on_feature_matching / _on_correspondence: a pose between two
+ * clouds that share no frame, the init of bs_icp_step.  The reference only calls Open3D.  Restated from Rusu, Blodow & Beetz 2009 (FPFH),
+ * Fischler & Bolles 1981 (RANSAC), Kabsch / Arun et al. (the fit) and Open3D's documented meaning; parity with Open3D is UNPINNED.  The
+ * statement is tests/_global_registration_ref.py.  Every pointer is a device pointer.
+ *   lists             row_start int64 [m + 1], index int32 [total], d2 fp32 [total]: the SORTED rows of bs_pc_radius_* for the points
+ *                     first .. first + m - 1 of a cloud of n points queried on itself; entries with d2 == 0 (the point itself, coincident
+ *                     points) are left out
+ *   bs_fpfh_spfh      table fp32 [n, 8] = (x, y, z, ., nx, ny, nz, .); for every pair (i, neighbour) in fp64 without contraction:
+ *                     a1 = n1 . dp / d, a2 = n2 . dp / d; when |a1| < |a2| the roles swap (n1 <-> n2, dp -> -dp, f3 = -a2), else f3 = a1;
+ *                     v = dp x n1 normalised (|v| = 0: the pair is skipped), w = n1 x v, f2 = v . n2, f1 = the angle of (n1 . n2, w . n2).
+ *                     Eleven bins each: floor(11 (f + 1) / 2) clipped for f2 and f3; for f1 the sector of the vector among the ten edge
+ *                     directions +-(2 j + 1) pi / 11, half-open, no transcendental function.  A zero or non-finite normal at either end
+ *                     skips the pair.  spfh int32 [n, BS_FPFH_ROW]: 33 counts (f1, f2, f3), then k = the counted pairs, then zeros
+ *   bs_fpfh_features  acc = sum_j (100 count_j / k_j) / (double) d2_ij: lane l of the row's wave adds entries l, l + 64, ... in order, then
+ *                     the xor butterfly 32 .. 1; each block of eleven scaled to sum 100 when its sum is positive; + 100 count_i / k_i;
+ *                     rounded to fp32 once.  k_i = 0 (no counted pair, a non-finite point): a zero row.  features fp32 [n, 33]
+ *   bs_feature_match  source fp32 [m, 33], target fp32 [n, 33]; distance = sum_k (a_k - b_k)^2 in fp32, sequential, no contraction.
+ *                     best uint64 [m], filled with ~0 by the caller: the minimum of (distance bits << 32 | target row) over the target
+ *                     rows without a non-finite value, merged over `splits` target splits by a 64-bit atomicMin; a source row with a
+ *                     non-finite value keeps ~0
+ *   bs_gr_*           corr fp64 [c, 6] = (source xyz, target xyz), 16-byte aligned, c >= 3.
+ *     _hypotheses     hypothesis h = h0 + i, i < count: three distinct rows from bs_loop_register's counter-based draw of (seed, pair 0,
+ *                     h, draw); rejected unless every pair of the three has |ps| >= s |pt| and |pt| >= s |ps| (s =
+ *                     edge_length_threshold, before any fit); Kabsch with its rank test; the three residuals^2 < tau^2.  fits fp64
+ *                     [count, 12] (rows of [R | t]), valid int32 [count]
+ *     _score          list int32 [n_valid]: the valid i ascending (the caller's compaction); score int32 [count], zeroed by the caller,
+ *                     += #(residual^2 < tau^2) by integer atomics over `splits` splits of the correspondences
+ *     _winner         best uint64 [1], zeroed before the first chunk: atomicMax of (score << 32 | ~h) over the scores > 0
+ *     _winner_fit     state fp64 [BS_GR_STATE_FIELDS]: 0-11 the rows of [R | t] of hypothesis h, 12 status (1 / 0), 13 inliers, 14 RMSE,
+ *                     15 rounds done
+ *     _refit_step     mask int32 [c] = residual^2 < tau^2 at the state's transform; partial fp64 [ceil(c / 256), BS_GR_PARTIAL_FIELDS]:
+ *                     count, Kabsch's 15 sums over the inliers, the sum of their squared residuals
+ *     _refit_finish   one wave adds the partials in a fixed order; final_round = 0: Kabsch over the inliers replaces the transform (fewer
+ *                     than 3 inliers or a collinear set: status 0); 1: writes the inlier count and the RMSE.  Status 0 makes both return
+ *                     at once
+ * No floating-point atomics: the same input gives the same bits in every call. */
+#define BS_FPFH_DIM 33
+#define BS_FPFH_ROW 36
+#define BS_GR_STATE_FIELDS 16
+#define BS_GR_PARTIAL_FIELDS 17
+int bs_fpfh_spfh(const void* table, int64_t n, const int64_t* row_start, const int32_t* index, const float* d2, int64_t m, int64_t first,
+                 int64_t total, int32_t* spfh, void* stream);
+int bs_fpfh_features(const int32_t* spfh, int64_t n, const int64_t* row_start, const int32_t* index, const float* d2, int64_t m, int64_t first,
+                     int64_t total, float* features, void* stream);
+int bs_feature_match(const float* source, int64_t m, const float* target, int64_t n, int32_t splits, void* best, void* stream);
+int bs_gr_hypotheses(const double* corr, int32_t c, uint64_t seed, uint32_t h0, int32_t count, double edge_length_threshold, double tau,
+                     double* fits, int32_t* valid, void* stream);
+int bs_gr_score(const double* corr, int32_t c, const double* fits, const int32_t* list, int32_t n_valid, int32_t count, int32_t splits, double tau,
+                int32_t* score, void* stream);
+int bs_gr_winner(const int32_t* score, int32_t count, uint32_t h0, void* best, void* stream);
+int bs_gr_winner_fit(const double* corr, int32_t c, uint64_t seed, uint32_t h, double edge_length_threshold, double tau, double* state,
+                     void* stream);
+int bs_gr_refit_step(const double* corr, int32_t c, const double* state, double tau, int32_t* mask, double* partial, void* stream);
+int bs_gr_refit_finish(const double* partial, int32_t c, int32_t final_round, double* state, void* stream);
+
 /* ---- sparse-feature scale path: ORB match displacement (N3, rgbd_odo = False) ---------------------------------------------------------
  * The role of scaling_system.compute_scaling_factor (BodySLAM_not_refactored/3DM/scaling_system.py:107-137), which
  * VO.estimate_relative_pose_between calls with rgbd_odo = False (3DM/visual_odometry.py:70-79): cv2.ORB_create() on both frames,
