@@ -183,6 +183,16 @@ _SIGS = {
     "bs_pc_dbscan_roots": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p],
     "bs_pc_dbscan_labels": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
                             C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    # orientation of normals along a minimum spanning tree (csrc/orient.hip); every pointer is a device pointer
+    "bs_pc_orient_edges": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_orient_clear": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "bs_pc_orient_select": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_orient_select_hi": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_orient_hook": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_pc_orient_compress": [C.c_void_p, C.c_int64, C.c_void_p],
+    "bs_pc_orient_seed": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "bs_pc_orient_flip": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                          C.c_void_p],
     # voxel down-sampling (csrc/voxel.hip); the origin is a pointer to 3 host doubles
     "bs_pc_voxel_assign": [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_pc_voxel_flags": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -211,6 +221,10 @@ _SIGS = {
     "bs_mesh_cc_compress": [C.c_void_p, C.c_int64, C.c_void_p],
     "bs_mesh_cc_roots": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "bs_mesh_cc_clusters": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_orient_hook": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_orient_compress": [C.c_void_p, C.c_int64, C.c_void_p],
+    "bs_mesh_orient_check": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_orient_flip": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_mesh_segment_sum": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "bs_mesh_triangle_geometry": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_mesh_vertex_normals": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
@@ -1124,7 +1138,86 @@ def pc_dbscan_labels(index, points, eps, count, min_points, parent, rank, n_clus
                                              p(labels), stream_ptr()), "bs_pc_dbscan_labels")
 
 
-PC_VOXEL_AXIS_BITS, PC_VOXEL_EMPTY_KEY, PC_VOXEL_NO_POINT = 21, -1, 0x7fffffff            # (the empty key as the int64 a torch fill_ takes)
+ORIENT_MAX_ITEMS, ORIENT_NO_KEY = 1 << 30, -1        # (union_parity.h; the 64-bit ~0 as the int64 a torch comparison takes)
+
+
+def _u8(t, n):
+    assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.numel() == n, "uint8 contiguous device tensor"
+
+
+def pc_orient_edges(points, normals, index, count, keys, valid):
+    """points, normals fp32 [n, 3]; index int32 [n, k], count int32 [n] (pc_query_knn of the cloud on itself); keys int64 [n k], valid int32 [n]"""
+    _pts(points, normals)
+    _i32(index, count, valid)
+    _i64(keys)
+    n, k = index.shape
+    assert points.shape[0] == n and normals.shape[0] == n and count.numel() == n and valid.numel() == n and keys.numel() == n * k
+    check(load_library().bs_pc_orient_edges(p(points), p(normals), n, p(index), p(count), k, p(keys), p(valid), stream_ptr()), "bs_pc_orient_edges")
+
+
+def pc_orient_clear(best, best_hi=None):
+    _i64(best)
+    if best_hi is not None:
+        _i32(best_hi)
+        assert best_hi.numel() == best.numel()
+    check(load_library().bs_pc_orient_clear(p(best), p(best_hi), best.numel(), stream_ptr()), "bs_pc_orient_clear")
+
+
+def pc_orient_select(keys, index, word, best, crossing):
+    """word int32 [n] (the bits of parent << 1 | parity, below 2^31), best int64 [n] cleared, crossing int32 [1] zeroed"""
+    _i64(keys, best)
+    _i32(index, word, crossing)
+    n, k = index.shape
+    assert keys.numel() == n * k and word.numel() == n and best.numel() == n and crossing.numel() >= 1
+    check(load_library().bs_pc_orient_select(p(keys), p(index), p(word), n, k, p(best), p(crossing), stream_ptr()), "bs_pc_orient_select")
+
+
+def pc_orient_select_hi(keys, index, word, best, best_hi):
+    _i64(keys, best)
+    _i32(index, word, best_hi)
+    n, k = index.shape
+    assert keys.numel() == n * k and word.numel() == n and best.numel() == n and best_hi.numel() == n
+    check(load_library().bs_pc_orient_select_hi(p(keys), p(index), p(word), n, k, p(best), p(best_hi), stream_ptr()), "bs_pc_orient_select_hi")
+
+
+def pc_orient_hook(normals, word, best, best_hi):
+    _pts(normals)
+    _i32(word, best_hi)
+    _i64(best)
+    n = normals.shape[0]
+    assert word.numel() == n and best.numel() == n and best_hi.numel() == n
+    check(load_library().bs_pc_orient_hook(p(normals), p(word), n, p(best), p(best_hi), stream_ptr()), "bs_pc_orient_hook")
+
+
+def pc_orient_compress(word):
+    _i32(word)
+    check(load_library().bs_pc_orient_compress(p(word), word.numel(), stream_ptr()), "bs_pc_orient_compress")
+
+
+def pc_orient_seed(points, valid, word, seed):
+    """seed int64 [n], cleared by pc_orient_clear"""
+    _pts(points)
+    _i32(valid, word)
+    _i64(seed)
+    n = points.shape[0]
+    assert valid.numel() == n and word.numel() == n and seed.numel() == n
+    check(load_library().bs_pc_orient_seed(p(points), p(valid), p(word), n, p(seed), stream_ptr()), "bs_pc_orient_seed")
+
+
+def pc_orient_flip(normals, valid, word, seed, direction, out, flipped):
+    """direction: three floats; out fp32 [n, 3] (not `normals`), flipped uint8 [n]"""
+    _pts(normals, out)
+    _i32(valid, word)
+    _i64(seed)
+    n = normals.shape[0]
+    _u8(flipped, n)
+    assert out.shape[0] == n and valid.numel() == n and word.numel() == n and seed.numel() == n and out.data_ptr() != normals.data_ptr()
+    dx, dy, dz = (float(v) for v in direction)
+    check(load_library().bs_pc_orient_flip(p(normals), p(valid), p(word), n, p(seed), dx, dy, dz, p(out), p(flipped), stream_ptr()),
+          "bs_pc_orient_flip")
+
+
+PC_VOXEL_AXIS_BITS, PC_VOXEL_EMPTY_KEY, PC_VOXEL_NO_POINT = 21, -1, 0x7fffffff           # (the empty key as the int64 a torch fill_ takes)
 PC_VOXEL_TABLE_FULL, PC_VOXEL_OUT_OF_RANGE, PC_VOXEL_BAD_ATTRIBUTE = 1, 2, 4
 
 
@@ -1546,6 +1639,43 @@ def mesh_cc_clusters(parent, edge_of_half, rank, triangle_clusters, cluster_n_tr
     assert edge_of_half.numel() == 3 * T and rank.numel() == T and triangle_clusters.numel() == T
     check(load_library().bs_mesh_cc_clusters(p(parent), p(edge_of_half), p(rank), T, cluster_n_triangles.numel(), p(triangle_clusters),
                                              p(cluster_n_triangles), stream_ptr()), "bs_mesh_cc_clusters")
+
+
+def _mesh_links(me, word):
+    """me: mesh.MeshEdges -> the leading arguments of a bs_mesh_orient_hook / _check call"""
+    _i32(me.edge_of_half, me.edge_count, me.edge_forward, me.edge_first_triangle, word)
+    T, E = word.numel(), me.edge_count.numel()
+    assert me.edge_of_half.numel() == 3 * T and me.edge_forward.numel() == E and me.edge_first_triangle.numel() == E
+    return p(me.edge_of_half), p(me.edge_count), p(me.edge_forward), p(me.edge_first_triangle), T, E
+
+
+def mesh_orient_hook(me, word, changed):
+    """me: mesh.MeshEdges; word int32 [T] (the bits of parent << 1 | parity), changed int32 [1]"""
+    _i32(changed)
+    check(load_library().bs_mesh_orient_hook(*_mesh_links(me, word), p(word), p(changed), stream_ptr()), "bs_mesh_orient_hook")
+
+
+def mesh_orient_compress(word):
+    _i32(word)
+    check(load_library().bs_mesh_orient_compress(p(word), word.numel(), stream_ptr()), "bs_mesh_orient_compress")
+
+
+def mesh_orient_check(me, word, bad):
+    """bad int32 [T] zeroed"""
+    _i32(bad)
+    assert bad.numel() == word.numel()
+    check(load_library().bs_mesh_orient_check(*_mesh_links(me, word), p(word), p(bad), stream_ptr()), "bs_mesh_orient_check")
+
+
+def mesh_orient_flip(triangles, edge_of_half, word, bad, out, flipped):
+    """out int32 [T, 3] (not `triangles`), flipped uint8 [T]"""
+    T = _tri(triangles)
+    _i32(edge_of_half, word, bad, out)
+    _u8(flipped, T)
+    assert edge_of_half.numel() == 3 * T and word.numel() == T and bad.numel() == T and tuple(out.shape) == (T, 3)
+    assert out.data_ptr() != triangles.data_ptr()
+    check(load_library().bs_mesh_orient_flip(p(triangles), p(edge_of_half), p(word), p(bad), T, p(out), p(flipped), stream_ptr()),
+          "bs_mesh_orient_flip")
 
 
 def mesh_segment_sum(values, start, out):

@@ -1,7 +1,8 @@
 // Mesh topology and clean-up (bs_mesh_edge_*, bs_mesh_cc_*, bs_mesh_segment_sum, bs_mesh_triangle_geometry, bs_mesh_vertex_normals,
-// bs_mesh_laplacian_step; include/bodyslam_hip.h): the roles of Open3D's TriangleMesh.cluster_connected_triangles, get_non_manifold_edges,
-// compute_triangle_normals, compute_vertex_normals, get_surface_area, filter_smooth_laplacian and filter_smooth_taubin.  Restated from
-// Open3D's documented meaning; parity with Open3D is UNPINNED.  The statement is tests/_mesh_ops_ref.py, DESIGN section 3.21 the argument.
+// bs_mesh_laplacian_step, bs_mesh_orient_*; include/bodyslam_hip.h): the roles of Open3D's TriangleMesh.cluster_connected_triangles,
+// get_non_manifold_edges, compute_triangle_normals, compute_vertex_normals, get_surface_area, filter_smooth_laplacian, filter_smooth_taubin,
+// is_orientable and orient_triangles.  Restated from Open3D's documented meaning; parity with Open3D is UNPINNED.  The statement is
+// tests/_mesh_ops_ref.py (tests/_orient_ref.py for bs_mesh_orient_*), DESIGN section 3.21 the argument (3.24 for the orientation).
 //
 //   edge_insert   one thread per half-edge h = 3 t + c (a = tri[t][c] -> b = tri[t][(c + 1) % 3]) of a valid triangle inserts the key
 //                 min(a, b) << 32 | max(a, b) into the open-addressing table of 64-bit keys of slot_table.h (slot_insert: the table voxel.hip
@@ -18,6 +19,11 @@
 //                 component has the same root, and since root(x) <= x it is the component's smallest index: unique whatever the schedule.
 //   cc_roots / cc_clusters   is_root flags for the caller's scan; cluster = rank of the root - 1, the sizes by integer atomics (one per distinct
 //                 cluster of a wave).
+//   orient_hook / _compress / _check / _flip   the winding: every edge of exactly two triangles links them with s = (edge_forward != 1) -- 0 when
+//                 the two run it in opposite directions, as neighbours of one orientation do -- through union_parity.h; edges of any other
+//                 count link nothing and connect nothing.  Rounds of (hook, compress) until a hook reports no change; check re-tests every
+//                 link against the stored parities and marks the root of a violated one; flip swaps the last two corners of every triangle
+//                 of an unmarked component whose parity to the component's smallest triangle is 1.
 //   segment_sum   one wave per segment of an fp64 array, reduce.h's column_sum order: cluster areas and the surface area.
 //   triangle_geometry   triangle.h, the functions mesh_scene.hip calls too: validity, the fp32 cross product with the kept rule, the unit
 //                 normal, the fp64 cross product and area.
@@ -33,6 +39,7 @@
 #include "slot_table.h"
 #include "triangle.h"
 #include "union_min.h"
+#include "union_parity.h"
 
 namespace bs {
 namespace {
@@ -149,6 +156,66 @@ __global__ void __launch_bounds__(MO_THREADS) cc_clusters_kernel(const int32_t* 
         if (lane == first) atomicAdd(&cluster_n_triangles[cf], (int32_t)__popcll(same));
         todo &= ~same;
     }
+}
+
+// ---- winding (the parity walk, the hook and the compression: union_parity.h, shared with orient.hip) -------------------------------------------
+// the link of half-edge h: its triangle t and the first triangle u of its edge, when the edge has exactly two triangles and t is the other one
+__device__ __forceinline__ bool orient_link(const int32_t* __restrict__ edge_of_half, const int32_t* __restrict__ edge_count,
+                                            const int32_t* __restrict__ edge_forward, const int32_t* __restrict__ edge_first_triangle,
+                                            int64_t n_triangles, int64_t n_edges, int64_t h, uint32_t& t, uint32_t& u, uint32_t& s) {
+    if (h >= 3 * n_triangles) return false;
+    const int32_t e = edge_of_half[h];
+    if (e < 0 || e >= n_edges || edge_count[e] != 2) return false;
+    const int32_t first = edge_first_triangle[e];
+    t = (uint32_t)(h / 3);
+    if (first < 0 || first >= n_triangles || (uint32_t)first == t) return false;
+    u = (uint32_t)first;
+    s = edge_forward[e] != 1 ? 1u : 0u;
+    return true;
+}
+
+__global__ void __launch_bounds__(MO_THREADS) orient_hook_kernel(const int32_t* __restrict__ edge_of_half, const int32_t* __restrict__ edge_count,
+                                                                 const int32_t* __restrict__ edge_forward,
+                                                                 const int32_t* __restrict__ edge_first_triangle, int64_t n_triangles,
+                                                                 int64_t n_edges, uint32_t* word, int32_t* __restrict__ changed) {
+    const int64_t h = (int64_t)blockIdx.x * MO_THREADS + threadIdx.x;
+    uint32_t t, u, s;
+    if (!orient_link(edge_of_half, edge_count, edge_forward, edge_first_triangle, n_triangles, n_edges, h, t, u, s)) return;
+    if (up_union(word, t, u, s, n_triangles)) *changed = 1;          // (every writer stores the same value)
+}
+
+__global__ void __launch_bounds__(MO_THREADS) orient_compress_kernel(uint32_t* word, int64_t n_triangles) {
+    const int64_t t = (int64_t)blockIdx.x * MO_THREADS + threadIdx.x;
+    if (t >= n_triangles) return;
+    up_compress(word, (uint32_t)t, n_triangles);
+}
+
+// after the fixed point and a compression word[t] = root << 1 | parity to the root: a link that the parities do not satisfy marks the root
+__global__ void __launch_bounds__(MO_THREADS) orient_check_kernel(const int32_t* __restrict__ edge_of_half, const int32_t* __restrict__ edge_count,
+                                                                  const int32_t* __restrict__ edge_forward,
+                                                                  const int32_t* __restrict__ edge_first_triangle, int64_t n_triangles,
+                                                                  int64_t n_edges, const uint32_t* __restrict__ word, int32_t* __restrict__ bad) {
+    const int64_t h = (int64_t)blockIdx.x * MO_THREADS + threadIdx.x;
+    uint32_t t, u, s;
+    if (!orient_link(edge_of_half, edge_count, edge_forward, edge_first_triangle, n_triangles, n_edges, h, t, u, s)) return;
+    const uint32_t wt = word[t], wu = word[u], r = wt >> 1;
+    if (r >= n_triangles) return;
+    if ((wu >> 1) != r || ((wt ^ wu) & 1u) != s) bad[r] = 1;          // (every writer stores the same value)
+}
+
+__global__ void __launch_bounds__(MO_THREADS) orient_flip_kernel(const int32_t* __restrict__ triangles, const int32_t* __restrict__ edge_of_half,
+                                                                 const uint32_t* __restrict__ word, const int32_t* __restrict__ bad,
+                                                                 int64_t n_triangles, int32_t* __restrict__ out, uint8_t* __restrict__ flipped) {
+    const int64_t t = (int64_t)blockIdx.x * MO_THREADS + threadIdx.x;
+    if (t >= n_triangles) return;
+    bool flip = false;
+    if (edge_of_half[3 * t] >= 0) {                                  // (a valid triangle has all three of its half-edges)
+        const uint32_t w = word[t], r = w >> 1;
+        flip = r < n_triangles && !bad[r] && (w & 1u);
+    }
+    const int32_t a = triangles[3 * t], b = triangles[3 * t + 1], c = triangles[3 * t + 2];
+    out[3 * t] = a; out[3 * t + 1] = flip ? c : b; out[3 * t + 2] = flip ? b : c;
+    flipped[t] = flip ? 1 : 0;
 }
 
 // out[s] = the sum of values[start[s] .. start[s + 1]) by one wave, column_sum's order: lane l adds elements l, l + 64, ... in order, then
@@ -357,6 +424,52 @@ extern "C" int bs_mesh_cc_clusters(const int32_t* parent, const int32_t* edge_of
                (long long)n_clusters);
     hipLaunchKernelGGL(cc_clusters_kernel, mo_grid(n_triangles), dim3(MO_THREADS), 0, st, parent, edge_of_half, rank, n_triangles, n_clusters,
                        triangle_clusters, cluster_n_triangles);
+    BS_CHECK_LAUNCH();
+    return BS_OK;
+}
+
+extern "C" int bs_mesh_orient_hook(const int32_t* edge_of_half, const int32_t* edge_count, const int32_t* edge_forward,
+                                  const int32_t* edge_first_triangle, int64_t n_triangles, int64_t n_edges, uint32_t* word, int32_t* changed,
+                                  void* stream) {
+    MO_ENTER("bs_mesh_orient_hook");
+    BS_REQUIRE(edge_of_half && word && changed && (n_edges == 0 || (edge_count && edge_forward && edge_first_triangle)),
+               "bs_mesh_orient_hook: null pointer");
+    BS_REQUIRE(mo_count(n_triangles) && n_edges >= 0 && n_edges <= 3 * n_triangles, "bs_mesh_orient_hook: T = %lld, E = %lld", (long long)n_triangles,
+               (long long)n_edges);
+    hipLaunchKernelGGL(orient_hook_kernel, mo_grid(3 * n_triangles), dim3(MO_THREADS), 0, st, edge_of_half, edge_count, edge_forward,
+                       edge_first_triangle, n_triangles, n_edges, word, changed);
+    BS_CHECK_LAUNCH();
+    return BS_OK;
+}
+
+extern "C" int bs_mesh_orient_compress(uint32_t* word, int64_t n_triangles, void* stream) {
+    MO_ENTER("bs_mesh_orient_compress");
+    BS_REQUIRE(word && mo_count(n_triangles), "bs_mesh_orient_compress: word %p, T = %lld", (void*)word, (long long)n_triangles);
+    hipLaunchKernelGGL(orient_compress_kernel, mo_grid(n_triangles), dim3(MO_THREADS), 0, st, word, n_triangles);
+    BS_CHECK_LAUNCH();
+    return BS_OK;
+}
+
+extern "C" int bs_mesh_orient_check(const int32_t* edge_of_half, const int32_t* edge_count, const int32_t* edge_forward,
+                                   const int32_t* edge_first_triangle, int64_t n_triangles, int64_t n_edges, const uint32_t* word, int32_t* bad,
+                                   void* stream) {
+    MO_ENTER("bs_mesh_orient_check");
+    BS_REQUIRE(edge_of_half && word && bad && (n_edges == 0 || (edge_count && edge_forward && edge_first_triangle)),
+               "bs_mesh_orient_check: null pointer");
+    BS_REQUIRE(mo_count(n_triangles) && n_edges >= 0 && n_edges <= 3 * n_triangles, "bs_mesh_orient_check: T = %lld, E = %lld", (long long)n_triangles,
+               (long long)n_edges);
+    hipLaunchKernelGGL(orient_check_kernel, mo_grid(3 * n_triangles), dim3(MO_THREADS), 0, st, edge_of_half, edge_count, edge_forward,
+                       edge_first_triangle, n_triangles, n_edges, word, bad);
+    BS_CHECK_LAUNCH();
+    return BS_OK;
+}
+
+extern "C" int bs_mesh_orient_flip(const int32_t* triangles, const int32_t* edge_of_half, const uint32_t* word, const int32_t* bad, int64_t n_triangles,
+                                  int32_t* out, uint8_t* flipped, void* stream) {
+    MO_ENTER("bs_mesh_orient_flip");
+    BS_REQUIRE(triangles && edge_of_half && word && bad && out && flipped && out != triangles, "bs_mesh_orient_flip: null pointer, or out == triangles");
+    BS_REQUIRE(mo_count(n_triangles), "bs_mesh_orient_flip: T = %lld", (long long)n_triangles);
+    hipLaunchKernelGGL(orient_flip_kernel, mo_grid(n_triangles), dim3(MO_THREADS), 0, st, triangles, edge_of_half, word, bad, n_triangles, out, flipped);
     BS_CHECK_LAUNCH();
     return BS_OK;
 }

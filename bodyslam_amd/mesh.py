@@ -14,8 +14,12 @@ vertices are finite and its fp32 cross product finite and non-zero (the rule of 
 normals and areas the kept ones.  Argument errors are ValueErrors raised before any launch; an empty mesh gives empty results; there is no
 CPU fallback.
 
-Not built: Open3D's vertex-manifold and self-intersection tests and hence is_watertight, is_orientable / re-orientation, simplification,
-subdivision, hole filling, signed distance."""
+``orient_triangles`` / ``is_orientable`` / ``orientable_components`` (Open3D's orient_triangles and is_orientable) repair the winding: a
+union-find with one parity bit per link over the two-triangle edges (csrc/union_parity.h); the statement is
+tests/_orient_ref.py.
+
+Not built: Open3D's vertex-manifold and self-intersection tests and hence is_watertight, outward orientation of closed components by signed
+volume, simplification, subdivision, hole filling, signed distance."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -28,6 +32,7 @@ from . import _args as AR
 from . import _lib as L
 
 last_rounds = 0          # the (hook, compress) rounds of the latest cluster_connected_triangles, the final unchanged one included
+last_orient_rounds = 0   # the (hook, compress) rounds of the latest orient_triangles / is_orientable / orientable_components, likewise
 
 
 @dataclass
@@ -202,6 +207,73 @@ def cluster_connected_triangles(vertices, triangles=None, slots: Optional[int] =
     with torch.cuda.device(dev):
         v, t = _on_device(v, t, dev)
         return _clusters(v, t, slots)
+
+
+# ---- winding -------------------------------------------------------------------------------------------------------------------------------
+def _orient(vertices, triangles, slots, device):
+    """-> (triangles int32 [T, 3], flipped bool [T], triangle_components int32 [T], component_orientable bool [C]), device tensors"""
+    global last_orient_rounds
+    v, t = _as_mesh(vertices, triangles)
+    slots = _check_slots(slots, 3 * int(t.shape[0]))
+    dev = _device(v, t, device)
+    with torch.cuda.device(dev):
+        v, t = _on_device(v, t, dev)
+        T = int(t.shape[0])
+        i32 = dict(dtype=torch.int32, device=dev)
+        last_orient_rounds = 0
+        if T == 0:
+            return t.clone(), torch.zeros(0, dtype=torch.bool, device=dev), torch.empty(0, **i32), torch.zeros(0, dtype=torch.bool, device=dev)
+        me = _edge_rows(t, int(v.shape[0]), slots)
+        word = torch.arange(T, **i32) * 2                                    # parent << 1 | parity: every triangle its own root
+        changed = torch.zeros(1, **i32)
+        for _ in range(T + 1):                       # every round that reports a change removes a root for good: at most T do
+            changed.zero_()
+            L.mesh_orient_hook(me, word, changed)
+            L.mesh_orient_compress(word)
+            last_orient_rounds += 1
+            if int(changed.cpu()) == 0:
+                break
+        else:
+            raise L.BodySlamHipError(f"orient_triangles: no fixed point after {T + 1} rounds")
+        bad = torch.zeros(T, **i32)
+        L.mesh_orient_check(me, word, bad)
+        out, flipped = torch.empty_like(t), torch.empty(T, dtype=torch.uint8, device=dev)
+        L.mesh_orient_flip(t, me.edge_of_half, word, bad, out, flipped)
+        root = word >> 1                                                     # (the labels are plumbing: a scan and two gathers)
+        is_root = (me.edge_of_half[0::3] >= 0) & (root == torch.arange(T, **i32))
+        rank = torch.cumsum(is_root.to(torch.int32), 0).to(torch.int32)
+        components = torch.where(me.edge_of_half[0::3] >= 0, rank[root.to(torch.int64)] - 1, torch.full((), -1, **i32)).to(torch.int32)
+        return out, flipped.to(torch.bool), components, bad[is_root] == 0
+
+
+def orient_triangles(vertices, triangles=None, slots: Optional[int] = None, device: int = 0):
+    """Open3D's orient_triangles -> (triangles int32 [T, 3], flipped bool [T], orientable bool); restated, parity with Open3D unpinned, the
+    statement is tests/_orient_ref.py.  Every edge of the edge table with exactly two triangles links them: they have one orientation when
+    they run the edge in opposite directions (edge_forward == 1), so the link says flip(t) xor flip(u) = (edge_forward != 1).  An edge
+    with any other count -- a boundary edge, or one with three triangles or more -- links nothing and connects nothing: the components
+    here are those of the two-triangle edges, finer than cluster_connected_triangles' where such edges exist.  csrc/mesh_ops.hip: rounds
+    of (hook with a parity bit, compress) over csrc/union_parity.h until nothing changes (``last_orient_rounds``), a launch that re-tests
+    every link, a launch that flips.
+
+    In an orientable component the triangle of smallest index keeps its winding and every other triangle is flipped when its parity to
+    that one is 1; a flipped triangle [a, b, c] becomes [a, c, b].  A component with a link its parities cannot satisfy (a Moebius strip)
+    is not orientable: it is returned unchanged, and orientable is False.  Invalid triangles are returned unchanged.  No outward
+    orientation by signed volume is attempted.  ``orientable_components`` gives the verdict per component."""
+    out, flipped, _, verdict = _orient(vertices, triangles, slots, device)
+    return out, flipped, bool(verdict.all())
+
+
+def orientable_components(vertices, triangles=None, slots: Optional[int] = None, device: int = 0):
+    """-> (triangle_components int32 [T], component_orientable bool [C]): the components of ``orient_triangles`` -- valid triangles joined
+    through edges of exactly two triangles --, numbered in the order of their first triangle as cluster_connected_triangles numbers its
+    clusters, -1 for an invalid triangle; and whether each can be wound consistently."""
+    _, _, components, verdict = _orient(vertices, triangles, slots, device)
+    return components, verdict
+
+
+def is_orientable(vertices, triangles=None, slots: Optional[int] = None, device: int = 0) -> bool:
+    """Open3D's is_orientable: every component of ``orient_triangles`` can be wound consistently (an empty mesh can)"""
+    return bool(_orient(vertices, triangles, slots, device)[3].all())
 
 
 def get_surface_area(vertices, triangles=None, device: int = 0) -> float:

@@ -28,8 +28,12 @@ parity with Open3D unpinned; the statement is tests/_mesh_scene_ref.py.  Distanc
 search_radius_vector_3d), and on them stand ``remove_radius_outlier`` (PointCloud.remove_radius_outlier) and ``cluster_dbscan``
 (PointCloud.cluster_dbscan, made deterministic).  Restated, parity with Open3D unpinned; the statement is tests/_radius_ref.py.
 
-Not built: orientation propagation, k > 32, Open3D's cubic-id trace format, Poisson-disk
-sampling of a mesh.
+``orient_normals_consistent_tangent_plane`` gives the normals of a cloud one sign per surface: the signs are propagated along the minimum
+spanning tree of the k-NN graph (csrc/orient.hip: Boruvka's rounds by 64-bit integer atomics over a union-find with a parity bit,
+csrc/union_parity.h; Open3D's PointCloud.orient_normals_consistent_tangent_plane without its Delaunay edges).  Restated, parity with Open3D
+unpinned; the statement is tests/_orient_ref.py.
+
+Not built: k > 32, Open3D's cubic-id trace format, Poisson-disk sampling of a mesh.
 """
 from __future__ import annotations
 
@@ -305,7 +309,8 @@ class NearestNeighbours:
         return row_start, index, d2
 
 
-last_rounds = 0                 # cluster_dbscan: the (hook, compress) rounds of the last call, the confirming one included
+last_rounds = 0                 # cluster_dbscan: the (hook, compress) rounds of the last call, the confirming one included; after
+                                # orient_normals_consistent_tangent_plane: its Boruvka rounds, the one that found no edge included
 last_clusters = 0               # cluster_dbscan: the clusters of the last call
 
 
@@ -381,7 +386,8 @@ def estimate_normals(points, k: int = 30, radius: Optional[float] = None, direct
     there are fewer than 3 neighbours or the largest eigenvalue is not positive and finite -- the convention of PointCloud.normals and of
     registration_icp: a zero normal leaves its pairs out; for exactly collinear neighbours the direction is unspecified.  Sign:
     direction=v flips when n . v < 0, camera_location=c when n . (c - p) < 0 (the two exclude each other); with neither, the component
-    of largest magnitude is made positive, so that the result is deterministic.  No propagation of the orientation along a spanning tree.
+    of largest magnitude is made positive, so that the result is deterministic -- not one sign per surface: on a tube both signs appear.
+``orient_normals_consistent_tangent_plane`` propagates one sign along a spanning tree.
     The cell size changes the time, never the bits.  Raises ValueError on bad arguments before the GPU is touched."""
     k = _check_k(k)
     _check_radius(radius)
@@ -396,6 +402,82 @@ def estimate_normals(points, k: int = 30, radius: Optional[float] = None, direct
         eig = torch.empty(n, 3, dtype=torch.float64, device=nn.dev) if return_eigenvalues else None
         L.pc_normals(nn.target, index, count, k, mode, vec, normals, eig)
     return (normals, eig) if return_eigenvalues else normals
+
+
+last_components = 0             # orient_normals_consistent_tangent_plane: the trees of the last call (one per component of the valid points)
+
+
+def _check_items(n: int, what: str) -> int:
+    """union_parity.h packs parent << 1 | parity into 32 bits"""
+    if n > L.ORIENT_MAX_ITEMS:
+        raise ValueError(f"{what}: {n} rows, at most 2^30 can be oriented")
+    return n
+
+
+def orient_normals_consistent_tangent_plane(points, normals, k: int, direction=(0.0, 0.0, 1.0), cell_size: Optional[float] = None,
+                                            device: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One sign per surface -> (normals fp32 [n, 3], flipped bool [n]), device tensors: the role of Open3D's
+    PointCloud.orient_normals_consistent_tangent_plane(k) (Hoppe et al. 1992).  Open3D is not vendored: the meaning is restated from its
+    documentation and parity with Open3D is unpinned; the statement is tests/_orient_ref.py and the result is bit-equal to it, the same bits
+    in every run.  ``last_components`` and ``last_rounds`` hold the number of trees and the rounds the last call took.
+
+    A point is VALID when its coordinates are finite and its normal is finite and not all zero.  The graph: the undirected edge {i, j},
+    i != j, exists when j is in row i of ``query_knn(cloud, cloud, k)`` or i in row j, and both ends are valid; k counts the point itself,
+    as in ``estimate_normals``, 2 <= k <= 32.  In fp64 without contraction, on the fp32 normals: d = (ax bx + ay by) + az bz, the weight
+    w = fl32(max(1 - |d|, 0)), the sign link s = (d < 0).  Edges are ordered by (the bits of w, min(i, j), max(i, j)); under that total
+    order the minimum spanning forest is unique (on a plane every weight is exactly 0: the indices decide).  Per tree the seed is the valid
+    point of largest fp32 z, ties to the lowest index; it is flipped when n . direction < 0 (the same fp64 expression; 0 does not flip), and
+    flip(x) = the seed's flip xor the parity of the signs s along the tree path from x to the seed.  A flipped normal has its three sign
+    bits toggled; invalid rows come back bit for bit and are never traversed.
+
+    Departure from Open3D: no Delaunay edges are added to the k-NN graph, so a disconnected graph gives several trees and each is oriented
+    on its own (``last_components`` tells); Open3D's lambda / cos_alpha_tol penalties are not built.
+
+    csrc/orient.hip: Boruvka's rounds on the k-NN lists as they lie -- clear, select the (w, low index) minimum per root by 64-bit integer
+    atomics, select the high index, hook with a parity bit (csrc/union_parity.h), compress -- until a round finds no edge between two
+    trees, then the seeds and the flips.  The cell size changes the time, never the bits.  Raises ValueError on bad arguments before the GPU
+    is touched; there is no CPU fallback."""
+    global last_components, last_rounds
+    k = AR.integer(k, "k", 2, L.PC_KNN_MAX)
+    _, vec = _check_orientation(direction, None)
+    if vec is None:
+        raise ValueError("direction: expected three finite numbers")
+    _check_cell_size(cell_size)
+    pts = as_points(points, "points")
+    n = _check_items(int(pts.shape[0]), "points")
+    nrm = _as_attribute(normals, "normals", n)
+    if nrm is None:
+        raise ValueError(f"normals: expected a float32 or float64 array or tensor of shape [{n}, 3]")
+    nn = NearestNeighbours(pts, cell_size=cell_size, device=device)
+    dev = nn.dev
+    with torch.cuda.device(dev):
+        nrm = nrm.to(dev).to(torch.float32).contiguous()
+        index, _, count = nn.query_knn(nn.target, k)
+        i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+        keys, valid = torch.empty(n * k, **i64), torch.empty(n, **i32)
+        L.pc_orient_edges(nn.target, nrm, index, count, keys, valid)
+        word = torch.arange(n, **i32) * 2                                    # parent << 1 | parity: every point its own root
+        best, best_hi = torch.empty(n, **i64), torch.empty(n, **i32)
+        crossing = torch.zeros(1, **i32)
+        rounds = 0
+        for _ in range(n + 1):                       # every round that finds a crossing edge hooks one for good: at most n - 1 do
+            crossing.zero_()
+            L.pc_orient_clear(best, best_hi)
+            L.pc_orient_select(keys, index, word, best, crossing)
+            rounds += 1
+            if int(crossing.cpu()) == 0:
+                break
+            L.pc_orient_select_hi(keys, index, word, best, best_hi)
+            L.pc_orient_hook(nrm, word, best, best_hi)
+            L.pc_orient_compress(word)
+        else:
+            raise L.BodySlamHipError(f"orient_normals_consistent_tangent_plane: still an edge between two trees after {n + 1} rounds")
+        L.pc_orient_clear(best)                                               # (best now holds the seeds)
+        L.pc_orient_seed(nn.target, valid, word, best)
+        out, flipped = torch.empty(n, 3, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+        L.pc_orient_flip(nrm, valid, word, best, vec, out, flipped)
+        last_components, last_rounds = int((best != L.ORIENT_NO_KEY).sum().cpu()), rounds
+    return out, flipped.to(torch.bool)
 
 
 def knn_mean_distance(points, nb_neighbors: int = 20, cell_size: Optional[float] = None, device: int = 0) -> torch.Tensor:

@@ -334,8 +334,10 @@ def compute_fpfh_feature(points, normals, radius, max_nn: Optional[int] = 100, c
 
 def mirror_fpfh(features):
     """The features a cloud would have with every normal negated: blocks 1 and 3 (f1, f3) reversed, block 2 unchanged -- a bin permutation, bit
-    for bit.  estimate_normals without direction or camera_location orients by the largest component, which is consistent inside a cloud but
-    flips with the cloud's pose: registration_global(normal_sign="either") therefore tries both.  numpy in, numpy out; torch in, torch out."""
+    for bit.  estimate_normals without direction or camera_location orients by the largest component, which is deterministic, consistent
+    only on a nearly flat cloud (on a tube both signs appear) and flips with the cloud's pose.
+    pointcloud.orient_normals_consistent_tangent_plane gives one sign per surface, but which of the two remains arbitrary between two
+    clouds: registration_global(normal_sign="either") therefore tries both.  numpy in, numpy out; torch in, torch out."""
     perm = list(range(10, -1, -1)) + list(range(11, 22)) + list(range(32, 21, -1))
     if isinstance(features, np.ndarray):
         _check_features(features, "features")

@@ -86,6 +86,18 @@ class PointCloud:
         self.normals = n.cpu().numpy() if isinstance(self.points, np.ndarray) else n
         return self.normals
 
+    def orient_normals_consistent_tangent_plane(self, k: int):
+        """o3d.geometry.PointCloud.orient_normals_consistent_tangent_plane(k): gives the cloud's normals (ValueError without them) one sign
+        per surface by propagating it along the minimum spanning tree of the k-NN graph; sets and returns ``self.normals``, numpy for a
+        numpy cloud, a device tensor otherwise.  pointcloud.orient_normals_consistent_tangent_plane states the rule and the departure
+        from Open3D (no Delaunay edges: every component of the k-NN graph is oriented on its own); restated, parity with Open3D unpinned."""
+        from .pointcloud import orient_normals_consistent_tangent_plane
+        if self.normals is None:
+            raise ValueError("orient_normals_consistent_tangent_plane needs the cloud's normals: estimate_normals first")
+        n, _ = orient_normals_consistent_tangent_plane(self.points, self.normals, k)
+        self.normals = n.cpu().numpy() if isinstance(self.points, np.ndarray) else n
+        return self.normals
+
     def remove_statistical_outlier(self, nb_neighbors: int, std_ratio: float):
         """o3d.geometry.PointCloud.remove_statistical_outlier -> (the PointCloud of the kept rows -- points, colours and normals --, their
         indices int64 ascending: numpy for a numpy cloud, device tensors otherwise).  pointcloud.remove_statistical_outlier states the
@@ -194,9 +206,23 @@ class TriangleMesh:
         return edge_topology(self.vertices, self.triangles).is_edge_manifold(allow_boundary_edges)
 
     def is_consistently_oriented(self) -> bool:
-        """every edge of two triangles is run once in each direction (the test of the winding as it stands; is_orientable is not built)"""
+        """every edge of two triangles is run once in each direction (the test of the winding as it stands; is_orientable asks whether it
+        can be made so, orient_triangles makes it so)"""
         from .mesh import edge_topology
         return edge_topology(self.vertices, self.triangles).is_consistently_oriented()
+
+    def is_orientable(self) -> bool:
+        """o3d is_orientable: every component of triangles joined through two-triangle edges can be wound consistently"""
+        from .mesh import is_orientable
+        return is_orientable(self.vertices, self.triangles)
+
+    def orient_triangles(self):
+        """o3d orient_triangles, returning a new mesh -> (TriangleMesh with every orientable component wound like its first triangle -- the
+        normals are not carried: they would be stale --, flipped bool [T], orientable bool).  A component that cannot be wound
+        consistently is left as it is and makes orientable False.  mesh.orient_triangles states the rule."""
+        from .mesh import orient_triangles
+        t, flipped, ok = orient_triangles(self.vertices, self.triangles)
+        return TriangleMesh(self.vertices, self.vertex_colors, self._out(t)), self._out(flipped), ok
 
     def is_closed(self) -> bool:
         """every edge has exactly two triangles; with is_consistently_oriented() the precondition of a signed distance (is_watertight, which

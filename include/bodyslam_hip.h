@@ -767,6 +767,46 @@ int bs_pc_dbscan_labels(const void* records, const int32_t* cell_start, int64_t 
                         const int32_t* dims, const float* points, int64_t n, float eps, const int32_t* count, int32_t min_points,
                         const int32_t* parent, const int32_t* rank, int64_t n_clusters, int32_t* labels, void* stream);
 
+/* ---- consistent orientation of normals along a minimum spanning tree ---------------------------------------------------------------------
+ * bs_pc_orient_* replace Open3D's PointCloud.orient_normals_consistent_tangent_plane (Hoppe et al. 1992).  Restated from Open3D's documented
+ * meaning; parity with Open3D is UNPINNED, and no Delaunay edges are added: a disconnected k-NN graph gives several trees, each oriented on
+ * its own.  The statement is tests/_orient_ref.py, DESIGN section 3.24 the argument.  All pointers are device pointers; n <= 2^30.
+ *   graph           index int32 [n, k], count int32 [n]: bs_pc_query_knn of the cloud on itself.  A point is VALID when its coordinates are
+ *                   finite and its normal is finite and not all zero.  The undirected edge {i, j}, i != j, exists when j is in row i or i in
+ *                   row j and both are valid.  In fp64 without contraction d = (ax bx + ay by) + az bz on the fp32 normals; the weight is
+ *                   w = fl32(max(1 - |d|, 0)), the sign link s = (d < 0): flip(i) xor flip(j) = s.  Edges are ordered by (the bits of w,
+ *                   min(i, j), max(i, j)): a total order, so the minimum spanning forest is unique
+ *   word            uint32 [n]: parent << 1 | parity, parity = flip(x) xor flip(parent); the caller starts it as x << 1.  parent <= x always:
+ *                   a root walk strictly descends, at most n steps.  Every stored word is a relation implied by the links hooked so far
+ *   bs_pc_orient_edges      keys [n k] of 64-bit words: w_bits << 32 | min(i, j) for a slot that is an edge, ~0 for any other; valid int32 [n]
+ *   bs_pc_orient_clear      best [n] of 64-bit words = ~0; best_hi int32 [n] (NULL: none) = 0x7fffffff
+ *   bs_pc_orient_select     every slot whose ends have different roots offers its key to best[] of both roots by 64-bit integer atomic
+ *                   minimum and sets crossing int32 [1] (zeroed by the caller).  Offers of one wave to one root are merged into one atomic
+ *   bs_pc_orient_select_hi  the crossing slots whose key equals their root's best offer max(i, j) to best_hi[] by integer atomic minimum
+ *   bs_pc_orient_hook       every root r with best[r] != ~0 hooks the link (lo, hi, s) of its edge: the parities pa, pb of the walks to the
+ *                   two roots, then an integer atomic minimum of (smaller root << 1 | pa ^ pb ^ s) into the larger root's word.  A hook
+ *                   that loses to a smaller root is not an error: the edge is selected again in the next round
+ *   bs_pc_orient_compress   word[x] = root(x) << 1 | parity to the root.  The caller repeats (zero crossing, clear, select, select_hi, hook,
+ *                   compress) until a select leaves crossing 0: at most n rounds find a crossing edge
+ *   bs_pc_orient_seed       seed [n] of 64-bit words (cleared to ~0 by bs_pc_orient_clear): per root the integer atomic minimum of
+ *                   (~ordered bits of z) << 32 | i over its valid points -- the point of largest fp32 z (-0 as +0), ties to the lowest index
+ *   bs_pc_orient_flip       the seed of a tree is flipped when (nx dx + ny dy) + nz dz < 0 in fp64; flip(x) = the seed's flip xor the parity
+ *                   of x to the root xor that of the seed to the root.  out fp32 [n, 3] (not `normals`): the normal with its three sign
+ *                   bits toggled where flipped, every other row bit for bit; flipped uint8 [n]
+ * Integer atomics only and no retry loops: the same bits in every run, for every order of the atomics. */
+int bs_pc_orient_edges(const float* points, const float* normals, int64_t n, const int32_t* index, const int32_t* count, int32_t k, void* keys,
+                       int32_t* valid, void* stream);
+int bs_pc_orient_clear(void* best, int32_t* best_hi, int64_t n, void* stream);
+int bs_pc_orient_select(const void* keys, const int32_t* index, const uint32_t* word, int64_t n, int32_t k, void* best, int32_t* crossing,
+                        void* stream);
+int bs_pc_orient_select_hi(const void* keys, const int32_t* index, const uint32_t* word, int64_t n, int32_t k, const void* best, int32_t* best_hi,
+                           void* stream);
+int bs_pc_orient_hook(const float* normals, uint32_t* word, int64_t n, const void* best, const int32_t* best_hi, void* stream);
+int bs_pc_orient_compress(uint32_t* word, int64_t n, void* stream);
+int bs_pc_orient_seed(const float* points, const int32_t* valid, const uint32_t* word, int64_t n, void* seed, void* stream);
+int bs_pc_orient_flip(const float* normals, const int32_t* valid, const uint32_t* word, int64_t n, const void* seed, double dx, double dy, double dz,
+                      float* out, uint8_t* flipped, void* stream);
+
 /* ---- voxel down-sampling -----------------------------------------------------------------------------------------------------------------
  * The four bs_pc_voxel_* launches replace Open3D's PointCloud.voxel_down_sample, which the reference calls at
  * BodySLAM_not_refactored/3DM/mapping_module.py:72,156,187 (0.005, 0.009 and 0.05 m), and return what voxel_down_sample_and_trace is used
@@ -923,8 +963,20 @@ int bs_mesh_sample(const void* records, int64_t n_triangles, const int64_t* cum,
  *   bs_mesh_laplacian_step one thread per vertex: mean = (the fp64 sum of in[nbr[nbr_start[v] .. nbr_start[v + 1])] in order) / count,
  *                          out = fl32(v + lambda (mean - v)) in fp64, clamped to [0, 1] before the rounding when `clamp`; a vertex without
  *                          neighbours is copied.  in and out fp32 [V, 3], distinct buffers
+ *   bs_mesh_orient_*       the winding (Open3D's is_orientable / orient_triangles; the statement is tests/_orient_ref.py, DESIGN section
+ *                          3.24).  Every edge with edge_count == 2 links its two triangles with s = (edge_forward != 1): flip(t) xor
+ *                          flip(u) = s.  Edges with any other count link nothing and connect nothing.  word uint32 [T] = parent << 1 |
+ *                          parity as for bs_pc_orient_hook (the same device functions), started as t << 1 by the caller
+ *   bs_mesh_orient_hook    one thread per half-edge hooks the link of its triangle and its edge's first triangle; changed int32 [1] = 1
+ *                          when the roots differed
+ *   bs_mesh_orient_compress word[t] = root(t) << 1 | parity to the root.  The caller repeats (zero changed, hook, compress) until changed
+ *                          stays 0, at most T rounds report a change
+ *   bs_mesh_orient_check   re-tests every link against the stored parities: a violated link sets bad int32 [T] (zeroed by the caller) at
+ *                          its root -- that component is not orientable
+ *   bs_mesh_orient_flip    out int32 [T, 3] (not `triangles`): [a, c, b] for a valid triangle of an orientable component whose parity to the
+ *                          component's smallest triangle is 1, every other row unchanged; flipped uint8 [T]
  * No floating-point atomics and no retry loops: the same bits in every run, for every table size and every order of the atomics.  Not built:
- * vertex-manifoldness, self-intersection and hence is_watertight, is_orientable / re-orientation, simplification, subdivision, hole filling. */
+ * vertex-manifoldness, self-intersection and hence is_watertight, simplification, subdivision, hole filling. */
 #define BS_MESH_EDGE_EMPTY_KEY 0xffffffffffffffffull
 #define BS_MESH_EDGE_NO_HALF 0x7fffffff
 enum { BS_MESH_EDGE_TABLE_FULL = 1 };
@@ -942,6 +994,13 @@ int bs_mesh_cc_compress(int32_t* parent, int64_t n_triangles, void* stream);
 int bs_mesh_cc_roots(const int32_t* parent, const int32_t* edge_of_half, int64_t n_triangles, int32_t* is_root, void* stream);
 int bs_mesh_cc_clusters(const int32_t* parent, const int32_t* edge_of_half, const int32_t* rank, int64_t n_triangles, int64_t n_clusters,
                         int32_t* triangle_clusters, int32_t* cluster_n_triangles, void* stream);
+int bs_mesh_orient_hook(const int32_t* edge_of_half, const int32_t* edge_count, const int32_t* edge_forward, const int32_t* edge_first_triangle,
+                        int64_t n_triangles, int64_t n_edges, uint32_t* word, int32_t* changed, void* stream);
+int bs_mesh_orient_compress(uint32_t* word, int64_t n_triangles, void* stream);
+int bs_mesh_orient_check(const int32_t* edge_of_half, const int32_t* edge_count, const int32_t* edge_forward, const int32_t* edge_first_triangle,
+                         int64_t n_triangles, int64_t n_edges, const uint32_t* word, int32_t* bad, void* stream);
+int bs_mesh_orient_flip(const int32_t* triangles, const int32_t* edge_of_half, const uint32_t* word, const int32_t* bad, int64_t n_triangles,
+                        int32_t* out, uint8_t* flipped, void* stream);
 int bs_mesh_segment_sum(const double* values, int64_t n_values, const int64_t* start, int64_t n_segments, double* out, void* stream);
 int bs_mesh_triangle_geometry(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, int32_t* flags,
                               float* normals, double* cross, double* area, void* stream);
