@@ -152,12 +152,38 @@ __global__ __launch_bounds__(BP_THREADS) void bp_write_kernel(const uint16_t* de
 // pose chain: G_i = G_{i-1} * T_i (fp64), R <- U diag(1, 1, det(U) det(V^T)) V^T.
 // One lane walks the chain (it is a strict recurrence); the 3x3 SVD is a one-sided Jacobi in fp64 (svd3.h).
 // ---------------------------------------------------------------------------------------------
+// The Jacobi leaves a zero column in U for every singular value that is exactly zero (V stays orthogonal: it is a product of rotations).
+// LAPACK completes the basis there, and so does this: rank 2 -> the cross product of the other two columns (the closest rotation is unique);
+// rank 1 -> any orthonormal pair beside the one column; rank 0 -> U = V, the identity.  Only called when s[kmin] == 0.
+__device__ void svd3_complete_u(double (&U)[3][3], const double (&s)[3], const double (&V)[3][3], int kmin) {
+    const int a = (kmin + 1) % 3, b = (kmin + 2) % 3;
+    if (s[a] > 0.0 && s[b] > 0.0) {
+        svd3_complete_column(U, kmin);
+    } else if (s[a] > 0.0 || s[b] > 0.0) {
+        const int c = s[a] > 0.0 ? a : b, p = (c + 1) % 3, q = (c + 2) % 3;   // column c is a unit vector; (c, p, q) is a cyclic order
+        int j = 0;                                                           // the axis least aligned with it
+        if (fabs(U[1][c]) < fabs(U[j][c])) j = 1;
+        if (fabs(U[2][c]) < fabs(U[j][c])) j = 2;
+        double e[3] = {0.0, 0.0, 0.0};
+        e[j] = 1.0;
+        double w[3] = {e[1] * U[2][c] - e[2] * U[1][c], e[2] * U[0][c] - e[0] * U[2][c], e[0] * U[1][c] - e[1] * U[0][c]};   // e x u_c
+        const double inv = 1.0 / sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+        for (int i = 0; i < 3; ++i) U[i][p] = w[i] * inv;
+        svd3_complete_column(U, q);                                          // u_q = u_c x u_p
+    } else {
+        for (int i = 0; i < 3; ++i)
+            for (int k = 0; k < 3; ++k) U[i][k] = V[i][k];
+    }
+}
+
 __device__ void svd3_project_so3(double (&M)[3][3]) {
     double s[3], U[3][3], V[3][3];
     svd3_jacobi(M, U, s, V);
     // the reflection correction acts on the SMALLEST singular direction (LAPACK orders them descending)
+    const int kmin = svd3_smallest(s);
+    if (s[kmin] == 0.0) svd3_complete_u(U, s, V, kmin);   // rank-deficient only: a full-rank block keeps its bits
     double D[3] = {1.0, 1.0, 1.0};
-    D[svd3_smallest(s)] = det3(U) * det3(V);  // det(V^T) == det(V)
+    D[kmin] = det3(U) * det3(V);  // det(V^T) == det(V)
     svd3_usvt(U, D, V, &M[0][0]);
 }
 
