@@ -33,11 +33,18 @@ RANSAC    hypothesis h draws three distinct correspondences with `_loop_closure_
           log(1 - confidence) / log(1 - (best / c)^3) <= the hypotheses tried (best = c: 0), else "max_iteration" after max_iteration.  The
           winner: the highest score, the lowest h.  best < 3: "degenerate", identity, zero mask, h = -1.  Then n_refit rounds of (Kabsch over
           the inliers, recount); fewer than 3 inliers or a collinear set: degenerate.  fitness = inliers / c, inlier_rmse over the inliers.
-The device computes singular vectors by Jacobi and adds the refit sums in another order: T and the RMSE agree to about 1e-9, every integer
-decision exactly as long as `margin` (relative to tau^2) is positive.  tau is rounded to float32 first, as the public layer rounds it.
+stages    `ransac` is composed of one function per device entry, each comparable on its own: `hypotheses` (bs_gr_hypotheses and
+          bs_gr_winner_fit: the fit is the identity where the edge-length checker or the rank test fails), `score` (bs_gr_score),
+          `winner_key` / `decode` (bs_gr_winner: score << 32 | ~h, pure integers), `refit_partials` (bs_gr_refit_step: per block of 256 rows
+          the 17 sums count, p, q, q p^T, r^2 over the inliers in the order of reduce.h's block_sum) and `refit_finish` (bs_gr_refit_finish:
+          the columns in the order of reduce.h's column_sum, then Kabsch from the sums or the final RMSE, and the 16-field state).
+The device computes singular vectors by Jacobi, the statement by LAPACK: transforms agree to about 1e-9, the refit's partial sums and the
+RMSE bit for bit, every integer decision exactly as long as `margin` (relative to tau^2) is positive -- `assert_clear` is the condition the
+tests hold an input to before they compare integers.  tau is rounded to float32 first, as the public layer rounds it.
 
-Also here, shared by tests/test_global_registration_cpu.py and tests/test_global_registration_gpu.py: the inputs (the bumpy pair of
-tests/_icp_ref.py at two poses, the constructed cloud, the planted correspondences, the recipe on thinned clouds)."""
+Also here, shared by tests/test_global_registration_cpu.py, tests/test_global_registration_gpu.py and
+tests/test_global_registration_stages_gpu.py: the inputs (the bumpy pair of tests/_icp_ref.py at two poses, the constructed cloud, the
+planted correspondences, the recipe on thinned clouds, the planted / exact scenes of the stage tests)."""
 import math
 import os
 import sys
@@ -46,6 +53,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _loop_closure_ref as LC  # noqa: E402
+from _mesh_ops_ref import wave_sum  # noqa: E402
 import _radius_ref as RR  # noqa: E402
 
 f32, f64 = np.float32, np.float64
@@ -253,72 +261,205 @@ def degenerate(c, **kw):
                      hypotheses=0, chunks=0, valid=np.zeros(0, bool), scores=np.zeros(0, np.int64)), **kw)
 
 
+MARGIN = 1e-10
+
+
+def assert_clear(margin):
+    """The condition under which integers are compared exactly: every discrete decision of the input (a checker, an inlier, a bin) lies at
+    least MARGIN from its threshold (RANSAC: relative to tau^2), far beyond what Jacobi against LAPACK or another order of the sums can
+    move a value."""
+    m = min(margin.values()) if isinstance(margin, dict) else float(margin)
+    assert m >= MARGIN, f"a decision lies {m:.3e} from its threshold (the bar is {MARGIN:.0e}): integers cannot be compared exactly"
+
+
+def _note(margins, r2, tau2):
+    if margins is not None and len(r2):
+        margins.append(float(np.min(np.abs(r2 - tau2)) / tau2))
+
+
+def _fit34(fit):
+    return np.concatenate([fit[0], fit[1][:, None]], 1)
+
+
+IDENTITY34 = np.eye(4)[:3]
+
+
+def hypotheses(P, Q, seed, h0, count, s_edge, tau):
+    """stage A (gr_hypotheses_kernel) for the hypotheses h0 .. h0 + count - 1 -> (ids int64 [count, 3], valid bool [count], fits float64
+    [count, 3, 4] = [R | t], margin).  The fit is the identity where the edge-length checker fails or Kabsch's rank test does, and Kabsch's
+    where only the distance checker failed.  margin: the edge-length decisions of every hypothesis and the distance decisions of every
+    fitted one, relative to tau^2."""
+    P, Q = np.asarray(P, f64).reshape(-1, 3), np.asarray(Q, f64).reshape(-1, 3)
+    c, s, tau2 = len(P), float(s_edge), float(tau) * float(tau)
+    ids = np.array([LC.sample(seed, 0, h, c) for h in range(h0, h0 + count)], np.int64).reshape(count, 3)
+    ok = np.ones(count, bool)
+    margin = np.inf
+    for a, b in ((0, 1), (0, 2), (1, 2)):
+        ds, dt = P[ids[:, a]] - P[ids[:, b]], Q[ids[:, a]] - Q[ids[:, b]]
+        ls = np.sqrt((ds[:, 0] * ds[:, 0] + ds[:, 1] * ds[:, 1]) + ds[:, 2] * ds[:, 2])
+        lt = np.sqrt((dt[:, 0] * dt[:, 0] + dt[:, 1] * dt[:, 1]) + dt[:, 2] * dt[:, 2])
+        ok &= (ls >= s * lt) & (lt >= s * ls)
+        margin = min(margin, float(np.min(np.abs(ls * ls - (s * lt) ** 2)) / tau2), float(np.min(np.abs(lt * lt - (s * ls) ** 2)) / tau2))
+    valid = np.zeros(count, bool)
+    fits = np.tile(IDENTITY34, (count, 1, 1))
+    for i in np.nonzero(ok)[0]:
+        fit = LC.kabsch(P[ids[i]], Q[ids[i]])
+        if fit is None:
+            continue
+        fits[i] = _fit34(fit)
+        r3 = _res2(fit, P[ids[i]], Q[ids[i]])
+        margin = min(margin, float(np.min(np.abs(r3 - tau2)) / tau2))
+        valid[i] = bool((r3 < tau2).all())
+    return ids, valid, fits, margin
+
+
+def score(P, Q, fits, listed, tau, margins=None):
+    """stage B (gr_score_kernel): fits [count, 3, 4], listed = the hypotheses to score (an entry outside 0 .. count - 1 is ignored) -> int64
+    [count], the number of correspondences with residual^2 < tau^2 (strictly), zero for a hypothesis that is not listed.  margins: a list
+    that receives the smallest |r^2 - tau^2| / tau^2 of every scored hypothesis."""
+    P, Q = np.asarray(P, f64).reshape(-1, 3), np.asarray(Q, f64).reshape(-1, 3)
+    fits = np.asarray(fits, f64).reshape(-1, 3, 4)
+    tau2 = float(tau) * float(tau)
+    out = np.zeros(len(fits), np.int64)
+    for i in np.asarray(listed, np.int64).reshape(-1):
+        if 0 <= i < len(fits):
+            r2 = _res2((fits[i, :, :3], fits[i, :, 3]), P, Q)
+            _note(margins, r2, tau2)
+            out[i] = int((r2 < tau2).sum())
+    return out
+
+
+def winner_key(best_key, scores, h0):
+    """stage C (gr_winner_kernel), pure integers: the maximum of best_key and (score << 32 | ~(h0 + t) mod 2^32) over the scores > 0 of a
+    chunk that starts at hypothesis h0 -- the highest score, then the lowest h; a score of zero never enters"""
+    key = int(best_key)
+    for t, sc in enumerate(np.asarray(scores, np.int64).reshape(-1).tolist()):
+        if sc > 0:
+            key = max(key, (sc << 32) | (~(int(h0) + t) & 0xffffffff))
+    return key
+
+
+def decode(key):
+    """-> (score, h) of a winner key"""
+    return int(key) >> 32, ~int(key) & 0xffffffff
+
+
+REFIT_BLOCK, REFIT_SUMS = 256, 17
+
+
+def refit_partials(P, Q, T, tau, margins=None):
+    """stage D, gr_refit_step_kernel: T [3 or 4, 4] -> (mask bool [c], partial float64 [ceil(c / 256), 17]).  A row of `partial` is a block's
+    sum of (1, p, q, q p^T row-major, r^2) over its inliers (r^2 < tau^2, r^2 in `_res2`'s order), each term started from +0.0 as kabsch_add
+    starts it, in the order of reduce.h's block_sum<17, 4>: inside each wave of 64 rows the xor butterfly 32, 16, .., 1, then the four waves
+    in order; a row that is absent or no inlier contributes +0.0."""
+    P, Q = np.asarray(P, f64).reshape(-1, 3), np.asarray(Q, f64).reshape(-1, 3)
+    T = np.asarray(T, f64)
+    c, tau2 = len(P), float(tau) * float(tau)
+    r2 = _res2((T[:3, :3], T[:3, 3]), P, Q)
+    _note(margins, r2, tau2)
+    mask = r2 < tau2
+    nb = -(-c // REFIT_BLOCK)
+    v = np.zeros((nb * REFIT_BLOCK, REFIT_SUMS), f64)
+    terms = np.concatenate([np.ones((c, 1)), 0.0 + P, 0.0 + Q, 0.0 + (Q[:, :, None] * P[:, None, :]).reshape(c, 9), r2[:, None]], 1)
+    v[:c] = np.where(mask[:, None], terms, 0.0)
+    v = v.reshape(nb, REFIT_BLOCK // 64, 64, REFIT_SUMS)
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, :, lane ^ o]
+    w = v[:, :, 0]
+    partial = w[:, 0]
+    for i in range(1, REFIT_BLOCK // 64):
+        partial = partial + w[:, i]
+    return mask, partial
+
+
+def kabsch_from_sums(s, n):
+    """rigid3.h's kabsch_from_sums with LAPACK's SVD: s = (sum p, sum q, sum q p^T row-major) over n pairs -> (R, t) or None where the second
+    singular value of S = sum q p^T - (sum q) mean(p)^T is below RANK_EPS"""
+    s = np.asarray(s, f64)
+    mp, mq = s[0:3] / n, s[3:6] / n
+    S = s[6:15].reshape(3, 3) - s[3:6, None] * mp[None, :]
+    if not np.all(np.isfinite(S)):
+        return None
+    U, d, Vt = np.linalg.svd(S)
+    if not d[1] >= LC.RANK_EPS:
+        return None
+    U, V = U.copy(), Vt.T.copy()
+    U[:, 2] = np.cross(U[:, 0], U[:, 1])
+    V[:, 2] = np.cross(V[:, 0], V[:, 1])
+    R = U @ V.T
+    return R, mq - R @ mp
+
+
+def refit_finish(partial, state, final):
+    """stage D, gr_refit_finish_kernel: partial [nblocks, 17], state [16] = (0-11 the rows of [R | t], 12 status, 13 inliers, 14 RMSE, 15 rounds)
+    -> the new state.  A status other than 1 on entry: nothing changes.  The columns are added as reduce.h's column_sum adds them (lane l
+    adds rows l, l + 64, ... in order from +0.0, then the butterfly: `wave_sum`); rounds + 1; fewer than 3 inliers: status 0.  final: inliers
+    and sqrt(sum r^2 / inliers).  Otherwise Kabsch from the sums replaces the transform, or status 0 where its rank test fails; the
+    transform stays as it was whenever the status is cleared."""
+    state = np.array(state, f64).reshape(16)
+    if state[12] != 1.0:
+        return state
+    partial = np.asarray(partial, f64).reshape(-1, REFIT_SUMS)
+    tot = np.array([wave_sum(partial[:, k]) for k in range(REFIT_SUMS)], f64)
+    state[15] = state[15] + 1.0
+    if not tot[0] >= 3.0:
+        state[12] = 0.0
+    elif final:
+        state[13], state[14] = tot[0], np.sqrt(tot[16] / tot[0])
+    else:
+        fit = kabsch_from_sums(tot[1:16], tot[0])
+        if fit is None:
+            state[12] = 0.0
+        else:
+            state[:12] = _fit34(fit).reshape(12)
+    return state
+
+
 def ransac(src, dst, tau, edge_length_threshold=0.9, max_iteration=100000, confidence=0.999, n_refit=2, seed=0):
-    """RANSAC over the correspondences src[i] -> dst[i] ([c, 3] each) -> dict(status, T, mask, h, inliers, fitness, rmse, hypotheses, chunks,
-    valid bool [hypotheses], scores int64 [hypotheses], margin = the smallest distance of any decision to its threshold relative to tau^2
-    (|r^2 - tau^2| / tau^2, |ls^2 - s^2 lt^2| / tau^2), unique = no second hypothesis reaches the winning score)"""
+    """RANSAC over the correspondences src[i] -> dst[i] ([c, 3] each), composed of the stages above -> dict(status, T, mask, h, inliers,
+    fitness, rmse, hypotheses, chunks, valid bool [hypotheses], scores int64 [hypotheses], margin = the smallest distance of any decision to
+    its threshold relative to tau^2 (|r^2 - tau^2| / tau^2, |ls^2 - s^2 lt^2| / tau^2), unique = no second hypothesis reaches the winning
+    score)"""
     P, Q = np.asarray(src, f64).reshape(-1, 3), np.asarray(dst, f64).reshape(-1, 3)
     tau = float(f32(tau))                                                  # (the public layer rounds the distance to float32 first, as registration_icp does)
-    c, s, tau2 = len(P), float(edge_length_threshold), tau * tau
+    c, s = len(P), float(edge_length_threshold)
     if c < 3:
         return degenerate(c)
-    margin, tried, chunks, best, status = np.inf, 0, 0, 0, "max_iteration"
+    margins, tried, chunks, key, status = [], 0, 0, 0, "max_iteration"
     valid_all, score_all = [], []
     while tried < max_iteration:
         cnt = min(CHUNK, max_iteration - tried)
-        ids = np.array([LC.sample(seed, 0, h, c) for h in range(tried, tried + cnt)], np.int64)
-        ok = np.ones(cnt, bool)
-        for a, b in ((0, 1), (0, 2), (1, 2)):
-            ds, dt = P[ids[:, a]] - P[ids[:, b]], Q[ids[:, a]] - Q[ids[:, b]]
-            ls = np.sqrt((ds[:, 0] * ds[:, 0] + ds[:, 1] * ds[:, 1]) + ds[:, 2] * ds[:, 2])
-            lt = np.sqrt((dt[:, 0] * dt[:, 0] + dt[:, 1] * dt[:, 1]) + dt[:, 2] * dt[:, 2])
-            ok &= (ls >= s * lt) & (lt >= s * ls)
-            margin = min(margin, float(np.min(np.abs(ls * ls - (s * lt) ** 2)) / tau2), float(np.min(np.abs(lt * lt - (s * ls) ** 2)) / tau2))
-        valid = np.zeros(cnt, bool)
-        score = np.zeros(cnt, np.int64)
-        for i in np.nonzero(ok)[0]:
-            fit = LC.kabsch(P[ids[i]], Q[ids[i]])
-            if fit is None:
-                continue
-            r3 = _res2(fit, P[ids[i]], Q[ids[i]])
-            margin = min(margin, float(np.min(np.abs(r3 - tau2)) / tau2))
-            if not (r3 < tau2).all():
-                continue
-            r2 = _res2(fit, P, Q)
-            margin = min(margin, float(np.min(np.abs(r2 - tau2)) / tau2))
-            valid[i] = True
-            score[i] = int((r2 < tau2).sum())
+        ids, valid, fits, m = hypotheses(P, Q, seed, tried, cnt, s, tau)
+        margins.append(m)
+        sc = score(P, Q, fits, np.nonzero(valid)[0], tau, margins)
+        key = winner_key(key, sc, tried)
         valid_all.append(valid)
-        score_all.append(score)
+        score_all.append(sc)
         tried += cnt
         chunks += 1
-        best = max(best, int(score.max()))
+        best = decode(key)[0]
         if best > 0 and stop_need(best, c, confidence) <= tried:
             status = "converged"
             break
     valid, scores = np.concatenate(valid_all), np.concatenate(score_all)
     common = dict(hypotheses=tried, chunks=chunks, valid=valid, scores=scores)
+    best, h = decode(key)
     if best < 3:
-        return degenerate(c, margin=margin, **common)
-    h = int(np.argmax(scores))                                             # (the first maximum: the lowest h)
+        return degenerate(c, margin=min(margins), **common)
     unique = int((scores == best).sum()) == 1
-    ids = list(LC.sample(seed, 0, h, c))
-    fit = LC.kabsch(P[ids], Q[ids])
+    state = np.zeros(16)
+    state[:12] = hypotheses(P, Q, seed, h, 1, s, tau)[2].reshape(12)       # (gr_winner_fit: the same code path as stage A)
+    state[12] = 1.0
     for rnd in range(n_refit + 1):
-        r2 = _res2(fit, P, Q)
-        margin = min(margin, float(np.min(np.abs(r2 - tau2)) / tau2))
-        mask = r2 < tau2
-        if mask.sum() < 3:
-            return degenerate(c, margin=margin, **common)
-        if rnd == n_refit:
-            break
-        fit = LC.kabsch(P[mask], Q[mask])
-        if fit is None:
-            return degenerate(c, margin=margin, **common)
+        mask, partial = refit_partials(P, Q, state[:12].reshape(3, 4), tau, margins)
+        state = refit_finish(partial, state, rnd == n_refit)
+        if state[12] != 1.0:
+            return degenerate(c, margin=min(margins), **common)
     T = np.eye(4)
-    T[:3, :3], T[:3, 3] = fit
-    return dict(status=status, T=T, mask=mask, h=h, inliers=int(mask.sum()), fitness=float(mask.sum()) / c, rmse=float(np.sqrt(np.mean(r2[mask]))),
-                margin=margin, unique=unique, **common)
+    T[:3] = state[:12].reshape(3, 4)
+    return dict(status=status, T=T, mask=mask, h=h, inliers=int(state[13]), fitness=float(state[13]) / c, rmse=float(state[14]),
+                margin=min(margins), unique=unique, **common)
 
 
 def ransac_on_features(src, dst, src_feat, dst_feat, mutual_filter, tau, **kw):
@@ -372,6 +513,56 @@ def planted(pair, n_true, n_total, seed):
     good = np.stack([rows, np.argmin(d, 1)], 1)
     bad = np.stack([rng.integers(0, len(pair["src"]), n_total - n_true), rng.integers(0, len(pair["tgt"]), n_total - n_true)], 1)
     return rng.permutation(np.concatenate([good, bad])).astype(np.int32)
+
+
+# ---- the scenes of the stage tests (tests/test_global_registration_stages_gpu.py; shown fair in tests/test_global_registration_cpu.py) ----------
+STAGE_POSE = axis_angle((0.3, -0.5, 0.8), 50.0, (0.02, -0.01, 0.03))
+STAGE_TAU = float(f32(0.002))
+STAGE_PLANTED = ((3, 3), (4, 3), (255, 90), (256, 90), (257, 90), (513, 150), (1025, 300), (16385, 5000))      # (c, n_true)
+
+
+def planted_scene(c, n_true, blocks=True):
+    """-> (P, Q float64 [c, 3]): P uniform in +-0.05 m; Q = STAGE_POSE P + N(0, 1e-4) on the first n_true rows, uniform on the rest.  With
+    `blocks` and c >= 255, rows 0 .. 5 of P lie on one line (true correspondences: a sample of three of them passes the edge-length
+    checker and fails the rank test) and the last three rows of P are one point (a sample with two of them fails the edge-length checker)."""
+    rng = np.random.default_rng(1000 + c)
+    P = rng.uniform(-0.05, 0.05, (c, 3))
+    if blocks and c >= 255:
+        P[:6] = P[0] + np.arange(6.0)[:, None] * np.array([0.004, -0.003, 0.002])
+        P[c - 3:] = P[c - 3]
+    Q = rng.uniform(-0.05, 0.05, (c, 3))
+    Q[:n_true] = P[:n_true] @ STAGE_POSE[:3, :3].T + STAGE_POSE[:3, 3] + rng.normal(0.0, 1e-4, (n_true, 3))
+    order = rng.permutation(c)                                             # the rows shuffled: true ones in every tile of 256, and in the last
+    last = int(np.nonzero(order < n_true)[0][-1])                          # row, so that the last block's partial row (c = 16385: the 65th) is
+    order[[last, c - 1]] = order[[c - 1, last]]                            # not zero
+    return P[order], Q[order]
+
+
+def blocks_scene():
+    """16 correspondences in which the degenerate samples are frequent: rows 0 .. 5 on one line and rows 9 .. 15 in general position, all
+    true; rows 6 .. 8 one point of P with three different targets"""
+    rng = np.random.default_rng(77)
+    P = rng.uniform(-0.05, 0.05, (16, 3))
+    P[:6] = P[0] + np.arange(6.0)[:, None] * np.array([0.004, -0.003, 0.002])
+    P[6:9] = P[6]
+    Q = P @ STAGE_POSE[:3, :3].T + STAGE_POSE[:3, 3] + rng.normal(0.0, 1e-4, (16, 3))
+    Q[6:9] = rng.uniform(-0.05, 0.05, (3, 3))
+    return P, Q
+
+
+EXACT_C = 300
+
+
+def exact_scene():
+    """-> (P, Q float64 [300, 3]) whose lengths, products and sums are exact in float64: P = distinct integer points of [-40, 40]^3 / 1024,
+    Q = a quarter turn about z, (x, y, z) -> (-y, x, z), plus (3, -2, 5) / 1024.  Every edge-length decision at edge_length_threshold = 1
+    sits exactly on ls == lt."""
+    rng = np.random.default_rng(300)
+    cells = rng.choice(81 ** 3, EXACT_C, replace=False)
+    K = np.stack([cells // 6561, (cells // 81) % 81, cells % 81], 1).astype(f64) - 40.0
+    P = K / 1024.0
+    Q = np.stack([0.0 - P[:, 1], P[:, 0], P[:, 2]], 1) + np.array([3.0, -2.0, 5.0]) / 1024.0
+    return P, Q
 
 
 CONSTRUCTED_RADIUS = 0.01

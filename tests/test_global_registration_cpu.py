@@ -182,6 +182,114 @@ def test_degenerate_statement():
     assert col["hypotheses"] == 4096 and not col["valid"].any()
 
 
+# ---- 3b: the statement in stages --------------------------------------------------------------------------------------------------------------------
+FROZEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "global_registration_ransac.npz")
+FROZEN_T_TOL = 1e-12      # T and the RMSE only: the refit now adds in reduce.h's order (the order the device is held to bit for bit), numpy's pairwise
+#                           one when the copy was frozen; Kabsch's S = sum q p^T - (sum q) mean(p)^T cancels two digits.  Measured 5.1e-14 and 2.8e-18.
+
+
+@pytest.mark.parametrize("n_total,max_iteration", [(1000, 100000), (5000, 20000)])
+def test_ransac_composed_of_stages_is_the_frozen_copy(n_total, max_iteration):
+    """golden/global_registration_ransac.npz holds what ransac() returned on the two planted cases while it was one function"""
+    p = pair("50")
+    cr = G.planted(p, 300, n_total, 5)
+    r = G.ransac(p["src"].astype(f64)[cr[:, 0]], p["tgt"].astype(f64)[cr[:, 1]], TAU, max_iteration=max_iteration)
+    with np.load(FROZEN) as z:
+        want = {k[len(f"c{n_total}_"):]: z[k] for k in z.files if k.startswith(f"c{n_total}_")}
+    got = [r["h"], r["inliers"], r["hypotheses"], r["chunks"], int(r["status"] == "converged"), int(r["unique"])]
+    print(n_total, got, "dT", np.abs(r["T"] - want["T"]).max(), "drmse", abs(r["rmse"] - want["floats"][0]))
+    assert got == want["scalars"].tolist()
+    assert np.array_equal(np.packbits(r["valid"]), want["valid"]) and np.array_equal(r["scores"], want["scores"])
+    assert np.array_equal(np.packbits(r["mask"]), want["mask"])
+    assert r["fitness"] == want["floats"][1] and r["margin"] == want["floats"][2]
+    assert np.abs(r["T"] - want["T"]).max() <= FROZEN_T_TOL and abs(r["rmse"] - want["floats"][0]) <= FROZEN_T_TOL
+
+
+def test_winner_key_round_trip_and_order():
+    top = (1 << 31) - 2
+    for h in (0, top):
+        key = G.winner_key(0, [7], h)
+        assert key == (7 << 32) | (0xffffffff - h) and G.decode(key) == (7, h)
+    assert G.winner_key(0, [0, 0, 0], 5) == 0                                            # a score of zero never enters
+    key = G.winner_key(0, [0, 4, 9, 9, 2], 100)                                          # a tie inside a chunk: the lower h
+    assert G.decode(key) == (9, 102)
+    assert G.winner_key(key, [9, 9], 4096) == key                                        # a tie in a later chunk does not displace
+    assert G.decode(G.winner_key(key, [3, 10], 4096)) == (10, 4097)                      # a larger score does
+    assert G.winner_key(key, [0, 0], 4096) == key
+    assert G.decode(G.winner_key(0, [1] * 257, top + 1 - 257)) == (1, top + 1 - 257) and G.decode(G.winner_key(0, [0] * 256 + [1], top + 1 - 257)) == (1, top)
+
+
+def test_refit_partials_add_the_plain_terms():
+    """c = 16385: 65 partial rows, the second trip of column_sum.  The fixed-order sums against numpy's of the same terms."""
+    c, n_true = G.STAGE_PLANTED[-1]
+    assert c == 16385 and -(-c // 256) == 65
+    P, Q = G.planted_scene(c, n_true)
+    mask, partial = G.refit_partials(P, Q, G.STAGE_POSE, G.STAGE_TAU)
+    r2 = np.sum((P @ G.STAGE_POSE[:3, :3].T + G.STAGE_POSE[:3, 3] - Q) ** 2, 1)
+    assert np.array_equal(mask, r2 < G.STAGE_TAU ** 2) and n_true <= mask.sum() < n_true + 50 and partial.shape == (65, 17)
+    terms = np.concatenate([np.ones((c, 1)), P, Q, (Q[:, :, None] * P[:, None, :]).reshape(c, 9), r2[:, None]], 1)[mask]
+    assert np.array_equal(partial[:, 0], np.add.reduceat(mask.astype(f64), np.arange(0, c, 256)))
+    assert partial[64, 0] == 1.0 and (partial[:, 0] > 0).all()                           # the 65th row is a true correspondence: lane 0's second row counts
+    assert np.allclose(partial.sum(0), terms.sum(0), rtol=1e-12, atol=0.0)
+    state = np.zeros(16)
+    state[:12], state[12] = G.STAGE_POSE[:3].reshape(12), 1.0
+    fin = G.refit_finish(partial, state, True)
+    assert fin[13] == mask.sum() and fin[15] == 1.0 and np.array_equal(fin[:13], state[:13])
+    assert abs(fin[14] - np.sqrt(r2[mask].mean())) <= 1e-12 * fin[14]
+    tot = np.array([G.wave_sum(partial[:, k]) for k in range(17)])
+    assert np.allclose(tot, terms.sum(0), rtol=1e-12, atol=0.0)
+    fit = G.refit_finish(partial, state, False)
+    want = G.LC.kabsch(P[mask], Q[mask])
+    assert fit[12] == 1.0 and fit[15] == 1.0 and np.abs(fit[:12].reshape(3, 4) - np.concatenate([want[0], want[1][:, None]], 1)).max() <= 1e-12
+
+
+def test_refit_state_machine_of_the_statement():
+    P, Q = G.exact_scene()
+    state = np.zeros(16)
+    state[:12], state[12] = np.eye(4)[:3].reshape(12), 1.0
+    line = P.copy()
+    line[:5] = np.arange(5.0)[:, None] * np.array([1.0, 2.0, -1.0]) / 1024.0
+    lq = line + 1.0
+    lq[:5] = line[:5]
+    for PP, QQ, want in ((P[:3], P[:3], 1.0), (P[:3], np.concatenate([P[:2], P[2:3] + 1.0]), 0.0), (line, lq, 0.0)):
+        mask, partial = G.refit_partials(PP, QQ, np.eye(4), G.STAGE_TAU)
+        for final in (False, True):
+            out = G.refit_finish(partial, state, final)
+            assert out[12] == (1.0 if final and mask.sum() >= 3 else want) and out[15] == 1.0
+            if out[12] == 0.0:
+                assert np.array_equal(out[:12], state[:12]) and out[13] == 0.0 and out[14] == 0.0
+    dead = state.copy()
+    dead[12] = 0.0
+    assert np.array_equal(G.refit_finish(partial, dead, False), dead)
+
+
+@pytest.mark.parametrize("c,n_true", G.STAGE_PLANTED)
+def test_stage_scenes_are_clear(c, n_true):
+    """every planted scene of the stage tests converges with every decision clear of its threshold, in one chunk"""
+    P, Q = G.planted_scene(c, n_true)
+    r = G.ransac(P, Q, G.STAGE_TAU, max_iteration=512 if c > 2000 else 4096)
+    print(c, n_true, r["status"], "h", r["h"], "inliers", r["inliers"], "valid", int(r["valid"].sum()), "margin", r["margin"])
+    G.assert_clear(r["margin"])
+    assert r["status"] == "converged" and r["chunks"] == 1 and n_true <= r["inliers"] <= n_true + 50
+    if c >= 255:                                                                        # (three noisy points fix a rotation to noise / extent only)
+        assert np.abs(r["T"] - G.STAGE_POSE).max() <= 1e-3
+
+
+def test_exact_scene_sits_on_the_edge_length_threshold():
+    P, Q = G.exact_scene()
+    assert len(np.unique(P, axis=0)) == G.EXACT_C and np.array_equal(P * 1024.0, np.round(P * 1024.0)) and MARGIN == G.MARGIN
+    for s in (0.9, 1.0):
+        r = G.ransac(P, Q, G.STAGE_TAU, edge_length_threshold=s, max_iteration=4096)
+        print(s, r["status"], r["h"], r["inliers"], r["margin"])
+        assert r["valid"].all() and len(r["valid"]) == 4096 and (r["scores"] == G.EXACT_C).all() and r["h"] == 0 and r["inliers"] == G.EXACT_C
+        assert (r["margin"] == 0.0) if s == 1.0 else (r["margin"] >= MARGIN)
+    grown = Q * (1.0 + 2.0 ** -20)                                                       # exact: no edge pair is congruent any more
+    assert np.array_equal(grown - Q, Q * 2.0 ** -20)
+    ids, valid, fits, margin = G.hypotheses(P, grown, 0, 0, 4096, 1.0, G.STAGE_TAU)
+    assert not valid.any() and margin >= MARGIN and np.array_equal(fits, np.tile(np.eye(4)[:3], (4096, 1, 1)))
+    assert G.hypotheses(P, grown, 0, 0, 4096, 0.9, G.STAGE_TAU)[3] >= MARGIN
+
+
 # ---- 4: the public layer --------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def built():

@@ -1,7 +1,9 @@
 """Global registration on the device against the numpy statement (tests/_global_registration_ref.py), stage by stage, each stage fed with the
 device's previous one where the stages chain: SPFH counts, FPFH rows, the feature match, RANSAC over planted correspondences, and the
-recipe end to end with the reconstruction evaluation that uses it.  Every discrete decision of these inputs lies at least 1e-10 from its
-threshold (tests/test_global_registration_cpu.py asserts it), so integers are compared exactly."""
+recipe end to end with the reconstruction evaluation that uses it.  Integers are compared exactly, under the condition that
+_global_registration_ref.assert_clear states and every test here that has a threshold asserts on its own input (the feature match has none:
+its distances are fp32 sums in one order on both sides, its ties exact); the entry points one
+at a time, at their edges and on their thresholds: tests/test_global_registration_stages_gpu.py."""
 import functools
 import os
 import sys
@@ -37,7 +39,8 @@ def statement(radius, max_nn):
     """the statement's lists, counts and k of the bumpy target, computed once"""
     tgt, tn = I.bumpy_target()
     ls = G.lists(tgt, radius, max_nn)
-    counts, k, _ = G.spfh(tgt, tn, *ls)
+    counts, k, margins = G.spfh(tgt, tn, *ls)
+    G.assert_clear(margins)
     return ls, counts, k
 
 
@@ -75,6 +78,7 @@ def test_spfh_constructed_rows(REG):
     r = G.CONSTRUCTED_RADIUS
     for max_nn in (None, 100):
         want = G.compute_fpfh(pts, nrm, r, max_nn)
+        G.assert_clear(want["margins"])
         for cell in (None, r / 4.0):
             f, s = REG._fpfh(pts, nrm, r, max_nn, cell, 0)
             got, gk = split_spfh(s.cpu().numpy())
@@ -117,7 +121,9 @@ def test_fpfh_repeats_chunks_and_the_method(REG, monkeypatch):
     bad = tgt.copy()
     bad[7] = np.nan                                                          # a non-finite point: a zero row, and nobody's neighbour
     fb = REG.compute_fpfh_feature(bad, tn, 0.010).cpu().numpy()
-    want = G.compute_fpfh(bad, tn, 0.010)["features"]
+    want = G.compute_fpfh(bad, tn, 0.010)
+    G.assert_clear(want["margins"])
+    want = want["features"]
     assert not fb[7].any() and np.array_equal(fb.view(np.uint32), want.view(np.uint32))
     fm = REG.mirror_fpfh(REG.compute_fpfh_feature(tgt, tn, 0.010))
     fn = REG.compute_fpfh_feature(tgt, -tn, 0.010)
@@ -185,6 +191,7 @@ def test_ransac_on_planted_correspondences(REG, monkeypatch, n_total, max_iterat
     p = pair("50")
     cr = G.planted(p, 300, n_total, 5)
     want = G.ransac(p["src"].astype(f64)[cr[:, 0]], p["tgt"].astype(f64)[cr[:, 1]], TAU, max_iteration=max_iteration)
+    G.assert_clear(want["margin"])
     monkeypatch.setattr(REG, "keep_tables", True)
     got = REG.registration_ransac_based_on_correspondence(p["src"], p["tgt"], cr, TAU, max_iteration=max_iteration)
     valid = np.concatenate([v for v, _ in REG.last_tables])
@@ -218,6 +225,7 @@ def test_ransac_on_feature_matching(REG):
     p = pair("170")
     s, t = pair_features("170")
     want, corres = G.ransac_on_features(p["src"], p["tgt"], s, t, False, TAU, max_iteration=4096)
+    G.assert_clear(want["margin"])
     got = REG.registration_ransac_based_on_feature_matching(p["src"], p["tgt"], s, t, False, TAU, max_iteration=4096)
     assert np.array_equal(got.correspondences.cpu().numpy(), corres) and got.h == want["h"] == MEASURED["raw_170"]["h"]
     assert got.inliers == want["inliers"] == MEASURED["raw_170"]["inliers"] and np.abs(got.transformation - want["T"]).max() <= T_TOL
@@ -237,6 +245,7 @@ def test_registration_global(REG, name):
     a = PC.voxel_down_sample(p["src"], VOXEL, normals=p["sn"], unit_normals=True)          # the statement on the device's thinned clouds
     b = PC.voxel_down_sample(p["tgt"], VOXEL, normals=p["tn"], unit_normals=True)
     want, corres, mirrored = G.recipe_on_thinned(*(x.cpu().numpy() for x in (a.points, a.normals, b.points, b.normals)), VOXEL, "given", **kw)
+    G.assert_clear(want["margin"])
     err, rot = errors(p, got.transformation, pose)
     m = MEASURED[f"recipe_{name}"]
     print(name, got.status, "h", got.h, "inliers", got.inliers, "of", len(corres), "err", err, "rot", rot)
