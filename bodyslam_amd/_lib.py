@@ -211,6 +211,11 @@ _SIGS = {
                           C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 8,
     "bs_mesh_closest_grid": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_int64,
                              C.c_float, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8,
+    "bs_mesh_hits_grid": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                          C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4,
+    "bs_mesh_hits_brute": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_hits_unpack": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 5,
     "bs_mesh_sample_weights": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_mesh_sample": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_int64] + [C.c_void_p] * 5,
     # mesh topology and clean-up (csrc/mesh_ops.hip); every pointer is a device pointer
@@ -1535,6 +1540,69 @@ def mesh_closest_grid(records, n_triangles, refs, cell_start, grid, query, max_d
                                               float(max_distance), int(shell_cap), p(geom_start), geom_start.numel() - 1, p(points), p(distance),
                                               p(geometry_ids), p(primitive_ids), p(uvs), p(fallback_list), p(fallback_count), stream_ptr()),
           "bs_mesh_closest_grid")
+
+
+MESH_HITS_COUNT, MESH_HITS_ANY, MESH_HITS_FILL = 0, 1, 2
+
+
+def _mesh_hits(rays, mode, out, row_start, keys):
+    """the sink of a bs_mesh_hits_* call -> total.  COUNT, ANY: out int32 [n]; FILL: row_start int64 [n + 1], keys int64 [total]"""
+    n = rays.shape[0]
+    _f32(rays, n, 6)
+    assert mode in (MESH_HITS_COUNT, MESH_HITS_ANY, MESH_HITS_FILL)
+    if mode == MESH_HITS_FILL:
+        _i64(row_start, keys)
+        assert row_start.numel() == n + 1 and keys.numel() >= 1
+        return keys.numel()
+    _i32(out)
+    assert out.numel() == n
+    return 0
+
+
+def mesh_hits_grid(records, n_triangles, refs, cell_start, grid, origin_limit, rays, mode, tnear, tfar, out, row_start, keys, fallback_list,
+                   fallback_count):
+    """every hit of the rays fp32 [n, 6] the walk covers into the sink of `mode` (_mesh_hits); the others on fallback_list int32 [>= n]"""
+    _mesh_records(records, n_triangles)
+    n = rays.shape[0]
+    total = _mesh_hits(rays, mode, out, row_start, keys)
+    (lo_, lo_p), (hi_, hi_p), h, (d_, d_p), pad = _mesh_grid(grid)
+    _mesh_index(refs, cell_start, d_, fallback_list, fallback_count, n)
+    check(load_library().bs_mesh_hits_grid(p(records), int(n_triangles), p(refs), p(cell_start), lo_p, hi_p, h, d_p, pad, float(origin_limit), p(rays), n,
+                                           int(mode), float(tnear), float(tfar), p(out), p(row_start), total, p(keys), p(fallback_list),
+                                           p(fallback_count), stream_ptr()), "bs_mesh_hits_grid")
+
+
+def mesh_hits_brute(records, n_triangles, rays, fallback_list, m, mode, tnear, tfar, out, row_start, keys, cursor):
+    """the rays of fallback_list (int32, m of them; None: all m = n) against every triangle into the sink of `mode`; cursor int32 [>= m]
+    scratch for FILL"""
+    _mesh_records(records, n_triangles)
+    n = rays.shape[0]
+    total = _mesh_hits(rays, mode, out, row_start, keys)
+    if fallback_list is None:
+        assert m == n
+    else:
+        _i32(fallback_list)
+        assert 1 <= m <= fallback_list.numel()
+    if mode == MESH_HITS_FILL:
+        _i32(cursor)
+        assert cursor.numel() >= m
+    check(load_library().bs_mesh_hits_brute(p(records), int(n_triangles), p(rays), n, p(fallback_list), int(m), int(mode), float(tnear), float(tfar),
+                                            p(out), p(row_start), total, p(keys), p(cursor), stream_ptr()), "bs_mesh_hits_brute")
+
+
+def mesh_hits_unpack(records, n_triangles, rays, keys, ray_ids, geom_start, t_hit, geometry_ids, primitive_ids, uvs):
+    """keys, ray_ids int64 [total] (sorted rows and the ray of each) -> t_hit fp32, geometry_ids, primitive_ids int32 [total], uvs fp32 [total, 2]"""
+    _mesh_records(records, n_triangles)
+    _f32(rays, rays.shape[0], 6)
+    _i64(keys, ray_ids)
+    total = keys.numel()
+    _f32(t_hit, total)
+    _f32(uvs, total, 2)
+    _i32(geom_start, geometry_ids, primitive_ids)
+    assert total >= 1 and ray_ids.numel() == total and geometry_ids.numel() == total and primitive_ids.numel() == total and geom_start.numel() >= 2
+    check(load_library().bs_mesh_hits_unpack(p(records), int(n_triangles), p(rays), rays.shape[0], p(keys), p(ray_ids), total, p(geom_start),
+                                             geom_start.numel() - 1, p(t_hit), p(geometry_ids), p(primitive_ids), p(uvs), stream_ptr()),
+          "bs_mesh_hits_unpack")
 
 
 def mesh_sample_weights(records, area, top, weights):

@@ -47,6 +47,7 @@
 //   bs_mesh_grid_count / _scatter   a thread per triangle over the cells of its padded box (its own cell range, inside the grid); integer atomics
 //   bs_mesh_cast_grid      one: a thread per ray, the walk below; at most nx + ny + nz + 3 steps
 //   bs_mesh_closest_grid   one: a thread per point, pc_walk (pc_grid.h) over triangle references
+//   bs_mesh_hits_grid / _brute / _unpack   one each: the walk or the brute-force block with a COUNT, ANY or FILL sink; see Counting below
 // No floating-point atomics anywhere: the same bits in every run.
 //
 // The grid and its bound.  lo, hi: the fp32 bounds of the kept triangles' vertices; cells by pc_cell; ext = the largest extent,
@@ -77,7 +78,26 @@
 //   the slab test o_a in [lo_a - pad, hi_a + pad].  A late stop costs time; an early one would be a wrong answer.
 //   Closest points.  After shell r the padded box of an unseen triangle is disjoint from the visited block, so pointcloud.hip's bound
 //   holds for every point of the box, and rule 2 puts the computed closest point in it; its slack is taken over hi + 2 pad.
-// Not built here: BVHs, test_occlusions, count / list_intersections, signed distance and occupancy.
+// Counting (bs_mesh_hits_*: count_intersections, list_intersections, test_occlusions; occupancy and the sign of a distance are composed
+//   from the counts; the statement is tests/_mesh_hits_ref.py, parity UNPINNED).  The closed predicate above lets an edge value of exactly
+//   0 be inside for both triangles at a shared edge: right for a minimum, wrong for a parity.  The COUNTING predicate (ms_ray_tri<true>)
+//   is the same arithmetic with one difference: an edge value E = Qx Py - Qy Px of the edge P -> Q that is exactly 0 in fp64 takes the
+//   sign of the first non-zero of (Qy - Py), -(Qx - Px), compared exactly -- the sign of E + eps (Qy - Py) + eps^2 (Px - Qx), E with the
+//   ray moved by (eps, eps^2) in the sheared plane.  Both zero: E stays 0, the triangle is edge-on and det rejects it.  The two triangles
+//   at an edge see P and Q reversed and decide opposite signs; around a vertex exactly one triangle of a fan claims the moved ray.  det, t,
+//   u, v come from the unperturbed values.
+//   Each hit exactly once.  A triangle is referenced from every cell of its box (ms_cell_range, the one expression of build and walk).
+//   Along a walk every cell index is monotone per axis, so the visited cells inside a box -- a product of three intervals -- are ONE
+//   contiguous run of the walk.  A triangle is tested only in the first cell of that run: the start cell, or a cell whose predecessor was
+//   outside the box; the predecessor differs in the one axis just stepped, so only that axis' range is computed.
+//   The bound still holds: (b) above shows that a triangle the closed predicate accepts is referenced in the VISITED cell of the state at
+//   t_Q, and the counting predicate accepts a subset of those (a tie only turns a zero into a sign).  The counting walk has no early stop
+//   -- (a) is not needed --, so it visits every cell the nearest-hit walk visits and more: the run of such a triangle is not empty, and
+//   its first cell tests it.  ANY stops at its first hit, which is a hit whatever lies beyond.  The fallback tests are those of
+//   ms_cast_grid_kernel; ms_hits_brute_kernel meets every (ray, triangle) pair in exactly one wave of one block.
+//   Loops: nx + ny + nz + 3 steps, the references of a cell, n_triangles.  Integer atomics only (counts, flags, a cursor per ray for
+//   keys); the rows are sorted by key afterwards (bs_pc_radius_sort; t >= +0, keys distinct), so no result depends on the order of arrival.
+// Not built here: BVHs, a fused pinhole kernel.
 #include <math.h>
 
 #include <algorithm>
@@ -121,6 +141,18 @@ __device__ __forceinline__ MsRay ms_ray(const float* __restrict__ ray) {
     return r;
 }
 
+// the sign of the fp64 edge value e of the edge P -> Q for a COUNT: an exact 0 takes the sign e would have with the ray moved by (eps, eps^2)
+// in the sheared plane, e + eps (Qy - Py) + eps^2 (Px - Qx) -- the first non-zero of the two, compared exactly; both zero: 0
+__device__ __forceinline__ int ms_tie_sign(double e, float Px, float Py, float Qx, float Qy) {
+    if (e > 0.0) return 1;
+    if (e < 0.0) return -1;
+    if (Qy != Py) return Qy > Py ? 1 : -1;
+    return Qx < Px ? 1 : (Qx > Px ? -1 : 0);
+}
+
+// TIE false: the closed predicate of the nearest hit (an edge value of 0 is inside for both triangles at the edge).  TIE true: the counting
+// predicate (ms_tie_sign: exactly one of them claims the ray).  Everything else -- det, t, u, v from the unperturbed values -- is shared.
+template <bool TIE = false>
 __device__ __forceinline__ bool ms_ray_tri(const MsRay& r, const f32x4 a, const f32x4 b, const f32x4 c, float& t, float& u, float& v) {
     const float Akz = ms_pick(a[0], a[1], a[2], r.kz) - r.oz, Bkz = ms_pick(b[0], b[1], b[2], r.kz) - r.oz, Ckz = ms_pick(c[0], c[1], c[2], r.kz) - r.oz;
     const float Ax = (ms_pick(a[0], a[1], a[2], r.kx) - r.ox) - r.Sx * Akz, Ay = (ms_pick(a[0], a[1], a[2], r.ky) - r.oy) - r.Sy * Akz;
@@ -132,8 +164,14 @@ __device__ __forceinline__ bool ms_ray_tri(const MsRay& r, const f32x4 a, const 
         const double Ud = (double)Cx * (double)By - (double)Cy * (double)Bx;
         const double Vd = (double)Ax * (double)Cy - (double)Ay * (double)Cx;
         const double Wd = (double)Bx * (double)Ay - (double)By * (double)Ax;
-        neg = Ud < 0.0 || Vd < 0.0 || Wd < 0.0;
-        pos = Ud > 0.0 || Vd > 0.0 || Wd > 0.0;
+        if (TIE) {
+            const int su = ms_tie_sign(Ud, Bx, By, Cx, Cy), sv = ms_tie_sign(Vd, Cx, Cy, Ax, Ay), sw = ms_tie_sign(Wd, Ax, Ay, Bx, By);
+            neg = su < 0 || sv < 0 || sw < 0;
+            pos = su > 0 || sv > 0 || sw > 0;
+        } else {
+            neg = Ud < 0.0 || Vd < 0.0 || Wd < 0.0;
+            pos = Ud > 0.0 || Vd > 0.0 || Wd > 0.0;
+        }
         U = (float)Ud; V = (float)Vd; W = (float)Wd;
     } else {
         neg = U < 0.0f || V < 0.0f || W < 0.0f;
@@ -381,6 +419,13 @@ __global__ void __launch_bounds__(MS_THREADS) ms_closest_finish_kernel(const f32
 }
 
 // ---- the grid ------------------------------------------------------------------------------------------------------------------------------
+// The cells of one axis a kept triangle is referenced from (a, b, c: its three coordinates on that axis): what the build scatters to and
+// what the counting walk takes the first cell of a run from -- one expression, so the two cannot disagree.
+__device__ __forceinline__ void ms_cell_range(float a, float b, float c, float pad, float lo, float h, int n, int& c0, int& c1) {
+    c0 = pc_cell(fminf(fminf(a, b), c) - pad, lo, h, n);
+    c1 = pc_cell(fmaxf(fmaxf(a, b), c) + pad, lo, h, n);
+}
+
 // SCATTER false: counts[cell] += 1 for every cell the triangle's padded box overlaps.  SCATTER true: `counts` is the cursor (a copy of the
 // exclusive scan) and the triangle's index goes to its slot.  The loops run over the triangle's own cell range, inside the grid.
 template <bool SCATTER>
@@ -392,10 +437,7 @@ __global__ void __launch_bounds__(MS_THREADS) ms_grid_kernel(const f32x4* __rest
     if (__float_as_int(a[3]) < 0) return;
     int c0[3], c1[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        c0[k] = pc_cell(fminf(fminf(a[k], b[k]), c[k]) - pad, g.lo[k], g.h, g.n[k]);
-        c1[k] = pc_cell(fmaxf(fmaxf(a[k], b[k]), c[k]) + pad, g.lo[k], g.h, g.n[k]);
-    }
+    for (int k = 0; k < 3; ++k) ms_cell_range(a[k], b[k], c[k], pad, g.lo[k], g.h, g.n[k], c0[k], c1[k]);
     for (int z = c0[2]; z <= c1[2]; ++z)
         for (int y = c0[1]; y <= c1[1]; ++y)
             for (int x = c0[0]; x <= c1[0]; ++x) {
@@ -478,6 +520,188 @@ __global__ void __launch_bounds__(MS_THREADS) ms_cast_grid_kernel(const f32x4* _
     }
     const unsigned long long key = bi == PC_NONE ? ~0ull : (((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(uint32_t)bi);
     ms_cast_write(records, n_triangles, key, rays, i, geom_start, n_geom, out);
+}
+
+// ---- every hit of a ray: counts, occlusion, lists ---------------------------------------------------------------------------------------------
+// MODE: BS_MESH_HITS_COUNT  out[ray] = the hits of the counting predicate with tnear <= t <= tfar
+//       BS_MESH_HITS_ANY    out[ray] = 1 when the CLOSED predicate has a hit with tnear <= t <= tfar (what cast_rays would find), else 0
+//       BS_MESH_HITS_FILL   the keys (t bits << 32 | global index) of COUNT's hits into keys [row_start[ray], row_start[ray + 1])
+struct MsHitsOut {
+    int32_t* out;
+    const int64_t* row_start;
+    int64_t total;
+    unsigned long long* keys;
+    float tnear, tfar;
+};
+
+template <int MODE>
+__device__ __forceinline__ bool ms_hits_test(const MsRay& ray, const f32x4 a, const f32x4 b, const f32x4 c, const MsHitsOut& o, float& t) {
+    float u, v;
+    return ms_ray_tri<MODE != BS_MESH_HITS_ANY>(ray, a, b, c, t, u, v) && t >= o.tnear && t <= o.tfar;
+}
+
+// the segment of ray `si` in keys: [b, b + cap), cap 0 for bounds that are not 0 <= b <= e <= total
+__device__ __forceinline__ void ms_hits_row(const MsHitsOut& o, int64_t si, int64_t& b, int64_t& cap) {
+    b = o.row_start[si];
+    const int64_t e = o.row_start[si + 1];
+    cap = (b >= 0 && e >= b && e <= o.total) ? e - b : 0;
+}
+
+// One thread per ray: ms_cast_grid_kernel's start, no early stop (ANY: at its first hit), and every hit exactly once -- a triangle is
+// tested only in the first visited cell of its cell box (the file header, "Counting").  `last`: the axis just stepped, -1 in the start cell.
+template <int MODE>
+__global__ void __launch_bounds__(MS_THREADS) ms_hits_grid_kernel(const f32x4* __restrict__ records, int64_t n_triangles,
+                                                                  const int32_t* __restrict__ refs, const int32_t* __restrict__ cell_start, PcGrid g,
+                                                                  float pad, float o_limit, const float* __restrict__ rays, int64_t m, MsHitsOut o,
+                                                                  int32_t* __restrict__ fb_list, int32_t* __restrict__ fb_count) {
+    const int64_t i = (int64_t)blockIdx.x * MS_THREADS + threadIdx.x;
+    if (i >= m) return;
+    if (MODE != BS_MESH_HITS_FILL) o.out[i] = 0;                   // (a ray on the list: the brute-force launch adds to it)
+    const MsRay ray = ms_ray(rays + 6 * i);
+    if (!ray.ok) return;
+    const float ox = rays[6 * i], oy = rays[6 * i + 1], oz = rays[6 * i + 2], dx = rays[6 * i + 3], dy = rays[6 * i + 4], dz = rays[6 * i + 5];
+    const float adx = fabsf(dx), ady = fabsf(dy), adz = fabsf(dz);
+    const bool dir_ok = (dx == 0.0f || (adx >= 8.673617e-19f && adx <= 1.1529215e+18f)) && (dy == 0.0f || (ady >= 8.673617e-19f && ady <= 1.1529215e+18f)) &&
+                        (dz == 0.0f || (adz >= 8.673617e-19f && adz <= 1.1529215e+18f));
+    if (!dir_ok || fabsf(ox) > o_limit || fabsf(oy) > o_limit || fabsf(oz) > o_limit) {
+        fb_list[atomicAdd(fb_count, 1)] = (int32_t)i;
+        return;
+    }
+    float t_in = 0.0f, t_out = INFINITY;
+    bool miss = false;
+    const float ix = dx != 0.0f ? __fdiv_rn(1.0f, dx) : 0.0f, iy = dy != 0.0f ? __fdiv_rn(1.0f, dy) : 0.0f, iz = dz != 0.0f ? __fdiv_rn(1.0f, dz) : 0.0f;
+#define MS_SLAB(o_, d_, inv_, a_)                                                                       \
+    if (d_ == 0.0f) {                                                                                   \
+        miss = miss || o_ < g.lo[a_] - pad || o_ > g.hi[a_] + pad;                                      \
+    } else {                                                                                            \
+        const float ta = ((g.lo[a_] - pad) - o_) * inv_, tb = ((g.hi[a_] + pad) - o_) * inv_;           \
+        t_in = fmaxf(t_in, fminf(ta, tb));                                                              \
+        t_out = fminf(t_out, fmaxf(ta, tb));                                                            \
+    }
+    MS_SLAB(ox, dx, ix, 0)
+    MS_SLAB(oy, dy, iy, 1)
+    MS_SLAB(oz, dz, iz, 2)
+#undef MS_SLAB
+    int32_t n = 0;
+    int64_t row = 0, cap = 0;
+    if (MODE == BS_MESH_HITS_FILL) ms_hits_row(o, i, row, cap);
+    if (!miss && t_in <= t_out) {
+        const int nx = g.n[0], ny = g.n[1], nz = g.n[2];
+        int cx = pc_cell(ox + t_in * dx, g.lo[0], g.h, nx), cy = pc_cell(oy + t_in * dy, g.lo[1], g.h, ny), cz = pc_cell(oz + t_in * dz, g.lo[2], g.h, nz);
+        const int sx = dx > 0.0f ? 1 : (dx < 0.0f ? -1 : 0), sy = dy > 0.0f ? 1 : (dy < 0.0f ? -1 : 0), sz = dz > 0.0f ? 1 : (dz < 0.0f ? -1 : 0);
+        const int steps = nx + ny + nz + 3;
+        int last = -1;
+        for (int k = 0; k < steps; ++k) {
+            // the cell before this one differs in `last` alone: a triangle whose range on that axis holds it was met in an earlier cell
+            const int prev = last == 0 ? cx - sx : (last == 1 ? cy - sy : cz - sz);
+            const float lo_l = ms_pick(g.lo[0], g.lo[1], g.lo[2], last);
+            const int n_l = last == 0 ? nx : (last == 1 ? ny : nz);
+            const int cell = (cz * ny + cy) * nx + cx;
+            const int32_t e = cell_start[cell + 1];
+            for (int32_t r = cell_start[cell]; r < e; ++r) {
+                const int32_t id = refs[r];
+                if (id < 0 || id >= n_triangles) continue;
+                const f32x4 a = records[3 * (int64_t)id], b = records[3 * (int64_t)id + 1], c = records[3 * (int64_t)id + 2];
+                if (last >= 0) {
+                    int c0, c1;
+                    ms_cell_range(ms_pick(a[0], a[1], a[2], last), ms_pick(b[0], b[1], b[2], last), ms_pick(c[0], c[1], c[2], last), pad, lo_l, g.h, n_l,
+                                  c0, c1);
+                    if (prev >= c0 && prev <= c1) continue;
+                }
+                float t;
+                if (!ms_hits_test<MODE>(ray, a, b, c, o, t)) continue;
+                if (MODE == BS_MESH_HITS_FILL && n < cap) o.keys[row + n] = ((unsigned long long)__float_as_uint(t) << 32) | (unsigned long long)(uint32_t)id;
+                ++n;
+            }
+            if (MODE == BS_MESH_HITS_ANY && n) break;
+            const float tx = sx ? ((g.lo[0] + (float)(cx + (sx > 0)) * g.h) - ox) * ix : INFINITY;
+            const float ty = sy ? ((g.lo[1] + (float)(cy + (sy > 0)) * g.h) - oy) * iy : INFINITY;
+            const float tz = sz ? ((g.lo[2] + (float)(cz + (sz > 0)) * g.h) - oz) * iz : INFINITY;
+            if (tx <= ty && tx <= tz) { if (!sx) break; last = 0; cx += sx; if (cx < 0 || cx >= nx) break; }
+            else if (ty <= tz) { if (!sy) break; last = 1; cy += sy; if (cy < 0 || cy >= ny) break; }
+            else { if (!sz) break; last = 2; cz += sz; if (cz < 0 || cz >= nz) break; }
+        }
+    }
+    if (MODE == BS_MESH_HITS_COUNT) o.out[i] = n;
+    if (MODE == BS_MESH_HITS_ANY) o.out[i] = n ? 1 : 0;
+}
+
+// The rays of `list` (or all) against every triangle, ms_brute_kernel's block: a pair (ray, triangle) is met by exactly one wave of one
+// block, so its hit is counted once.  COUNT adds the block's count (integer atomicAdd), ANY sets the flag (atomicOr), FILL takes a slot
+// from the ray's cursor (integer atomicAdd; cursor int32 [m], zeroed): the order of arrival is not fixed and the rows are sorted afterwards.
+template <int MODE>
+__global__ void __launch_bounds__(MS_THREADS) ms_hits_brute_kernel(const f32x4* __restrict__ records, int64_t n_triangles, const float* __restrict__ rays,
+                                                                   int64_t n_rows, int64_t m, const int32_t* __restrict__ list, int64_t chunk_len,
+                                                                   MsHitsOut o, int32_t* __restrict__ cursor) {
+    __shared__ f32x4 tile[3 * MS_TILE];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t q = (int64_t)blockIdx.x * MS_RAYS + lane;
+    bool valid = q < m;
+    int64_t si = 0;
+    if (valid) {
+        si = list ? (int64_t)list[q] : q;
+        valid = si >= 0 && si < n_rows;                     // (a listed row outside the array is no query)
+        if (!valid) si = 0;
+    }
+    MsRay ray = {};
+    if (valid) {
+        ray = ms_ray(rays + 6 * si);
+        valid = ray.ok;
+    }
+    int64_t row = 0, cap = 0;
+    if (MODE == BS_MESH_HITS_FILL && valid) ms_hits_row(o, si, row, cap);
+    const int64_t t0 = (int64_t)blockIdx.y * chunk_len, t1 = t0 + chunk_len < n_triangles ? t0 + chunk_len : n_triangles;
+    int32_t n = 0;
+    for (int64_t base = t0; base < t1; base += MS_TILE) {
+        __syncthreads();
+        const int cnt = t1 - base < MS_TILE ? (int)(t1 - base) : MS_TILE;
+        for (int k = t; k < 3 * cnt; k += MS_THREADS) tile[k] = records[3 * base + k];
+        __syncthreads();
+        for (int j = w; j < cnt; j += MS_WAVES) {
+            const f32x4 a = tile[3 * j], b = tile[3 * j + 1], c = tile[3 * j + 2];
+            const int32_t id = __float_as_int(a[3]);
+            if (id < 0 || !valid) continue;                 // (id is the same in every lane)
+            if (MODE == BS_MESH_HITS_ANY && n) continue;
+            float th;
+            if (!ms_hits_test<MODE>(ray, a, b, c, o, th)) continue;
+            if (MODE == BS_MESH_HITS_FILL) {
+                const int64_t pos = atomicAdd(&cursor[q], 1);
+                if (pos >= 0 && pos < cap) o.keys[row + pos] = ((unsigned long long)__float_as_uint(th) << 32) | (unsigned long long)(uint32_t)id;
+            }
+            ++n;
+        }
+    }
+    if (valid && n) {
+        if (MODE == BS_MESH_HITS_COUNT) atomicAdd(&o.out[si], n);
+        if (MODE == BS_MESH_HITS_ANY) atomicOr(&o.out[si], 1);
+    }
+}
+
+// row j of a sorted list: the triangle of the key against ray ray_ids[j] again (the counting predicate, the same bits) for t, uv and ids
+__global__ void __launch_bounds__(MS_THREADS) ms_hits_unpack_kernel(const f32x4* __restrict__ records, int64_t n_triangles, const float* __restrict__ rays,
+                                                                    int64_t n_rows, const unsigned long long* __restrict__ keys,
+                                                                    const int64_t* __restrict__ ray_ids, int64_t total,
+                                                                    const int32_t* __restrict__ geom_start, int32_t n_geom, float* __restrict__ t_hit,
+                                                                    int32_t* __restrict__ geometry_ids, int32_t* __restrict__ primitive_ids,
+                                                                    float* __restrict__ uvs) {
+    const int64_t j = (int64_t)blockIdx.x * MS_THREADS + threadIdx.x;
+    if (j >= total) return;
+    const int64_t gi = (int64_t)(keys[j] & 0xffffffffull), si = ray_ids[j];
+    float t = INFINITY, u = 0.0f, v = 0.0f;
+    int32_t geom = -1, prim = -1;
+    if (gi < n_triangles && si >= 0 && si < n_rows) {
+        const MsRay ray = ms_ray(rays + 6 * si);
+        if (ray.ok && ms_ray_tri<true>(ray, records[3 * gi], records[3 * gi + 1], records[3 * gi + 2], t, u, v)) {
+            geom = ms_geometry(geom_start, n_geom, (int32_t)gi);
+            prim = (int32_t)gi - geom_start[geom];
+        } else {
+            t = INFINITY; u = 0.0f; v = 0.0f;
+        }
+    }
+    t_hit[j] = t;
+    geometry_ids[j] = geom;
+    primitive_ids[j] = prim;
+    uvs[2 * j] = u; uvs[2 * j + 1] = v;
 }
 
 // The sink of pc_walk over triangle references: the minimum of (d2, index)
@@ -594,10 +818,32 @@ void ms_launch_brute(const f32x4* records, int64_t n_triangles, const float* in,
                        chunk_len, keys);
 }
 
+template <int MODE>
+void ms_launch_hits_brute(const f32x4* records, int64_t n_triangles, const float* rays, int64_t n_rows, int64_t m, const int32_t* list, const MsHitsOut& o,
+                          int32_t* cursor, hipStream_t st) {
+    const int64_t sb = cdiv64(m, MS_RAYS), tiles = cdiv64(n_triangles, MS_TILE);
+    const int64_t want = std::max<int64_t>(1, cdiv64(4 * (int64_t)cu_count(), sb));
+    const int64_t chunk_len = cdiv64(tiles, std::min<int64_t>(std::min<int64_t>(tiles, want), 65535)) * MS_TILE;
+    const int64_t chunks = cdiv64(n_triangles, chunk_len);
+    hipLaunchKernelGGL((ms_hits_brute_kernel<MODE>), dim3((unsigned)sb, (unsigned)chunks), dim3(MS_THREADS), 0, st, records, n_triangles, rays, n_rows, m,
+                       list, chunk_len, o, cursor);
+}
+
+// the sink's arguments, alike for the two launches: COUNT and ANY need out, FILL needs row_start, keys and 1 <= total < 2^31
+bool ms_hits_args(const char* who, int32_t mode, float tnear, float tfar, const int32_t* out, const int64_t* row_start, int64_t total, const void* keys) {
+    if (mode != BS_MESH_HITS_COUNT && mode != BS_MESH_HITS_ANY && mode != BS_MESH_HITS_FILL) { set_error("%s: unknown mode %d", who, mode); return false; }
+    if (!(tnear == tnear && tfar == tfar)) { set_error("%s: tnear %g, tfar %g", who, (double)tnear, (double)tfar); return false; }
+    if (mode == BS_MESH_HITS_FILL ? !(row_start && keys && total >= 1 && total < ((int64_t)1 << 31) && ((uintptr_t)keys & 7) == 0) : !out) {
+        set_error("%s: mode %d needs %s", who, mode, mode == BS_MESH_HITS_FILL ? "row_start, 8-byte aligned keys and 1 <= total < 2^31" : "out");
+        return false;
+    }
+    return true;
+}
+
 }  // namespace
 }  // namespace bs
 
-#define MS_ENTER(name)                                                                        \
+#define MS_ENTER(name)                                                                       \
     using namespace bs;                                                                       \
     if (!initialized()) { set_error(name ": call bs_init first"); return BS_ERR_NOT_INIT; }
 
@@ -786,6 +1032,77 @@ extern "C" int bs_mesh_sample(const void* records, int64_t n_triangles, const in
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(ms_sample_kernel, dim3((unsigned)cdiv64(n, MS_THREADS)), dim3(MS_THREADS), 0, st, static_cast<const f32x4*>(records),
                        n_triangles, cum, triangles, vertex_colors, n_vertices, seed, first, n, points, colors, normals, index);
+    BS_CHECK_LAUNCH();
+    return BS_OK;
+}
+
+// ---- every hit of a ray --------------------------------------------------------------------------------------------------------------------
+extern "C" int bs_mesh_hits_grid(const void* records, int64_t n_triangles, const int32_t* refs, const int32_t* cell_start, const float* lo,
+                                 const float* hi, float cell_size, const int32_t* dims, float pad, float origin_limit, const float* rays, int64_t m,
+                                 int32_t mode, float tnear, float tfar, int32_t* out, const int64_t* row_start, int64_t total, void* keys,
+                                 int32_t* fallback_list, int32_t* fallback_count, void* stream) {
+    MS_ENTER("bs_mesh_hits_grid");
+    PcGrid g;
+    BS_REQUIRE(refs && cell_start && rays && fallback_list && fallback_count, "bs_mesh_hits_grid: null pointer");
+    BS_REQUIRE(m >= 1 && m < ((int64_t)1 << 31) && origin_limit >= 0.0f, "bs_mesh_hits_grid: m = %lld, origin limit %g", (long long)m,
+               (double)origin_limit);
+    if (!ms_hits_args("bs_mesh_hits_grid", mode, tnear, tfar, out, row_start, total, keys)) return BS_ERR_INVALID;
+    if (!ms_grid_args("bs_mesh_hits_grid", records, n_triangles, lo, hi, cell_size, dims, pad, g)) return BS_ERR_INVALID;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    BS_CHECK_HIP(hipMemsetAsync(fallback_count, 0, 4, st));
+    const MsHitsOut o{out, row_start, total, static_cast<unsigned long long*>(keys), tnear, tfar};
+    const dim3 grid((unsigned)cdiv64(m, MS_THREADS)), block(MS_THREADS);
+    const f32x4* rec = static_cast<const f32x4*>(records);
+#define MS_HITS_GRID(MODE_)                                                                                                                    \
+    hipLaunchKernelGGL(ms_hits_grid_kernel<MODE_>, grid, block, 0, st, rec, n_triangles, refs, cell_start, g, pad, origin_limit, rays, m, o, \
+                       fallback_list, fallback_count)
+    if (mode == BS_MESH_HITS_COUNT) MS_HITS_GRID(BS_MESH_HITS_COUNT);
+    else if (mode == BS_MESH_HITS_ANY) MS_HITS_GRID(BS_MESH_HITS_ANY);
+    else MS_HITS_GRID(BS_MESH_HITS_FILL);
+#undef MS_HITS_GRID
+    BS_CHECK_LAUNCH();
+    return BS_OK;
+}
+
+extern "C" int bs_mesh_hits_brute(const void* records, int64_t n_triangles, const float* rays, int64_t n_rows, const int32_t* list, int64_t m,
+                                  int32_t mode, float tnear, float tfar, int32_t* out, const int64_t* row_start, int64_t total, void* keys,
+                                  int32_t* cursor, void* stream) {
+    MS_ENTER("bs_mesh_hits_brute");
+    BS_REQUIRE(rays && (records || n_triangles == 0), "bs_mesh_hits_brute: null pointer");
+    BS_REQUIRE(n_rows >= m && n_rows < ((int64_t)1 << 31), "bs_mesh_*_brute: %lld rows for m = %lld", (long long)n_rows, (long long)m);
+    BS_REQUIRE(m >= 1 && n_triangles >= 0 && n_triangles <= BS_MESH_MAX_TRIANGLES, "bs_mesh_hits_brute: m = %lld, %lld triangles", (long long)m,
+               (long long)n_triangles);
+    BS_REQUIRE(((uintptr_t)records & 15) == 0, "bs_mesh_hits_brute: records must be 16-byte aligned");
+    if (!ms_hits_args("bs_mesh_hits_brute", mode, tnear, tfar, out, row_start, total, keys)) return BS_ERR_INVALID;
+    BS_REQUIRE(mode != BS_MESH_HITS_FILL || cursor, "bs_mesh_hits_brute: mode %d needs cursor", mode);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // without a list every row is this call's; with one, bs_mesh_hits_grid has zeroed the listed rows
+    if (mode != BS_MESH_HITS_FILL && !list) BS_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)m * 4, st));
+    if (mode == BS_MESH_HITS_FILL) BS_CHECK_HIP(hipMemsetAsync(cursor, 0, (size_t)m * 4, st));
+    if (n_triangles > 0) {
+        const MsHitsOut o{out, row_start, total, static_cast<unsigned long long*>(keys), tnear, tfar};
+        const f32x4* rec = static_cast<const f32x4*>(records);
+        if (mode == BS_MESH_HITS_COUNT) ms_launch_hits_brute<BS_MESH_HITS_COUNT>(rec, n_triangles, rays, n_rows, m, list, o, cursor, st);
+        else if (mode == BS_MESH_HITS_ANY) ms_launch_hits_brute<BS_MESH_HITS_ANY>(rec, n_triangles, rays, n_rows, m, list, o, cursor, st);
+        else ms_launch_hits_brute<BS_MESH_HITS_FILL>(rec, n_triangles, rays, n_rows, m, list, o, cursor, st);
+        BS_CHECK_LAUNCH();
+    }
+    return BS_OK;
+}
+
+extern "C" int bs_mesh_hits_unpack(const void* records, int64_t n_triangles, const float* rays, int64_t n_rows, const void* keys, const int64_t* ray_ids,
+                                   int64_t total, const int32_t* geom_start, int32_t n_geom, float* t_hit, int32_t* geometry_ids,
+                                   int32_t* primitive_ids, float* primitive_uvs, void* stream) {
+    MS_ENTER("bs_mesh_hits_unpack");
+    BS_REQUIRE(records && rays && keys && ray_ids && geom_start && t_hit && geometry_ids && primitive_ids && primitive_uvs,
+               "bs_mesh_hits_unpack: null pointer");
+    BS_REQUIRE(n_rows >= 1 && n_rows < ((int64_t)1 << 31) && total >= 1 && total < ((int64_t)1 << 31) && n_triangles >= 1 &&
+               n_triangles <= BS_MESH_MAX_TRIANGLES && n_geom >= 1, "bs_mesh_hits_unpack: %lld rays, total = %lld, %lld triangles, %d geometries",
+               (long long)n_rows, (long long)total, (long long)n_triangles, n_geom);
+    BS_REQUIRE(((uintptr_t)records & 15) == 0 && ((uintptr_t)keys & 7) == 0, "bs_mesh_hits_unpack: records must be 16-byte, keys 8-byte aligned");
+    hipLaunchKernelGGL(ms_hits_unpack_kernel, dim3((unsigned)cdiv64(total, MS_THREADS)), dim3(MS_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+                       static_cast<const f32x4*>(records), n_triangles, rays, n_rows, static_cast<const unsigned long long*>(keys), ray_ids, total,
+                       geom_start, n_geom, t_hit, geometry_ids, primitive_ids, primitive_uvs);
     BS_CHECK_LAUNCH();
     return BS_OK;
 }

@@ -656,6 +656,66 @@ def evaluate_reconstruction_surface(pred, gt, thresholds: Sequence[float] = (0.0
     return _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, align, icp, gt_mesh, n_gt_samples)
 
 
+@dataclass
+class SignedReconstructionMetrics:
+    """surface: evaluate_reconstruction_surface's result, the same bits.  The pred points with a finite distance to the surface (the ones
+    its accuracy counts) are split by compute_occupancy of the ground-truth mesh: n_inside, n_outside, fraction_inside = n_inside / their
+    sum (NaN for none); inside, outside: the DistanceStats of the two subsets' distances; signed_mean = (the sum of the outside distances -
+    the sum of the inside distances) / their number -- negative for a map that lies inside the organ, as one with too small a depth scale
+    does, positive for one outside.  An unsigned distance cannot tell the two apart."""
+    surface: ReconstructionMetrics
+    n_inside: int
+    n_outside: int
+    fraction_inside: float
+    inside: DistanceStats
+    outside: DistanceStats
+    signed_mean: float
+
+    def as_dict(self) -> Dict[str, float]:
+        out = self.surface.as_dict()
+        for side, st in (("inside", self.inside), ("outside", self.outside)):
+            for k in DISTANCE_STAT_NAMES:
+                out[f"{side}_{k}"] = float(getattr(st, k))
+        out["fraction_inside"], out["signed_mean"] = float(self.fraction_inside), float(self.signed_mean)
+        out["n_inside"], out["n_outside"] = int(self.n_inside), int(self.n_outside)
+        return out
+
+
+def evaluate_reconstruction_signed(pred, gt, thresholds: Sequence[float] = (0.001, 0.002, 0.005), transform=None,
+                                   max_distance: Optional[float] = None, align: Optional[str] = None, icp: Optional[dict] = None,
+                                   n_gt_samples: Optional[int] = None, nsamples: int = 1) -> SignedReconstructionMetrics:
+    """evaluate_reconstruction_surface(pred, gt, ..., gt_mesh="surface") and on which SIDE of the ground-truth surface the reconstruction
+    lies (SignedReconstructionMetrics).  gt: a tsdf.TriangleMesh that is_closed(), else ValueError -- the sign of a distance is defined
+    only for a closed mesh; it is undefined for a point at distance ~ 0.  The side is RaycastingScene.compute_occupancy(points, nsamples)
+    of the very points the accuracy side measures: after `transform` and the optional alignment.  nsamples: odd, 1 .. 15; more than one
+    outvotes a sample whose ray meets a triangle edge-on.  (A function of its own: evaluate_reconstruction_surface's parameter list is
+    pinned by tests/test_mesh_scene_cpu.py.)"""
+    from .raycasting import _check_nsamples
+    from .tsdf import TriangleMesh
+    n = _check_nsamples(nsamples)
+    if not isinstance(gt, TriangleMesh):
+        raise ValueError(f"evaluate_reconstruction_signed needs a tsdf.TriangleMesh as gt, got {type(gt).__name__}")
+    _check_gt_mesh("surface", gt, n_gt_samples)
+    _check_thresholds(thresholds)
+    _check_align(align, icp)
+    AR.device_for()
+    if not gt.is_closed():
+        raise ValueError("gt: the mesh is not closed (an edge without exactly two triangles): the side of its surface is not defined")
+    side: dict = {"nsamples": n}
+    surface = _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, align, icp, "surface", n_gt_samples, side)
+    d, occ = side["distance"], side["occupancy"]
+    matched = torch.isfinite(d)
+    d_in, d_out = d[matched & (occ == 1.0)].contiguous(), d[matched & (occ != 1.0)].contiguous()
+    none = np.zeros(L.PC_STATS_FIELDS)                                # (bs_pc_stats takes no empty tensor: the record of no distances)
+    r_in = distance_stats_record(d_in) if d_in.numel() else none
+    r_out = distance_stats_record(d_out) if d_out.numel() else none
+    n_in, n_out = int(d_in.numel()), int(d_out.numel())
+    total = n_in + n_out
+    return SignedReconstructionMetrics(surface=surface, n_inside=n_in, n_outside=n_out, fraction_inside=n_in / total if total else math.nan,
+                                       inside=_distance_stats(r_in), outside=_distance_stats(r_out),
+                                       signed_mean=float(r_out[4] - r_in[4]) / total if total else math.nan)
+
+
 def _check_gt_mesh(gt_mesh, gt, n_gt_samples) -> bool:
     from .tsdf import TriangleMesh
     if gt_mesh not in GT_MESH:
@@ -676,7 +736,9 @@ def _check_gt_mesh(gt_mesh, gt, n_gt_samples) -> bool:
 
 
 def _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, align, icp, gt_mesh="vertices",
-                             n_gt_samples=None) -> ReconstructionMetrics:
+                             n_gt_samples=None, side: Optional[dict] = None) -> ReconstructionMetrics:
+    """side (evaluate_reconstruction_signed): a dict with "nsamples"; it receives "distance", the accuracy side's distances, and
+    "occupancy" of the same points in the same scene"""
     from . import pointcloud as PC
     from .tsdf import MAP, TSDF
     surface = _check_gt_mesh(gt_mesh, gt, n_gt_samples)
@@ -724,6 +786,8 @@ def _evaluate_reconstruction(pred, gt, thresholds, transform, max_distance, alig
             scene = RaycastingScene(device=dev.index)
             scene.add_triangles(gt)
             d_pg = scene.compute_distance(p, max_distance=max_distance)
+            if side is not None:
+                side["distance"], side["occupancy"] = d_pg, scene.compute_occupancy(p, nsamples=side["nsamples"])
         else:
             d_pg, _ = PC.NearestNeighbours(g).query(p, max_distance=max_distance)
         d_gp, _ = PC.NearestNeighbours(p).query(g, max_distance=max_distance)

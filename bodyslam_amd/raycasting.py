@@ -15,8 +15,13 @@ kernels (rays across lanes, triangles streamed through LDS tiles); ``method="bru
 The cell size changes the time, never the result: both methods return the same bits (the bound: top of csrc/mesh_scene.hip).  There is no
 CPU fallback: without a GPU the calls raise BodySlamHipError.
 
-Not built: BVHs, test_occlusions, count_intersections, list_intersections, signed distance and occupancy (they need a watertight mesh), a
-fused pinhole kernel that never materialises rays.
+Every hit of a ray, not the nearest (count_intersections, list_intersections, test_occlusions; compute_occupancy and
+compute_signed_distance are composed from the counts): the same walk without its early stop, every triangle tested in the first visited
+cell of its cell range, and -- for counts and lists -- a COUNTING predicate: cast_rays' arithmetic, except that an edge value of exactly 0
+takes the sign it would have with the ray moved by (eps, eps^2) in the sheared plane, so that exactly one of the triangles at a shared edge
+or vertex claims the ray and the parity of a count is right for a closed mesh (tests/_mesh_hits_ref.py; parity with Open3D unpinned).
+
+Not built: BVHs, a fused pinhole kernel that never materialises rays.
 """
 from __future__ import annotations
 
@@ -29,6 +34,9 @@ from . import _args as AR
 from . import _lib as L
 from . import pointcloud as PC
 
+# sample j of an occupancy query casts along row j: exactly representable directions
+OCCUPANCY_DIRECTIONS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1), (-1, 1, 1), (1, -1, 1), (1, 1, -1), (-1, 0, 0), (0, -1, 0), (0, 0, -1), (-1, -1, -1),
+                        (1, -1, -1), (-1, 1, -1), (-1, -1, 1), (1, 2, 3))
 INVALID_ID = 0xFFFFFFFF             # geometry_ids / primitive_ids of a miss: the bit pattern of -1 in the int32 tensors returned
 METHODS = ("grid", "brute")
 SHELL_CAP = PC.SHELL_CAP
@@ -72,6 +80,23 @@ def _as_rows(x, width: int, what: str) -> torch.Tensor:
 def _check_method(method) -> None:
     if method not in METHODS:
         raise ValueError(f"unknown method {method!r}: one of {METHODS}")
+
+
+def _check_range(tnear, tfar):
+    """-> (tnear, tfar) as the fp32 values the kernels compare with; ValueError for anything but two numbers that are not NaN"""
+    out = []
+    for name, v in (("tnear", tnear), ("tfar", tfar)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or v != v:
+            raise ValueError(f"{name} {v!r}: expected a number")
+        out.append(float(np.float32(v)))
+    return tuple(out)
+
+
+def _check_nsamples(nsamples) -> int:
+    n = AR.integer(nsamples, "nsamples", 1, len(OCCUPANCY_DIRECTIONS), "an odd integer in 1 .. 15")
+    if n % 2 == 0:
+        raise ValueError(f"nsamples {nsamples!r}: expected an odd integer in 1 .. 15")
+    return n
 
 
 class RaycastingScene:
@@ -249,3 +274,119 @@ class RaycastingScene:
     def compute_distance(self, query, max_distance: Optional[float] = None, method: str = "grid") -> torch.Tensor:
         """compute_closest_points(query)["distance"]: fp32 [...] device tensor, the unsigned distance to the surface"""
         return self.compute_closest_points(query, max_distance=max_distance, method=method)["distance"]
+
+    # ---- every hit of a ray ----------------------------------------------------------------------------------------------------------------
+    def _hits(self, r: torch.Tensor, mode: int, method: str, tnear: float = 0.0, tfar: float = float("inf"), out=None, row_start=None, keys=None):
+        """one sink (L.MESH_HITS_*) over the rays r fp32 [m, 6] on the device, m >= 1: the walk and the brute force for its list, or the brute
+        force alone"""
+        m = int(r.shape[0])
+        fill = mode == L.MESH_HITS_FILL
+        if method == "grid" and self.grid is not None:
+            fb_list = torch.empty(m, dtype=torch.int32, device=self.dev)
+            fb_count = torch.empty(1, dtype=torch.int32, device=self.dev)
+            L.mesh_hits_grid(self.records, self.n_triangles, self.refs, self.cell_start, self.grid, self.origin_limit, r, mode, tnear, tfar, out,
+                             row_start, keys, fb_list, fb_count)
+            n_fb = int(fb_count.cpu())
+            if n_fb:
+                cursor = torch.empty(n_fb, dtype=torch.int32, device=self.dev) if fill else None
+                L.mesh_hits_brute(self.records, self.n_triangles, r, fb_list, n_fb, mode, tnear, tfar, out, row_start, keys, cursor)
+            self.last_fallback = n_fb
+        else:
+            cursor = torch.empty(m, dtype=torch.int32, device=self.dev) if fill else None
+            L.mesh_hits_brute(self.records, self.n_triangles, r, None, m, mode, tnear, tfar, out, row_start, keys, cursor)
+
+    def _rays(self, rays):
+        r = _as_rows(rays, 6, "rays")
+        self._build()
+        return tuple(r.shape[:-1]), r
+
+    def count_intersections(self, rays, method: str = "grid") -> torch.Tensor:
+        """rays [..., 6] as ``cast_rays`` takes them -> int32 [...] device tensor: how many kept triangles the ray hits with 0 <= t < inf
+        under the counting predicate (the module's docstring): a ray through a shared edge or vertex counts one of the triangles there, so
+        for a closed mesh the count's parity says on which side the origin lies.  A ray that passes a triangle seen edge-on (|det| below
+        2^-12 of its products) does not count it: such a ray can be off by one.  A ray with a non-finite component or a zero direction: 0."""
+        _check_method(method)
+        shape, r = self._rays(rays)
+        with torch.cuda.device(self.dev):
+            r = r.to(self.dev).to(torch.float32).reshape(-1, 6).contiguous()
+            out = torch.zeros(int(r.shape[0]), dtype=torch.int32, device=self.dev)
+            if r.shape[0]:
+                self._hits(r, L.MESH_HITS_COUNT, method, out=out)
+        return out.reshape(shape)
+
+    def test_occlusions(self, rays, tnear: float = 0.0, tfar: float = float("inf"), method: str = "grid") -> torch.Tensor:
+        """rays [..., 6] -> bool [...] device tensor: whether the ray hits a kept triangle with tnear <= t <= tfar (compared in fp32) under
+        ``cast_rays``' own closed predicate, found by a walk that stops at the first such hit: with the defaults it equals
+        isfinite(cast_rays(rays)["t_hit"]) exactly.  A ray with a non-finite component or a zero direction: False."""
+        _check_method(method)
+        tn, tf = _check_range(tnear, tfar)
+        shape, r = self._rays(rays)
+        with torch.cuda.device(self.dev):
+            r = r.to(self.dev).to(torch.float32).reshape(-1, 6).contiguous()
+            out = torch.zeros(int(r.shape[0]), dtype=torch.int32, device=self.dev)
+            if r.shape[0]:
+                self._hits(r, L.MESH_HITS_ANY, method, tn, tf, out=out)
+        return (out != 0).reshape(shape)
+
+    def list_intersections(self, rays, method: str = "grid") -> Dict[str, torch.Tensor]:
+        """rays [..., 6], m of them when flattened -> a dict of device tensors over all the hits ``count_intersections`` counts: ray_splits
+        int64 [m + 1] (the rows of ray i are ray_splits[i] .. ray_splits[i + 1] - 1); ray_ids int64 [total]; t_hit fp32 [total];
+        geometry_ids, primitive_ids int32 [total]; primitive_uvs fp32 [total, 2], as ``cast_rays`` defines them.  Rows are in ray order
+        and, within a ray, ascending in (t, global triangle index).  ValueError when total exceeds 2^31 - 1.  For a ray with no edge value
+        of exactly 0 the first row is ``cast_rays``' hit."""
+        _check_method(method)
+        _, r = self._rays(rays)
+        with torch.cuda.device(self.dev):
+            r = r.to(self.dev).to(torch.float32).reshape(-1, 6).contiguous()
+            m = int(r.shape[0])
+            counts = torch.zeros(m, dtype=torch.int32, device=self.dev)
+            if m:
+                self._hits(r, L.MESH_HITS_COUNT, method, out=counts)
+            splits = torch.zeros(m + 1, dtype=torch.int64, device=self.dev)
+            splits[1:] = torch.cumsum(counts, 0, dtype=torch.int64)                          # the scan is plumbing: integer, exact
+            total = int(splits[-1].cpu())
+            if total > 2 ** 31 - 1:
+                raise ValueError(f"list_intersections: {total} hits, at most 2^31 - 1")
+            f = dict(dtype=torch.float32, device=self.dev)
+            out = dict(ray_splits=splits, ray_ids=torch.repeat_interleave(torch.arange(m, dtype=torch.int64, device=self.dev), counts.to(torch.int64)),
+                       t_hit=torch.empty(total, **f), geometry_ids=torch.empty(total, dtype=torch.int32, device=self.dev),
+                       primitive_ids=torch.empty(total, dtype=torch.int32, device=self.dev), primitive_uvs=torch.empty(total, 2, **f))
+            if total:
+                keys, ordered = torch.empty(total, dtype=torch.int64, device=self.dev), torch.empty(total, dtype=torch.int64, device=self.dev)
+                self._hits(r, L.MESH_HITS_FILL, method, row_start=splits, keys=keys)
+                L.pc_radius_sort(keys, splits, ordered)
+                L.mesh_hits_unpack(self.records, self.n_triangles, r, ordered, out["ray_ids"].contiguous(), self.geom_start, out["t_hit"],
+                                   out["geometry_ids"], out["primitive_ids"], out["primitive_uvs"])
+        return out
+
+    def compute_occupancy(self, query, nsamples: int = 1, method: str = "grid") -> torch.Tensor:
+        """query [..., 3] -> fp32 [...] device tensor: 1.0 inside, 0.0 outside, NaN for a query with a non-finite coordinate.  Sample j casts
+        from the query along OCCUPANCY_DIRECTIONS[j]; the point is inside when the majority of the nsamples (odd, 1 .. 15, else ValueError)
+        ``count_intersections`` is odd (rays and vote are composed with torch: plumbing, integers).  The answer is meaningful only for a
+        CLOSED mesh (tsdf.TriangleMesh.is_closed) and is undefined at distance ~ 0 from the surface.  A ray through a triangle seen
+        edge-on (the 2^-12 rule of the arithmetic) misses it and flips that sample: nsamples > 1 exists for this case."""
+        _check_method(method)
+        n = _check_nsamples(nsamples)
+        q = _as_rows(query, 3, "query")
+        shape = tuple(q.shape[:-1])
+        if q.numel() // 3 * n >= 2 ** 31:
+            raise ValueError(f"query: {q.numel() // 3} points by {n} samples, at most 2^31 - 1 rays")
+        self._build()
+        with torch.cuda.device(self.dev):
+            q = q.to(self.dev).to(torch.float32).reshape(-1, 3)
+            m = int(q.shape[0])
+            rays = torch.empty(n, m, 6, dtype=torch.float32, device=self.dev)
+            rays[:, :, :3] = q[None]
+            rays[:, :, 3:] = torch.tensor(OCCUPANCY_DIRECTIONS[:n], dtype=torch.float32, device=self.dev)[:, None, :]
+            odd = (self.count_intersections(rays, method=method) & 1).sum(0)
+            occ = (2 * odd > n).to(torch.float32)
+            occ = torch.where(torch.isfinite(q).all(1), occ, torch.full_like(occ, float("nan")))
+        return occ.reshape(shape)
+
+    def compute_signed_distance(self, query, nsamples: int = 1, method: str = "grid") -> torch.Tensor:
+        """query [..., 3] -> fp32 [...] device tensor: ``compute_distance``'s bits, negated where ``compute_occupancy(query, nsamples)`` is 1.
+        NaN (a non-finite query) stays NaN; a scene without a kept triangle gives +inf.  The sign is meaningful only for a CLOSED mesh and
+        undefined at distance ~ 0; an edge-on triangle on a sample's ray can flip that sample, which nsamples > 1 outvotes."""
+        occ = self.compute_occupancy(query, nsamples=nsamples, method=method)
+        d = self.compute_distance(query, method=method)
+        return torch.where(occ == 1.0, -d, d)

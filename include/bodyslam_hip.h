@@ -891,8 +891,28 @@ int bs_pc_voxel_finish(const float* points, const float* colors, const float* no
  *                          (fallback_count int32 [1]) for bs_mesh_cast_brute with that list
  *   bs_mesh_closest_grid   one thread per point walks the Chebyshev shells of the point grid (pc_walk) over the references; a point still
  *                          searching after shell_cap goes onto the list for bs_mesh_closest_brute
+ *   bs_mesh_hits_grid      every hit of a ray, not the nearest -- Open3D's RaycastingScene.count_intersections, list_intersections and
+ *                          test_occlusions (compute_occupancy and compute_signed_distance are composed from the counts); parity UNPINNED, the
+ *                          statement is tests/_mesh_hits_ref.py.  The walk of bs_mesh_cast_grid without its early stop; a triangle is tested
+ *                          only in the first visited cell of its cell range, so every hit is met exactly once.  tnear <= t <= tfar (not NaN).
+ *                          mode BS_MESH_HITS_COUNT: out int32 [m] = the hits of the COUNTING predicate -- cast_rays' arithmetic, except that an
+ *                          edge value of exactly 0 takes the sign it would have with the ray moved by (eps, eps^2) in the sheared plane, so
+ *                          that exactly one of the triangles at a shared edge or vertex claims the ray.  BS_MESH_HITS_ANY: out = 1 when the
+ *                          CLOSED predicate of bs_mesh_cast_grid has a hit (Open3D's test_occlusions; with tnear 0, tfar +inf it is
+ *                          t_hit < inf of that call), else 0.  BS_MESH_HITS_FILL: row_start int64 [m + 1] is the caller's exclusive scan of
+ *                          COUNT's out, total = row_start[m] in [1, 2^31); the keys (t bits << 32 | global index) of a ray's hits go to keys
+ *                          [row_start[i], row_start[i + 1]) in walk order, nothing beyond the segment.  The caller sorts the rows with
+ *                          bs_pc_radius_sort (t >= +0: the key order is the order of (t, index)).  The pointers a mode does not use may be NULL.
+ *                          Rays the padding does not cover go onto fallback_list with out = 0, as in bs_mesh_cast_grid
+ *   bs_mesh_hits_brute     the same three modes for the rays of list (or the rows 0 .. m - 1) against every triangle: COUNT adds to out [n_rows]
+ *                          (integer atomics; zeroed here without a list, by bs_mesh_hits_grid with one), FILL takes slots from cursor int32 [m]
+ *                          (zeroed here), so the order inside a row is not fixed before the sort.  Parity UNPINNED as above
+ *   bs_mesh_hits_unpack    row j of the sorted keys, ray_ids int64 [total] (the ray of every row): the triangle is evaluated again under the
+ *                          counting predicate -- t_hit, geometry_ids, primitive_ids [total], primitive_uvs [total, 2] as bs_mesh_cast_brute
+ *                          writes them (Open3D's list_intersections; parity UNPINNED)
  * list rows are checked against n_rows, the rows of the ray / query array.  No floating-point atomics: the same bits in every run, for every
- * cell size.  Not built: BVHs, occlusion tests, intersection counts and lists, signed distance, occupancy. */
+ * cell size.  Not built: BVHs, a fused pinhole kernel. */
+enum { BS_MESH_HITS_COUNT = 0, BS_MESH_HITS_ANY = 1, BS_MESH_HITS_FILL = 2 };
 #define BS_MESH_MAX_TRIANGLES 536870912         /* 2^29 */
 #define BS_MESH_MAX_SAMPLED_TRIANGLES (1 << 22)
 int bs_mesh_records(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, void* records, int32_t* kept,
@@ -916,6 +936,15 @@ int bs_mesh_closest_grid(const void* records, int64_t n_triangles, const int32_t
                          float cell_size, const int32_t* dims, float pad, const float* query, int64_t m, float max_distance, int32_t shell_cap,
                          const int32_t* geom_start, int32_t n_geom, float* points, float* distance, int32_t* geometry_ids, int32_t* primitive_ids,
                          float* primitive_uvs, int32_t* fallback_list, int32_t* fallback_count, void* stream);
+int bs_mesh_hits_grid(const void* records, int64_t n_triangles, const int32_t* refs, const int32_t* cell_start, const float* lo, const float* hi,
+                      float cell_size, const int32_t* dims, float pad, float origin_limit, const float* rays, int64_t m, int32_t mode, float tnear,
+                      float tfar, int32_t* out, const int64_t* row_start, int64_t total, void* keys, int32_t* fallback_list,
+                      int32_t* fallback_count, void* stream);
+int bs_mesh_hits_brute(const void* records, int64_t n_triangles, const float* rays, int64_t n_rows, const int32_t* list, int64_t m, int32_t mode,
+                       float tnear, float tfar, int32_t* out, const int64_t* row_start, int64_t total, void* keys, int32_t* cursor, void* stream);
+int bs_mesh_hits_unpack(const void* records, int64_t n_triangles, const float* rays, int64_t n_rows, const void* keys, const int64_t* ray_ids,
+                        int64_t total, const int32_t* geom_start, int32_t n_geom, float* t_hit, int32_t* geometry_ids, int32_t* primitive_ids,
+                        float* primitive_uvs, void* stream);
 int bs_mesh_sample_weights(const void* records, int64_t n_triangles, double* area, void* top, int64_t* weights, void* stream);
 int bs_mesh_sample(const void* records, int64_t n_triangles, const int64_t* cum, const int32_t* triangles, const float* vertex_colors,
                    int64_t n_vertices, uint64_t seed, uint64_t first, int64_t n, float* points, float* colors, float* normals, int32_t* index,
