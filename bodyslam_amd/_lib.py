@@ -234,6 +234,16 @@ _SIGS = {
     "bs_mesh_triangle_geometry": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "bs_mesh_vertex_normals": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "bs_mesh_laplacian_step": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p, C.c_void_p],
+    # is this mesh a solid (csrc/mesh_solid.hip); every pointer is a device pointer
+    "bs_mesh_fan_hook": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_fan_compress": [C.c_void_p, C.c_int64, C.c_void_p],
+    "bs_mesh_fan_count": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_solid_records": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "bs_mesh_pairs_grid": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                           C.c_float, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5,
+    "bs_mesh_pairs_brute": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] +
+                           [C.c_void_p] * 4,
+    "bs_mesh_signed_volume": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     # rigid ICP registration (csrc/icp.hip); lo, hi and dims are pointers to host arrays
     "bs_icp_step": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                     C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -1788,3 +1798,95 @@ def mesh_laplacian_step(src, nbr_start, nbr, lam, clamp, out):
     assert out.shape[0] == V and nbr_start.numel() == V + 1 and src.data_ptr() != out.data_ptr()
     check(load_library().bs_mesh_laplacian_step(p(src), V, p(nbr_start), p(nbr) if nbr.numel() else None, nbr.numel(), float(lam), int(bool(clamp)),
                                                 p(out), stream_ptr()), "bs_mesh_laplacian_step")
+
+
+# ---- is this mesh a solid (csrc/mesh_solid.hip) -----------------------------------------------------------------------------------------
+MESH_PAIRS_COUNT, MESH_PAIRS_ANY, MESH_PAIRS_FILL = 0, 1, 2
+
+
+def mesh_fan_hook(triangles, edge_of_half, edge_first_triangle, parent, changed):
+    """triangles int32 [T, 3], edge_of_half int32 [3 T], edge_first_triangle int32 [E], parent int32 [3 T] over the corners, changed int32 [1]"""
+    T = _tri(triangles)
+    _i32(edge_of_half, edge_first_triangle, parent, changed)
+    assert edge_of_half.numel() == 3 * T and parent.numel() == 3 * T and changed.numel() >= 1
+    check(load_library().bs_mesh_fan_hook(p(triangles), T, p(edge_of_half), p(edge_first_triangle), edge_first_triangle.numel(), p(parent), p(changed),
+                                          stream_ptr()), "bs_mesh_fan_hook")
+
+
+def mesh_fan_compress(parent):
+    _i32(parent)
+    check(load_library().bs_mesh_fan_compress(p(parent), parent.numel(), stream_ptr()), "bs_mesh_fan_compress")
+
+
+def mesh_fan_count(triangles, n_vertices, edge_of_half, parent, count):
+    """count int32 [V] zeroed: the corner classes at every vertex"""
+    T = _tri(triangles)
+    _i32(edge_of_half, parent, count)
+    assert edge_of_half.numel() == 3 * T and parent.numel() == 3 * T and count.numel() == n_vertices >= 1
+    check(load_library().bs_mesh_fan_count(p(triangles), T, int(n_vertices), p(edge_of_half), p(parent), p(count), stream_ptr()), "bs_mesh_fan_count")
+
+
+def mesh_solid_records(vertices, triangles, records, kept):
+    """vertices fp32 [V, 3], triangles int32 [T, 3], records fp32 [T, 3, 4] (the vertex rows in the fourth lanes), kept int32 [1]"""
+    _pts(vertices)
+    T = _tri(triangles)
+    _i32(kept)
+    assert kept.numel() >= 1 and vertices.shape[0] >= 1
+    _mesh_records(records, T)
+    check(load_library().bs_mesh_solid_records(p(vertices), vertices.shape[0], p(triangles), T, p(records), p(kept), stream_ptr()), "bs_mesh_solid_records")
+
+
+def _mesh_pairs(q_records, records, mode, out, row_start, keys, any_flag):
+    """the sink of a bs_mesh_pairs_* call -> (n_q, n_triangles, total)"""
+    n_q, T = q_records.shape[0], records.shape[0]
+    _mesh_records(q_records, n_q)
+    _mesh_records(records, T)
+    assert mode in (MESH_PAIRS_COUNT, MESH_PAIRS_ANY, MESH_PAIRS_FILL) and n_q >= 1 and T >= 1
+    total = 0
+    if mode == MESH_PAIRS_COUNT:
+        _i32(out)
+        assert out.numel() == n_q
+    elif mode == MESH_PAIRS_ANY:
+        _i32(any_flag)
+        assert any_flag.numel() >= 1
+    else:
+        _i64(row_start, keys)
+        assert row_start.numel() == n_q + 1 and keys.numel() >= 1
+        total = keys.numel()
+    return n_q, T, total
+
+
+def mesh_pairs_grid(q_records, records, refs, cell_start, grid, self_mode, cell_cap, mode, out, row_start, keys, any_flag, fallback_list, fallback_count):
+    """the intersecting pairs of the query triangles the walk covers into the sink of `mode`; the others on fallback_list int32 [>= n_q]"""
+    n_q, T, total = _mesh_pairs(q_records, records, mode, out, row_start, keys, any_flag)
+    (lo_, lo_p), (hi_, hi_p), h, (d_, d_p), pad = _mesh_grid(grid)
+    _mesh_index(refs, cell_start, d_, fallback_list, fallback_count, n_q)
+    check(load_library().bs_mesh_pairs_grid(p(q_records), n_q, p(records), T, p(refs), refs.numel(), p(cell_start), lo_p, hi_p, h, d_p, pad,
+                                            int(bool(self_mode)), int(cell_cap), int(mode), p(out), p(row_start), total, p(keys), p(any_flag),
+                                            p(fallback_list), p(fallback_count), stream_ptr()), "bs_mesh_pairs_grid")
+
+
+def mesh_pairs_brute(q_records, fallback_list, m, records, self_mode, mode, out, row_start, keys, cursor, any_flag):
+    """the query triangles of fallback_list (int32, m of them; None: all) against every triangle into the sink of `mode`; cursor int32 [>= m]
+    scratch for FILL"""
+    n_q, T, total = _mesh_pairs(q_records, records, mode, out, row_start, keys, any_flag)
+    if fallback_list is None:
+        assert m == n_q
+    else:
+        _i32(fallback_list)
+        assert 1 <= m <= fallback_list.numel()
+    if mode == MESH_PAIRS_FILL:
+        _i32(cursor)
+        assert cursor.numel() >= m
+    check(load_library().bs_mesh_pairs_brute(p(q_records), n_q, p(fallback_list), int(m), p(records), T, int(bool(self_mode)), int(mode), p(out),
+                                             p(row_start), total, p(keys), p(cursor), p(any_flag), stream_ptr()), "bs_mesh_pairs_brute")
+
+
+def mesh_signed_volume(vertices, triangles, parent, vol6):
+    """parent int32 [T]: bs_mesh_cc_compress' fixed point; vol6 fp64 [T]"""
+    _pts(vertices)
+    T = _tri(triangles)
+    _i32(parent)
+    _f64(vol6)
+    assert parent.numel() == T and vol6.numel() == T and vertices.shape[0] >= 1
+    check(load_library().bs_mesh_signed_volume(p(vertices), vertices.shape[0], p(triangles), T, p(parent), p(vol6), stream_ptr()), "bs_mesh_signed_volume")

@@ -419,12 +419,7 @@ __global__ void __launch_bounds__(MS_THREADS) ms_closest_finish_kernel(const f32
 }
 
 // ---- the grid ------------------------------------------------------------------------------------------------------------------------------
-// The cells of one axis a kept triangle is referenced from (a, b, c: its three coordinates on that axis): what the build scatters to and
-// what the counting walk takes the first cell of a run from -- one expression, so the two cannot disagree.
-__device__ __forceinline__ void ms_cell_range(float a, float b, float c, float pad, float lo, float h, int n, int& c0, int& c1) {
-    c0 = pc_cell(fminf(fminf(a, b), c) - pad, lo, h, n);
-    c1 = pc_cell(fmaxf(fmaxf(a, b), c) + pad, lo, h, n);
-}
+// (ms_cell_range, the cells of one axis a kept triangle is referenced from, is in triangle.h: mesh_solid.hip walks the same grid)
 
 // SCATTER false: counts[cell] += 1 for every cell the triangle's padded box overlaps.  SCATTER true: `counts` is the cursor (a copy of the
 // exclusive scan) and the triangle's index goes to its slot.  The loops run over the triangle's own cell range, inside the grid.

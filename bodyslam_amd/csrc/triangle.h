@@ -58,4 +58,12 @@ __device__ __forceinline__ void tri_cross64(const P a, const P b, const P c, dou
 }
 __device__ __forceinline__ double tri_area64(const double (&n)[3]) { return 0.5 * sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]); }
 
+// The cells of one axis a kept triangle is referenced from in the triangle grid (a, b, c: its three coordinates on that axis): what the
+// build scatters to (mesh_scene.hip), what the counting walk takes the first cell of a run from, and what the pair search takes the first
+// common cell of two triangles from (mesh_solid.hip) -- one expression, so they cannot disagree.
+__device__ __forceinline__ void ms_cell_range(float a, float b, float c, float pad, float lo, float h, int n, int& c0, int& c1) {
+    c0 = pc_cell(fminf(fminf(a, b), c) - pad, lo, h, n);
+    c1 = pc_cell(fmaxf(fmaxf(a, b), c) + pad, lo, h, n);
+}
+
 }  // namespace bs

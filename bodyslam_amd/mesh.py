@@ -18,8 +18,15 @@ CPU fallback.
 union-find with one parity bit per link over the two-triangle edges (csrc/union_parity.h); the statement is
 tests/_orient_ref.py.
 
-Not built: Open3D's vertex-manifold and self-intersection tests and hence is_watertight, outward orientation of closed components by signed
-volume, simplification, subdivision, hole filling, signed distance."""
+Is the mesh a solid (csrc/mesh_solid.hip; the statement is tests/_mesh_solid_ref.py): ``get_non_manifold_vertices`` /
+``is_vertex_manifold``, ``get_self_intersecting_triangles`` / ``is_self_intersecting``, ``get_intersecting_triangles`` / ``is_intersecting``,
+``is_watertight``, ``component_volumes`` / ``get_volume``, ``orient_outward`` and ``check_solid`` -- Open3D's predicate family restated,
+parity unpinned.  Every decision is a sign of a fixed-order fp64 expression or an exact comparison: the same result in every run, for
+every grid and table size.
+
+Not built: exact arithmetic beyond fp64 (a determinant below the bound of DESIGN 3.26 takes the sign the stated arithmetic gives it),
+intersections of triangles that share a vertex, welding (merge_close_vertices), simplification, subdivision, hole filling or any other
+repair, booleans."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -33,6 +40,11 @@ from . import _lib as L
 
 last_rounds = 0          # the (hook, compress) rounds of the latest cluster_connected_triangles, the final unchanged one included
 last_orient_rounds = 0   # the (hook, compress) rounds of the latest orient_triangles / is_orientable / orientable_components, likewise
+last_fan_rounds = 0      # the (hook, compress) rounds of the latest get_non_manifold_vertices / is_vertex_manifold, likewise
+last_fallback = 0        # the query triangles of the latest grid search for intersecting pairs that were finished by brute force
+PAIR_METHODS = ("auto", "grid", "brute")
+PAIR_CELL_CAP = 512      # a query triangle whose cell box holds more cells than this is finished by brute force (a starting point, not tuned)
+PAIR_AUTO_BRUTE = 1 << 16    # method="auto": brute force when (query triangles) x (triangles) is at most this, the grid otherwise
 
 
 @dataclass
@@ -168,7 +180,8 @@ def _segment_sums(values: torch.Tensor, start: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _clusters(v, t, slots):
+def _clusters(v, t, slots, per_triangle=None):
+    """per_triangle(me, parent) -> fp64 [T]: what to sum per cluster; None: the areas of the kept triangles"""
     dev, T = t.device, int(t.shape[0])
     i32 = dict(dtype=torch.int32, device=dev)
     if T == 0:
@@ -183,8 +196,11 @@ def _clusters(v, t, slots):
     L.mesh_cc_clusters(parent, me.edge_of_half, rank, clusters, n_tri)
     c_area = torch.empty(0, dtype=torch.float64, device=dev)
     if C:
-        area = torch.empty(T, dtype=torch.float64, device=dev)
-        L.mesh_triangle_geometry(_safe_vertices(v), t, area=area)
+        if per_triangle is None:
+            area = torch.empty(T, dtype=torch.float64, device=dev)
+            L.mesh_triangle_geometry(_safe_vertices(v), t, area=area)
+        else:
+            area = per_triangle(me, parent)
         order = torch.sort(clusters, stable=True)[1]                                             # (the sort and the gather are plumbing)
         start = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(n_tri.to(torch.int64), 0)]) + (T - int(n_tri.sum().cpu()))
         c_area = _segment_sums(area[order].contiguous(), start.contiguous())
@@ -288,6 +304,325 @@ def get_surface_area(vertices, triangles=None, device: int = 0) -> float:
         area = torch.empty(T, dtype=torch.float64, device=dev)
         L.mesh_triangle_geometry(_safe_vertices(v), t, area=area)
         return float(_segment_sums(area, torch.tensor([0, T], dtype=torch.int64, device=dev)).cpu()[0])
+
+
+# ---- is the mesh a solid: vertex fans, intersecting pairs, volume (csrc/mesh_solid.hip) -------------------------------------------------------
+def _fan_counts(t: torch.Tensor, n_vertices: int, me: MeshEdges) -> torch.Tensor:
+    """int32 [V]: the classes of corners at every vertex.  A round that reports a change removes a root for good: the cap is 3 T + 1 rounds."""
+    global last_fan_rounds
+    dev, T = t.device, int(t.shape[0])
+    parent = torch.arange(3 * T, dtype=torch.int32, device=dev)
+    changed = torch.zeros(1, dtype=torch.int32, device=dev)
+    last_fan_rounds = 0
+    for _ in range(3 * T + 1):
+        changed.zero_()
+        L.mesh_fan_hook(t, me.edge_of_half, me.edge_first_triangle, parent, changed)
+        L.mesh_fan_compress(parent)
+        last_fan_rounds += 1
+        if int(changed.cpu()) == 0:
+            break
+    else:
+        raise L.BodySlamHipError(f"get_non_manifold_vertices: no fixed point after {3 * T + 1} rounds")
+    count = torch.zeros(n_vertices, dtype=torch.int32, device=dev)
+    L.mesh_fan_count(t, n_vertices, me.edge_of_half, parent, count)
+    return count
+
+
+def _non_manifold_vertices(v, t, slots) -> torch.Tensor:
+    T, V = int(t.shape[0]), int(v.shape[0])
+    if T == 0 or V == 0:
+        return torch.empty(0, dtype=torch.int32, device=t.device)
+    return torch.nonzero(_fan_counts(t, V, _edge_rows(t, V, slots)) > 1)[:, 0].to(torch.int32)
+
+
+def get_non_manifold_vertices(vertices, triangles=None, slots: Optional[int] = None, device: int = 0) -> torch.Tensor:
+    """Open3D's get_non_manifold_vertices -> int32 [n] vertex rows, ascending.  A vertex is manifold when the valid triangles that contain it
+    form one set connected through shared edges that contain the vertex: one fan, closed or open (a boundary fan is manifold, and so is a
+    vertex in no valid triangle).  A bow-tie -- two fans that meet in the vertex alone -- is reported.  An edge of three or more triangles
+    connects all of them, so the end points of a non-manifold EDGE are not reported for that reason alone: ask get_non_manifold_edges.
+    csrc/mesh_solid.hip: union by minimum over the 3 T corners, rounds of (hook, compress) until nothing changes (``last_fan_rounds``),
+    then the classes per vertex counted with integer atomics.  The result does not depend on ``slots``."""
+    v, t = _as_mesh(vertices, triangles)
+    slots = _check_slots(slots, 3 * int(t.shape[0]))
+    dev = _device(v, t, device)
+    with torch.cuda.device(dev):
+        v, t = _on_device(v, t, dev)
+        return _non_manifold_vertices(v, t, slots)
+
+
+def is_vertex_manifold(vertices, triangles=None, slots: Optional[int] = None, device: int = 0) -> bool:
+    """Open3D's is_vertex_manifold: ``get_non_manifold_vertices`` is empty"""
+    return int(get_non_manifold_vertices(vertices, triangles, slots, device).shape[0]) == 0
+
+
+def _check_pair_args(method, cells):
+    if method not in PAIR_METHODS:
+        raise ValueError(f"unknown method {method!r}: one of {PAIR_METHODS}")
+    if cells is not None:
+        AR.integer(cells, "cells", 1, 1 << 20, "None or an integer in 1 .. 2^20")
+    return method, cells
+
+
+def _solid_records(v: torch.Tensor, t: torch.Tensor):
+    """-> (records fp32 [T, 3, 4] with the vertex rows in the fourth lanes, the number of kept triangles)"""
+    records = torch.empty(int(t.shape[0]), 3, 4, dtype=torch.float32, device=t.device)
+    kept = torch.empty(1, dtype=torch.int32, device=t.device)
+    L.mesh_solid_records(v, t, records, kept)
+    return records, int(kept.cpu())
+
+
+def _pair_grid(records: torch.Tensor, n_kept: int, cells: Optional[int]):
+    """The scene's triangle grid over the kept triangles of `records` (raycasting.RaycastingScene._build_grid: bounds, padding, count, scan,
+    scatter) -> (grid, cell_start, refs).  cells None: the scene's default cell size, grown by 1.25 until the limits hold; otherwise the
+    cell edge is the box's longest extent over `cells` (a little more, so that cells = 1 is one cell), and a broken limit is a ValueError."""
+    from . import pointcloud as PC
+    from .raycasting import grid_padding, max_references
+    dev, T = records.device, int(records.shape[0])
+    pts = records[records[:, 0, 3].contiguous().view(torch.int32) >= 0][:, :, :3].reshape(-1, 3)
+    lo, hi = pts.amin(0).cpu().numpy(), pts.amax(0).cpu().numpy()
+    pad, _ = grid_padding(lo, hi)
+    if cells is None:
+        h = PC.default_cell_size(lo, hi, n_kept)
+    else:
+        ext = float((hi.astype(np.float32) - lo.astype(np.float32)).max())
+        h = float(np.float32(ext / cells) * np.float32(1.0 + 2.0 ** -10)) if ext > 0.0 else 1.0
+    cap = max_references(T)
+    while True:
+        dims = PC.grid_dims(lo, hi, h)
+        n_cells, n_refs = PC.n_cells(dims), None
+        if n_cells <= L.PC_MAX_CELLS:
+            grid = (lo, hi, h, dims.astype(np.int32), pad)
+            counts = torch.zeros(n_cells, dtype=torch.int32, device=dev)
+            L.mesh_grid_count(records, T, grid, counts)
+            n_refs = int(counts.sum(dtype=torch.int64).cpu())
+            if n_refs <= cap:
+                break
+        if cells is not None:
+            what = f"{n_cells} cells, at most 2^24" if n_refs is None else f"{n_refs} references, at most {cap}"
+            raise ValueError(f"cells {cells}: a grid of {dims[0]} x {dims[1]} x {dims[2]} with {what}")
+        h = float(np.float32(h * 1.25))
+    cell_start = torch.zeros(n_cells + 1, dtype=torch.int32, device=dev)
+    cell_start[1:] = torch.cumsum(counts, 0).to(torch.int32)                              # (the scan is plumbing: integer, exact)
+    refs = torch.empty(max(n_refs, 1), dtype=torch.int32, device=dev)
+    L.mesh_grid_scatter(records, T, grid, cell_start[:-1].clone(), refs)
+    return grid, cell_start, refs
+
+
+def _pairs(a, b, method: str, cells: Optional[int], want_list: bool, device: int):
+    """the intersecting pairs of mesh a with itself (b None) or with mesh b -> int32 [n, 2] (want_list) or bool"""
+    global last_fallback
+    method, cells = _check_pair_args(method, cells)
+    va, ta = _as_mesh(*a)
+    vb, tb = _as_mesh(*b) if b is not None else (None, None)
+    dev = _device(va, ta, device) if b is None else AR.device_for(va, ta, vb, tb, device=device)
+    with torch.cuda.device(dev):
+        i32 = dict(dtype=torch.int32, device=dev)
+        last_fallback = 0
+        none = torch.empty(0, 2, **i32) if want_list else False
+        va, ta = _on_device(va, ta, dev)
+        if b is not None:
+            vb, tb = _on_device(vb, tb, dev)
+        if min(ta.shape[0], va.shape[0]) == 0 or (b is not None and min(tb.shape[0], vb.shape[0]) == 0):
+            return none
+        q_rec, q_kept = _solid_records(va, ta)
+        rec, kept = (q_rec, q_kept) if b is None else _solid_records(vb, tb)
+        if q_kept == 0 or kept == 0:
+            return none
+        n_q, self_mode = int(q_rec.shape[0]), b is None
+        if method == "auto":
+            method = "brute" if n_q * int(rec.shape[0]) <= PAIR_AUTO_BRUTE else "grid"
+        index = _pair_grid(rec, kept, cells) if method == "grid" else None
+
+        def run(mode, out=None, row_start=None, keys=None, flag=None):
+            global last_fallback
+            if index is None:
+                cursor = torch.empty(n_q, **i32) if mode == L.MESH_PAIRS_FILL else None
+                L.mesh_pairs_brute(q_rec, None, n_q, rec, self_mode, mode, out, row_start, keys, cursor, flag)
+                return
+            grid, cell_start, refs = index
+            fb_list, fb_count = torch.empty(n_q, **i32), torch.empty(1, **i32)
+            L.mesh_pairs_grid(q_rec, rec, refs, cell_start, grid, self_mode, PAIR_CELL_CAP, mode, out, row_start, keys, flag, fb_list, fb_count)
+            last_fallback = int(fb_count.cpu())
+            if last_fallback:
+                cursor = torch.empty(last_fallback, **i32) if mode == L.MESH_PAIRS_FILL else None
+                L.mesh_pairs_brute(q_rec, fb_list, last_fallback, rec, self_mode, mode, out, row_start, keys, cursor, flag)
+
+        if not want_list:
+            flag = torch.zeros(1, **i32)
+            run(L.MESH_PAIRS_ANY, flag=flag)
+            return bool(int(flag.cpu()))
+        counts = torch.zeros(n_q, **i32)
+        run(L.MESH_PAIRS_COUNT, out=counts)
+        splits = torch.zeros(n_q + 1, dtype=torch.int64, device=dev)
+        splits[1:] = torch.cumsum(counts, 0, dtype=torch.int64)                           # (the scan is plumbing: integer, exact)
+        total = int(splits[-1].cpu())
+        if total > 2 ** 31 - 1:
+            raise L.BodySlamHipError(f"intersecting triangles: {total} pairs, at most 2^31 - 1")
+        if total == 0:
+            return none
+        keys, ordered = torch.empty(total, dtype=torch.int64, device=dev), torch.empty(total, dtype=torch.int64, device=dev)
+        run(L.MESH_PAIRS_FILL, row_start=splits, keys=keys)
+        L.pc_radius_sort(keys, splits, ordered)
+        return torch.stack([ordered >> 32, ordered & 0xFFFFFFFF], 1).to(torch.int32)      # (unpacking the keys is plumbing)
+
+
+def get_self_intersecting_triangles(vertices, triangles=None, method: str = "auto", cells: Optional[int] = None, device: int = 0) -> torch.Tensor:
+    """Open3D's get_self_intersecting_triangles -> int32 [n, 2]: the pairs (i, j), i < j, of KEPT triangles that have a point in common,
+    rows in ascending (i, j).  Triangles are closed sets: touching in one point counts.  Only pairs that share no vertex INDEX are tested
+    (Open3D's rule): a triangle folded onto its neighbour is therefore not found, and a mesh that is not welded -- the same position under
+    several vertex rows -- reports every seam.  Candidates are the pairs whose fp32 boxes overlap; the decision is Guigue & Devillers'
+    test over the signs of orient3d, each computed once in fp64 in the order of the vertex rows, and an edge-separation test over
+    orient2d for coplanar pairs (tests/_mesh_solid_ref.py): exact whenever a determinant exceeds 2^-50 of the sum
+    of its products, and the stated arithmetic's answer otherwise.  method: "grid" walks the scene's triangle grid (cells: the cells
+    along the box's longest side; None: the scene's default) and finishes the triangles whose cell box is too large by brute force
+    (``last_fallback``); "brute" tests everything against everything; "auto" picks brute force for small inputs.  The method and the
+    grid change the time, never the result.  More than 2^31 - 1 pairs: BodySlamHipError."""
+    return _pairs((vertices, triangles), None, method, cells, True, device)
+
+
+def is_self_intersecting(vertices, triangles=None, method: str = "auto", cells: Optional[int] = None, device: int = 0) -> bool:
+    """Open3D's is_self_intersecting: ``get_self_intersecting_triangles`` is not empty, found by a search that stops at the first pair"""
+    return _pairs((vertices, triangles), None, method, cells, False, device)
+
+
+def _two(mesh_a, mesh_b):
+    return tuple((m, None) if not isinstance(m, (tuple, list)) else tuple(m) for m in (mesh_a, mesh_b))
+
+
+def get_intersecting_triangles(mesh_a, mesh_b, method: str = "auto", cells: Optional[int] = None, device: int = 0) -> torch.Tensor:
+    """int32 [n, 2]: every pair (i of mesh_a, j of mesh_b) of kept triangles with a point in common, ascending; the predicate of
+    ``get_self_intersecting_triangles`` (mesh_a is the lower mesh).  mesh_a, mesh_b: a tsdf.TriangleMesh or a (vertices, triangles)
+    pair each.  The grid is mesh_b's."""
+    a, b = _two(mesh_a, mesh_b)
+    return _pairs(a, b, method, cells, True, device)
+
+
+def is_intersecting(mesh_a, mesh_b, method: str = "auto", cells: Optional[int] = None, device: int = 0) -> bool:
+    """Open3D's is_intersecting(other): a triangle of mesh_a and one of mesh_b have a point in common"""
+    a, b = _two(mesh_a, mesh_b)
+    return _pairs(a, b, method, cells, False, device)
+
+
+def _component_volumes(v, t, slots):
+    """-> (triangle_clusters int32 [T], volume fp64 [C], NaN where the cluster is not closed or not consistently wound)"""
+    T = int(t.shape[0])
+    bad_half = []
+
+    def vol6(me, parent):
+        e = me.edge_of_half.to(torch.int64).clamp(min=0)
+        bad_half.append((me.edge_of_half >= 0) & ((me.edge_count[e] != 2) | (me.edge_forward[e] != 1)))
+        out = torch.empty(T, dtype=torch.float64, device=t.device)
+        L.mesh_signed_volume(_safe_vertices(v), t, parent, out)
+        return out
+    clusters, n_tri, six = _clusters(v, t, slots, vol6)
+    if six.numel() == 0:
+        return clusters, six
+    bad = torch.zeros(six.numel(), dtype=torch.bool, device=t.device)                      # (integers and masks: plumbing)
+    rows = bad_half[0].reshape(T, 3).any(1) & (clusters >= 0)
+    bad[clusters[rows].to(torch.int64)] = True
+    return clusters, torch.where(bad, torch.full_like(six, float("nan")), six * (1.0 / 6.0))
+
+
+def component_volumes(vertices, triangles=None, slots: Optional[int] = None, device: int = 0):
+    """-> (triangle_clusters int32 [T], volume fp64 [C]): the signed volume of every cluster of cluster_connected_triangles, positive when
+    the cluster is wound outwards.  Per kept triangle a . (b x c) in fp64, a, b, c the differences of its vertices to the first vertex
+    of the cluster's smallest triangle -- so a cluster's volume depends on no other cluster and not on where the mesh lies --, summed in
+    cluster_area's fixed order and multiplied by 1 / 6.  NaN for a cluster that is not closed (an edge without exactly two triangles)
+    or not consistently oriented: it has no volume."""
+    v, t = _as_mesh(vertices, triangles)
+    slots = _check_slots(slots, 3 * int(t.shape[0]))
+    dev = _device(v, t, device)
+    with torch.cuda.device(dev):
+        v, t = _on_device(v, t, dev)
+        return _component_volumes(v, t, slots)
+
+
+def orient_outward(vertices, triangles=None, slots: Optional[int] = None, device: int = 0):
+    """``orient_triangles``, then every closed, consistently wound cluster whose signed volume is negative is turned inside out: the last
+    two corners of each of its triangles are swapped -> (triangles int32 [T, 3], flipped bool [T] against the input, solid bool [C]:
+    whether the cluster -- cluster_connected_triangles' numbering -- has a volume and now a non-negative one).  A cluster that is open
+    or cannot be wound consistently is left as ``orient_triangles`` leaves it and is reported False."""
+    out, flipped, _ = orient_triangles(vertices, triangles, slots, device)
+    v, t = _as_mesh(vertices, triangles)
+    with torch.cuda.device(out.device):
+        v = v.to(out.device).to(torch.float32).contiguous()
+        clusters, vol = _component_volumes(v, out, _check_slots(slots, 3 * int(out.shape[0])))
+        if vol.numel() == 0:
+            return out, flipped, torch.zeros(0, dtype=torch.bool, device=out.device)
+        turn = (clusters >= 0) & (vol[clusters.clamp(min=0).to(torch.int64)] < 0.0)
+        out = torch.where(turn[:, None], out[:, [0, 2, 1]], out)                           # (swapping two columns is plumbing)
+        return out, flipped ^ turn, ~torch.isnan(vol)
+
+
+@dataclass
+class SolidReport:
+    """check_solid's result"""
+    is_edge_manifold: bool              # every edge has exactly two triangles (Open3D's is_edge_manifold(allow_boundary_edges=False))
+    is_vertex_manifold: bool
+    is_self_intersecting: bool
+    is_watertight: bool                 # edge-manifold without boundary, vertex-manifold, not self-intersecting
+    is_consistently_oriented: bool
+    n_boundary_edges: int
+    n_non_manifold_edges: int           # edges with more than two triangles
+    n_non_manifold_vertices: int
+    n_intersecting_pairs: int
+    volume: Optional[float]             # get_volume's value when the mesh is watertight and consistently oriented, else None
+
+
+def is_watertight(vertices, triangles=None, method: str = "auto", cells: Optional[int] = None, slots: Optional[int] = None, device: int = 0) -> bool:
+    """Open3D's is_watertight: edge-manifold with no boundary edge allowed, vertex-manifold, and not self-intersecting -- evaluated in that
+    order, the cheap terms first, and no further than the first that fails"""
+    _check_pair_args(method, cells)
+    v, t = _as_mesh(vertices, triangles)
+    slots = _check_slots(slots, 3 * int(t.shape[0]))
+    dev = _device(v, t, device)
+    with torch.cuda.device(dev):
+        vd, td = _on_device(v, t, dev)
+        T, V = int(td.shape[0]), int(vd.shape[0])
+        if T and V:
+            me = _edge_rows(td, V, slots)
+            if not me.is_edge_manifold(False) or bool((_fan_counts(td, V, me) > 1).any()):
+                return False
+    return not is_self_intersecting(v, t, method, cells, device)
+
+
+def _total_volume(vol: torch.Tensor) -> float:
+    return abs(float(_segment_sums(vol.contiguous(), torch.tensor([0, vol.numel()], dtype=torch.int64, device=vol.device)).cpu()[0])) if vol.numel() else 0.0
+
+
+def get_volume(vertices, triangles=None, method: str = "auto", cells: Optional[int] = None, slots: Optional[int] = None, device: int = 0) -> float:
+    """Open3D's get_volume, with its precondition: ValueError naming the failed condition unless the mesh is watertight and consistently
+    oriented; otherwise abs of the sum of ``component_volumes`` (in cluster_area's fixed order)"""
+    r = check_solid(vertices, triangles, method, cells, slots, device)
+    if r.volume is None:
+        why = ("it has boundary or non-manifold edges" if not r.is_edge_manifold else "it has non-manifold vertices" if not r.is_vertex_manifold
+               else "it intersects itself" if r.is_self_intersecting else "it is not consistently oriented")
+        raise ValueError(f"get_volume: the mesh is not a watertight, consistently oriented solid: {why}")
+    return r.volume
+
+
+def check_solid(vertices, triangles=None, method: str = "auto", cells: Optional[int] = None, slots: Optional[int] = None, device: int = 0) -> SolidReport:
+    """Everything a user should know before trusting a signed distance or a volume -> SolidReport: the five verdicts, the counts behind
+    them, and the volume when the mesh has one.  An empty mesh is watertight and has volume 0."""
+    _check_pair_args(method, cells)
+    v, t = _as_mesh(vertices, triangles)
+    slots = _check_slots(slots, 3 * int(t.shape[0]))
+    dev = _device(v, t, device)
+    with torch.cuda.device(dev):
+        vd, td = _on_device(v, t, dev)
+        T, V = int(td.shape[0]), int(vd.shape[0])
+        me = _edge_rows(td, V, slots)
+        n_boundary, n_nm_edges = int(me.get_boundary_edges().shape[0]), int(me.get_non_manifold_edges().shape[0])
+        n_nm_vertices = int((_fan_counts(td, V, me) > 1).sum().cpu()) if T and V else 0
+        oriented = me.is_consistently_oriented()
+    n_pairs = int(get_self_intersecting_triangles(v, t, method, cells, device).shape[0])
+    watertight = n_boundary == 0 and n_nm_edges == 0 and n_nm_vertices == 0 and n_pairs == 0
+    volume = None
+    if watertight and oriented:
+        with torch.cuda.device(dev):
+            volume = _total_volume(_component_volumes(vd, td, slots)[1])
+    return SolidReport(n_boundary == 0 and n_nm_edges == 0, n_nm_vertices == 0, n_pairs > 0, watertight, oriented, n_boundary, n_nm_edges,
+                       n_nm_vertices, n_pairs, volume)
 
 
 # ---- normals -------------------------------------------------------------------------------------------------------------------------------

@@ -176,8 +176,7 @@ class TriangleMesh:
         self.triangle_normals, self.vertex_normals = triangle_normals, vertex_normals
 
     # ---- topology and clean-up: thin wrappers of bodyslam_amd/mesh.py, which states the rules; restated from Open3D's documentation, parity with
-    # Open3D unpinned.  Results are numpy for a mesh of numpy arrays and device tensors for a mesh of device tensors.  Open3D's vertex-manifold
-    # and self-intersection tests, and hence is_watertight, are not built.
+    # Open3D unpinned.  Results are numpy for a mesh of numpy arrays and device tensors for a mesh of device tensors.
     def _host(self) -> bool:
         return isinstance(self.vertices, np.ndarray)
 
@@ -225,10 +224,70 @@ class TriangleMesh:
         return TriangleMesh(self.vertices, self.vertex_colors, self._out(t)), self._out(flipped), ok
 
     def is_closed(self) -> bool:
-        """every edge has exactly two triangles; with is_consistently_oriented() the precondition of a signed distance (is_watertight, which
-        also wants vertex-manifoldness and no self-intersection, is not built)"""
+        """every edge has exactly two triangles; is_watertight() also wants vertex-manifoldness and no self-intersection, and with
+        is_consistently_oriented() it is the precondition of a signed distance and of get_volume()"""
         from .mesh import edge_topology
         return edge_topology(self.vertices, self.triangles).is_closed()
+
+    # ---- is the mesh a solid (mesh.py states the rules; csrc/mesh_solid.hip) ----------------------------------------------------------------
+    def get_non_manifold_vertices(self):
+        """o3d get_non_manifold_vertices: int32 [n], the vertices whose triangles form more than one fan (a bow-tie), ascending; the end
+        points of an edge with three or more triangles are not reported for that reason alone"""
+        from .mesh import get_non_manifold_vertices
+        return self._out(get_non_manifold_vertices(self.vertices, self.triangles))
+
+    def is_vertex_manifold(self) -> bool:
+        from .mesh import is_vertex_manifold
+        return is_vertex_manifold(self.vertices, self.triangles)
+
+    def get_self_intersecting_triangles(self, method: str = "auto", cells: Optional[int] = None):
+        """o3d get_self_intersecting_triangles: int32 [n, 2], the pairs i < j of triangles without a common vertex index that have a point
+        in common (touching counts), ascending"""
+        from .mesh import get_self_intersecting_triangles
+        return self._out(get_self_intersecting_triangles(self.vertices, self.triangles, method=method, cells=cells))
+
+    def is_self_intersecting(self, method: str = "auto", cells: Optional[int] = None) -> bool:
+        from .mesh import is_self_intersecting
+        return is_self_intersecting(self.vertices, self.triangles, method=method, cells=cells)
+
+    def get_intersecting_triangles(self, other: "TriangleMesh", method: str = "auto", cells: Optional[int] = None):
+        """int32 [n, 2]: the pairs (triangle of this mesh, triangle of `other`) that have a point in common, ascending"""
+        from .mesh import get_intersecting_triangles
+        return self._out(get_intersecting_triangles(self, other, method=method, cells=cells))
+
+    def is_intersecting(self, other: "TriangleMesh", method: str = "auto", cells: Optional[int] = None) -> bool:
+        """o3d is_intersecting(other)"""
+        from .mesh import is_intersecting
+        return is_intersecting(self, other, method=method, cells=cells)
+
+    def is_watertight(self) -> bool:
+        """o3d is_watertight: every edge has exactly two triangles, every vertex one fan, and no two triangles intersect -- what
+        compute_signed_distance, compute_occupancy and evaluate_reconstruction_signed assume of the mesh"""
+        from .mesh import is_watertight
+        return is_watertight(self.vertices, self.triangles)
+
+    def component_volumes(self):
+        """-> (triangle_clusters int32 [T], signed volume float64 [C] of every cluster, positive when wound outwards, NaN when the cluster
+        is open or not consistently oriented)"""
+        from .mesh import component_volumes
+        return tuple(self._out(x) for x in component_volumes(self.vertices, self.triangles))
+
+    def get_volume(self) -> float:
+        """o3d get_volume: ValueError unless the mesh is watertight and consistently oriented"""
+        from .mesh import get_volume
+        return get_volume(self.vertices, self.triangles)
+
+    def orient_outward(self):
+        """orient_triangles(), then every closed cluster with a negative signed volume turned inside out -> (a new TriangleMesh -- the
+        normals are not carried: they would be stale --, flipped bool [T], solid bool [C]: the clusters that have a volume)"""
+        from .mesh import orient_outward
+        t, flipped, solid = orient_outward(self.vertices, self.triangles)
+        return TriangleMesh(self.vertices, self.vertex_colors, self._out(t)), self._out(flipped), self._out(solid)
+
+    def check_solid(self):
+        """-> mesh.SolidReport: the verdicts, the counts behind them and the volume when the mesh has one"""
+        from .mesh import check_solid
+        return check_solid(self.vertices, self.triangles)
 
     def cluster_connected_triangles(self):
         """o3d cluster_connected_triangles -> (triangle_clusters int32 [T], cluster_n_triangles int32 [C], cluster_area float64 [C]); triangles

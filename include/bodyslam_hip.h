@@ -1005,7 +1005,7 @@ int bs_mesh_sample(const void* records, int64_t n_triangles, const int64_t* cum,
  *   bs_mesh_orient_flip    out int32 [T, 3] (not `triangles`): [a, c, b] for a valid triangle of an orientable component whose parity to the
  *                          component's smallest triangle is 1, every other row unchanged; flipped uint8 [T]
  * No floating-point atomics and no retry loops: the same bits in every run, for every table size and every order of the atomics.  Not built:
- * vertex-manifoldness, self-intersection and hence is_watertight, simplification, subdivision, hole filling. */
+ * simplification, subdivision, hole filling. */
 #define BS_MESH_EDGE_EMPTY_KEY 0xffffffffffffffffull
 #define BS_MESH_EDGE_NO_HALF 0x7fffffff
 enum { BS_MESH_EDGE_TABLE_FULL = 1 };
@@ -1037,6 +1037,63 @@ int bs_mesh_vertex_normals(const double* cross, int64_t n_triangles, const int64
                            float* normals, void* stream);
 int bs_mesh_laplacian_step(const float* in, int64_t n_vertices, const int64_t* nbr_start, const int32_t* nbr, int64_t n_nbr, double lambda,
                            int32_t clamp, float* out, void* stream);
+
+/* ---- is this mesh a solid (csrc/mesh_solid.hip) ----------------------------------------------------------------------------------------
+ * The roles of Open3D's TriangleMesh.get_non_manifold_vertices, is_vertex_manifold, get_self_intersecting_triangles, is_self_intersecting,
+ * is_intersecting, is_watertight and get_volume.  Restated from Open3D's documented meaning; parity with Open3D is UNPINNED.  The statement
+ * is tests/_mesh_solid_ref.py and every result equals it, in every run and for every grid; DESIGN section 3.26 is the argument.  All
+ * pointers are device pointers; VALID and KEPT are those of the mesh clean-up above.
+ *   bs_mesh_fan_hook       the elements are the corners 3 t + c of the valid triangles.  parent int32 [3 T] starts as 0 .. 3 T - 1.  One
+ *                          thread per half-edge h = 3 t + c (a = tri[t][c] -> b = tri[t][(c + 1) % 3]) of edge e with first triangle u =
+ *                          edge_first_triangle[e] hooks the corner of a in t with the corner of a in u, and likewise for b, by minimum as
+ *                          bs_mesh_cc_hook does (the same device function); changed int32 [1] = 1 when two roots differed.  An edge of three
+ *                          or more triangles joins them all
+ *   bs_mesh_fan_compress   parent[x] = root(x).  The caller repeats (zero changed, hook, compress) until changed stays 0: at most 3 T rounds
+ *                          report a change
+ *   bs_mesh_fan_count      count int32 [V] (zeroed) += 1 for every root corner of a valid triangle at the vertex: a vertex is NON-MANIFOLD iff
+ *                          its count exceeds 1 (a vertex in no valid triangle has count 0; a boundary fan has one class)
+ *   bs_mesh_solid_records  records [T, 3] of 16 bytes like bs_mesh_records', with the vertex rows in the fourth lanes: (x, y, z, row) per
+ *                          corner, and -1 in the first corner's lane of a triangle that is not kept, which is all bs_mesh_grid_count and
+ *                          bs_mesh_grid_scatter read of it.  kept int32 [1] = the kept triangles
+ *   bs_mesh_pairs_grid     the pairs (query triangle i of q_records, triangle j of records) of kept triangles that intersect as closed sets.
+ *                          self != 0: one mesh (q_records == records), pairs i < j without a common vertex row; else every pair of the two
+ *                          meshes.  Candidates: the closed fp32 boxes overlap.  The predicate is a function of the signs of orient3d -- each
+ *                          computed once, in the order of the four vertex ids (mesh, row): fp64 differences u, v, w to the lowest id, det =
+ *                          (ux (vy wz - vz wy) + uy (vz wx - vx wz)) + uz (vx wy - vy wx) without contraction, sign times the parity of the
+ *                          sort -- as in Guigue & Devillers' test, and of orient2d (likewise) when all three vertices of one triangle have
+ *                          sign 0 against the other's plane: the plane drops the axis of the largest component of triangle i's fp64 normal.
+ *                          One thread per query triangle walks the cells of its own cell box in the triangle grid of `records` (refs [n_refs],
+ *                          cell_start [cells + 1]: bs_mesh_grid_count / _scatter) and tests a pair only in the cell whose index per axis is
+ *                          the larger of the two boxes' first cells: each pair is met once.  A query triangle whose box has more than
+ *                          cell_cap cells goes onto fallback_list int32 [>= n_q] (fallback_count int32 [1]) for bs_mesh_pairs_brute.
+ *                          mode BS_MESH_PAIRS_COUNT: out int32 [n_q] = the pairs of each query triangle (0 for one on the list);
+ *                          BS_MESH_PAIRS_FILL: row_start int64 [n_q + 1] is the caller's exclusive scan of the counts, total = row_start[n_q]
+ *                          in [1, 2^31); the keys i << 32 | j go to keys [row_start[i], row_start[i + 1]), nothing beyond the segment; the
+ *                          caller sorts the rows (bs_pc_radius_sort).  BS_MESH_PAIRS_ANY: any int32 [1] (zeroed by the caller) is set when a
+ *                          pair exists; threads leave once it is set
+ *   bs_mesh_pairs_brute    the query triangles of list int32 [m] (NULL: all, m = n_q) against every triangle through LDS tiles, each pair in
+ *                          exactly one wave of one block, into the same sinks: COUNT adds to out (zeroed here when list is NULL), FILL takes
+ *                          slots from cursor int32 [>= m] (zeroed here)
+ *   bs_mesh_signed_volume  vol6 fp64 [T] = a . (b x c) = (ax (by cz - bz cy) + ay (bz cx - bx cz)) + az (bx cy - by cx) with a, b, c the fp64
+ *                          differences of a kept triangle's vertices to v[tri[parent[t]][0]] (parent: bs_mesh_cc_compress' fixed point), 0
+ *                          for any other triangle.  The caller sums a cluster with bs_mesh_segment_sum and multiplies by 1 / 6
+ * Integer atomics only.  Not built: exact arithmetic beyond fp64, pairs that share a vertex, welding, hole filling, booleans. */
+enum { BS_MESH_PAIRS_COUNT = 0, BS_MESH_PAIRS_ANY = 1, BS_MESH_PAIRS_FILL = 2 };
+int bs_mesh_fan_hook(const int32_t* triangles, int64_t n_triangles, const int32_t* edge_of_half, const int32_t* edge_first_triangle, int64_t n_edges,
+                     int32_t* parent, int32_t* changed, void* stream);
+int bs_mesh_fan_compress(int32_t* parent, int64_t n_corners, void* stream);
+int bs_mesh_fan_count(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, const int32_t* edge_of_half, const int32_t* parent,
+                      int32_t* count, void* stream);
+int bs_mesh_solid_records(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, void* records, int32_t* kept,
+                          void* stream);
+int bs_mesh_pairs_grid(const void* q_records, int64_t n_q, const void* records, int64_t n_triangles, const int32_t* refs, int64_t n_refs,
+                       const int32_t* cell_start, const float* lo, const float* hi, float cell_size, const int32_t* dims, float pad, int32_t self,
+                       int64_t cell_cap, int32_t mode, int32_t* out, const int64_t* row_start, int64_t total, void* keys, int32_t* any,
+                       int32_t* fallback_list, int32_t* fallback_count, void* stream);
+int bs_mesh_pairs_brute(const void* q_records, int64_t n_q, const int32_t* list, int64_t m, const void* records, int64_t n_triangles, int32_t self,
+                        int32_t mode, int32_t* out, const int64_t* row_start, int64_t total, void* keys, int32_t* cursor, int32_t* any, void* stream);
+int bs_mesh_signed_volume(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const int32_t* parent,
+                          double* vol6, void* stream);
 
 /* ---- rigid ICP registration ------------------------------------------------------------------------------------------------------------
  * bs_icp_step + bs_icp_finish replace Open3D's pipelines.registration.registration_icp with TransformationEstimationPointToPlane or
